@@ -1,13 +1,20 @@
 """bench.py -- SAM-BERT training-step throughput on MI355X (BASELINE.json metric / config).
 
-  python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N>1: launched by torch.distributed.run)
 
 A "step" = one full training step of the hot path on one seeded synthetic batch per rank
 (B=32 phoneme sequences, T_in=64, ~612 mel frames): forward, the five masked-L1
 losses, backward, global-norm clip (1.0), fused Adam, NoamLR -- i.e. Sambert_Trainer.train_step
 (reference kantts/train/trainer.py:898-1005) with dropout on as shipped.  Inputs are resident in HBM
-before the timed region.  value = valid mel frames of all ranks / max-over-ranks wall time.
-Extra objects on the JSON line:
+before the timed region.  value = valid mel frames of all ranks / max-over-ranks wall time; ms_per_step = that wall time
+over the K timed steps.  A plain run does only that: set-up, W warm-up steps, K timed steps, the JSON line.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last of them computed as float32 DIR/<name>.npy (see
+dump_outputs).  Model, batch and dropout streams are seeded, and with --dump-outputs the last timed step starts from that
+seeded state (restore_training_state: one in-place copy of weights, Adam moments and counters, inside the timed window),
+so the same arguments give the same inputs to it in every run; config.final_loss is then that step's loss.  A plain run
+does not restore: its final_loss is the loss after 1 + W + K steps.
+--full: everything else below, after the timed steps (the data-parallel exchange probe as well).
+Extra objects on the JSON line (--full only):
   "roofline"     dominant kernel of the step = the MFMA GEMM on the decoder-FFN contractions.  With fp32 activations in
                  HBM these are bandwidth-bound (57 flop/byte against a machine balance of ~310), so the binding roof
                  is HBM: achieved = algorithmic bytes (A + B + C once, fp32) / mean launch duration, each contraction
@@ -23,9 +30,10 @@ Extra objects on the JSON line:
                  roofline (rank 0, N=1 only; --no-hifigan skips it).
 Progress markers go to stderr ("[bench  12.3 s] ...").  --backend gloo --share-device runs the N-rank code path on ONE GPU (a
 functional check of spawn / rendezvous / barrier / max-over-ranks / the exchange between the two graphs, not a scaling
-figure); --no-roofline / --no-forward-only / --no-fp32 / --no-inference / --no-cpu-baseline trim legs for experiment runs.
+figure); --no-roofline / --no-forward-only / --no-fp32 / --no-inference / --no-cpu-baseline trim the legs of a --full run.
 """
 import argparse
+import copy
 import json
 import os
 import sys
@@ -1097,6 +1105,53 @@ def config5_parity(am, cfg, utts, idx, batch=32, threads=0, mode="kernel", voc=N
                              "sample": "%d of the leg's utterances through oracle/torch_oracle.py, %.1f s" % (len(ref), cpu_s)}}
 
 
+def training_state(optimizer, scheduler, dev):
+    """Copy of what a training step reads besides the batch and changes for the next one: weights, Adam moments and step
+    counts (host and device), learning rate, dropout offset."""
+    from kantts._hip import rng_state
+
+    return {"opt": optimizer.snapshot(), "sched": copy.deepcopy(scheduler.state_dict()),
+            "lr": [g["lr"] for g in optimizer.param_groups], "rng": rng_state(dev).clone()}
+
+
+def restore_training_state(state, optimizer, scheduler, dev):
+    """Put back a training_state() copy, in place (captured graphs keep the addresses of every buffer it writes)."""
+    from kantts._hip import rng_state
+
+    optimizer.restore(state["opt"])
+    scheduler.load_state_dict(copy.deepcopy(state["sched"]))
+    for g, lr in zip(optimizer.param_groups, state["lr"]):
+        g["lr"] = lr
+    optimizer.sync_lr()
+    rng_state(dev).copy_(state["rng"])
+
+
+DUMP_SAMPLE = 1 << 22  # positions of the weight / gradient sample: 2 x 16 MB of float32
+
+
+def dump_outputs(dirname, loss, optimizer, seed=0):
+    """--dump-outputs: what a caller of the timed training step holds after its last step, as float32 ``dirname/<name>.npy``:
+    ``loss`` (the step's objective), ``grad_norm`` (global gradient norm before clipping), ``weights`` (the updated
+    parameters) and ``grads`` (the step's gradients).  That step is the first training step from the seeded state
+    (main() restores it), whatever --steps / --warmup are: Adam's moments start at zero and NoamLR gives lr = 2.5e-7,
+    so ``weights`` is the seeded initialisation to about 1e-7 and the signal for comparing two builds is in ``loss``,
+    ``grad_norm`` and ``grads``.  ``weights`` and ``grads`` are every trainable parameter flattened and concatenated
+    in ``module.parameters()`` order; above DUMP_SAMPLE values, both keep the same fixed sample of positions (drawn with
+    ``seed``, sorted) so that the files stay small and two builds compare position for position."""
+    import numpy as np
+
+    arena = optimizer.arena
+    weights = torch.cat([p.detach().reshape(-1) for p in arena.params])
+    grads = torch.cat([g.reshape(-1) for g in arena.grad_views])
+    if weights.numel() > DUMP_SAMPLE:
+        idx = torch.randperm(weights.numel(), generator=torch.Generator().manual_seed(seed))[:DUMP_SAMPLE]
+        idx = idx.sort().values.to(weights.device)
+        weights, grads = weights[idx], grads[idx]
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in (("loss", loss.detach()), ("grad_norm", optimizer.grad_norm()), ("weights", weights), ("grads", grads)):
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
+
+
 def _spawn_ranks(n, argv):
     """`python bench.py --gpus N` outside a torch.distributed.run launch: re-exec under it (one rank per GPU of this
     node, rendezvous on 127.0.0.1) and pass its JSON line through."""
@@ -1118,6 +1173,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary measurement and check (roofline, forward pass, "
+                         "data-parallel exchange, fp32 / MAS / HiFi-GAN / mel-STFT / inference legs, CPU baselines, parity)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1143,6 +1203,8 @@ def main():
                          "(arena buckets, graph segments, the all-reduce between their replays, RCCL's init and its watchdog "
                          "thread beside relaxed-mode captures) executes on a one-GPU box; not a scaling figure")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     CPU_THREADS["n"] = args.cpu_threads or None
     if args.oracle_probe:
@@ -1204,12 +1266,15 @@ def main():
 
     mode = args.mode
     step = eager_step
+    seeded = None  # training state before the first step (the capture puts back what its warm-up changed)
     if mode == "graph":
         try:
             from kantts.train.graph_step import GraphedSambertStep
 
             step = GraphedSambertStep(net, optimizer, scheduler, mel_crit, pros_crit, batch,
                                       overlap_wgrad=not args.no_wgrad_overlap, group_wgrads=not args.no_wgrad_group)
+            if args.dump_outputs:
+                seeded = training_state(optimizer, scheduler, dev)
             step()  # first replay (and, data-parallel, the first all-reduce between the two graphs) inside the guard
             torch.cuda.synchronize()
         except Exception as exc:  # capture is an optimisation; say so loudly and measure the eager path
@@ -1220,6 +1285,9 @@ def main():
             hip.ops.wgrad_overlap.enable(False)
             net.device_band_width = False
             optimizer.dyn = None
+            seeded = None
+    if args.dump_outputs and seeded is None:
+        seeded = training_state(optimizer, scheduler, dev)
 
     _note("model built, step %s" % mode)
     for _ in range(args.warmup):
@@ -1228,7 +1296,12 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if args.dump_outputs and i == args.steps - 1:
+            # The dumped step starts from the seeded state, so its inputs are the same in every run.  Without this they
+            # would not be: the backward kernels sum with float atomics, and Adam turns that rounding, on gradients
+            # that are nothing but rounding, into whole learning-rate steps, so runs drift apart step by step.
+            restore_training_state(seeded, optimizer, scheduler, dev)
         loss = step()
     torch.cuda.synchronize()
     if distributed:
@@ -1249,13 +1322,16 @@ def main():
         per_rank_ms = [1e3 * float(a[0]) / args.steps for a in allt]
     else:
         dt_max, total_frames = dt, float(frames)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, optimizer)
+        _note("outputs of the last timed step written to %s" % args.dump_outputs)
 
     # ---- data-parallel runs: how much of the gradient exchange is NOT hidden behind backward.  The same captured step
     # replayed without its collectives (weights diverge between the replicas from here on: nothing after this point reads
     # them) -- exposed = step with the exchange - step without it, max over ranks.
     dp_info = None
     final_loss = float(loss.detach())
-    if distributed and mode == "graph":
+    if args.full and distributed and mode == "graph":
         dp_info = {"form": ("%d graph segments, one all-reduce per gradient bucket issued between the replays "
                             "(kantts/train/segments.py)" % len(step.segments.segments)) if step.segments is not None
                    else "two graphs: backward | bucketed all-reduce | update",
@@ -1285,7 +1361,7 @@ def main():
     # branch), replayed from its own hipGraph: SURVEY 8(d) prices the MFMA roofline on the forward pass
     # (152.3 GFLOP at batch 32: roofline.forward_mfma_frac = 152.3e9 / t_fwd / peak)
     fwd_ms = None
-    if rank == 0 and world == 1 and mode == "graph" and not args.no_forward_only:
+    if args.full and rank == 0 and world == 1 and mode == "graph" and not args.no_forward_only:
         try:
             def fwd_only():
                 hip.ops.advance_rng(dev)
@@ -1326,12 +1402,13 @@ def main():
 
     # ---- roofline of the dominant kernel: HIP events around every GEMM launch of one extra step
     roof = None
-    rank_roof = rank == 0 and not args.no_roofline
+    roofline = args.full and not args.no_roofline
+    rank_roof = rank == 0 and roofline
     if rank_roof:
         hip.profile_begin()
     net.device_band_width = False
     hip.ops.wgrad_overlap.enable(False, group_wgrads=not args.no_wgrad_group)
-    if not args.no_roofline:
+    if roofline:
         eager_step()  # instrumented launches are issued eagerly on every rank (the step holds a collective)
     torch.cuda.synchronize()
     if rank == 0 and args.no_roofline and fwd_ms is not None:
@@ -1426,18 +1503,19 @@ def main():
                        "collective_backend": (("nccl (RCCL)" if args.backend == "nccl" else "gloo") if distributed else None),
                        "shared_device": bool(args.share_device and distributed),
                        "data_parallel": dp_info},
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roof
         del step, net, optimizer, model, opt
         torch.cuda.empty_cache()
-        if world == 1 and args.precision != "fp32" and not args.no_fp32:
+        if args.full and world == 1 and args.precision != "fp32" and not args.no_fp32:
             try:  # the parity-proven path (fp32 MFMA) on the same step, beside the throughput (bf16) line
                 out["fp32_path"] = fp32_leg(hip, cfg, batch, frames, mel_crit, pros_crit, dev)
                 hip.set_precision(args.precision)
                 _note("fp32 leg done")
             except Exception as exc:
                 out["fp32_path"] = {"error": "%s: %s" % (type(exc).__name__, str(exc)[:300])}
-        if world == 1 and not args.no_fp32:
+        if args.full and world == 1 and not args.no_fp32:
             try:  # the MAS training step, captured since round 6
                 out["mas_step"] = mas_leg(hip, cfg, args.precision, dev)
                 hip.set_precision(args.precision)
@@ -1445,7 +1523,7 @@ def main():
             except Exception as exc:
                 out["mas_step"] = {"error": "%s: %s" % (type(exc).__name__, str(exc)[:300])}
             torch.cuda.empty_cache()
-        if world == 1 and not args.no_hifigan:
+        if args.full and world == 1 and not args.no_hifigan:
             try:
                 out["hifigan"] = hifigan_leg(hip, args.precision)
                 _note("HiFi-GAN leg done")
@@ -1459,14 +1537,14 @@ def main():
                 _note("mel-STFT leg done")
             except Exception as exc:
                 out["melspec"] = {"error": "%s: %s" % (type(exc).__name__, str(exc)[:300])}
-        if world == 1 and not args.no_inference:
+        if args.full and world == 1 and not args.no_inference:
             try:
                 out["inference"] = inference_leg(hip, cfg, args.precision, parity_utts=0 if args.no_cpu_baseline else 32,
                                                  cpu_threads=_cpu_threads())
                 _note("inference leg done")
             except Exception as exc:
                 out["inference"] = {"error": "%s: %s" % (type(exc).__name__, str(exc)[:300])}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"], out["parity_error"] = cpu_baseline(cfg, hip)
                 _note("SAM-BERT CPU baseline + parity done")

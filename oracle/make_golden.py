@@ -788,6 +788,95 @@ def dsp_melspec_case():
           {k: (v.shape, v.dtype) for k, v in fix["extract"]["mel_dict"].items()})
 
 
+def sketch(t, n=256):
+    """A tensor too large to store whole: shape, float64 sum and norm, and ``n`` values at evenly spaced flat positions
+    (torch.linspace(0, numel - 1, n).long(): the test takes the same positions without storing them)."""
+    t = t.detach()
+    flat = t.reshape(-1)
+    if flat.numel() <= n:
+        return {"shape": tuple(t.shape), "full": t.clone()}
+    idx = torch.linspace(0, flat.numel() - 1, n).long()
+    return {"shape": tuple(t.shape), "sum": float(t.double().sum()), "norm": float(t.double().norm()),
+            "sample": flat[idx].clone()}
+
+
+def check_cases_case():
+    """What oracle/check_vs_reference.py compares, recorded: SAM-BERT at the tiny (B=4, T_in=24) and the FULL (B=4,
+    T_in=48) configuration -- outputs, every attention map, losses, every parameter gradient -- HiFi-GAN G / MPD / MSD at
+    512 and 64 generator channels -- outputs, feature maps, every parameter gradient -- and one mel spectrogram.  Tensors
+    above 256 values are kept as sketch()es; inputs and weights are regenerated from the seeds by the test.  Written
+    to check_cases_sambert.pt (with the mel case) and check_cases_hifigan.pt."""
+    from kantts.models.hifigan.hifigan import Generator, MultiPeriodDiscriminator, MultiScaleDiscriminator
+
+    fix = {"sambert": {}, "hifigan": {}}
+    for name, tiny, B, T_in, min_len in (("tiny", True, 4, 24, 10), ("full", False, 4, 48, 20)):
+        cfg = O.sambert_config(tiny=tiny)
+        torch.manual_seed(0)
+        m = KanTtsSAMBERT(dict(cfg))
+        m.eval()
+        batch = O.synthetic_sambert_batch(B=B, T_in=T_in, min_len=min_len)
+        res = m(**batch)
+        mel_, mel = MelReconLoss()(batch["output_lengths"], batch["mel_targets"], res["dec_outputs"],
+                                   res["postnet_outputs"])
+        d, p, e = ProsodyReconLoss()(batch["input_lengths"], res["duration_targets"], res["pitch_targets"],
+                                     res["energy_targets"], res["log_duration_predictions"], res["pitch_predictions"],
+                                     res["energy_predictions"])
+        total = mel_ + mel + d + p + e
+        total.backward()
+        fix["sambert"][name] = dict(
+            tiny=tiny, batch_args=dict(B=B, T_in=T_in, min_len=min_len), weight_checksums=checksums(m.state_dict()),
+            outputs={k: sketch(res[k]) for k in ("dec_outputs", "postnet_outputs", "log_duration_predictions",
+                                                 "pitch_predictions", "energy_predictions", "LR_text_outputs")},
+            LR_length_rounded=res["LR_length_rounded"].clone(), x_band_width=res["x_band_width"],
+            attn={k: [sketch(a) for a in res[k]] for k in ("enc_slf_attn_lst", "pnca_x_attn_lst", "pnca_h_attn_lst")},
+            losses=dict(mel_loss_=float(mel_), mel_loss=float(mel), dur_loss=float(d), pitch_loss=float(p),
+                        energy_loss=float(e), total=float(total)),
+            grads={n: sketch(p_.grad) for n, p_ in m.named_parameters() if p_.grad is not None})
+    for channels, B, frames in ((512, 1, 8), (64, 2, 8)):
+        torch.manual_seed(0)
+        G, D1, D2 = Generator(channels=channels), MultiPeriodDiscriminator(), MultiScaleDiscriminator()
+        g = torch.Generator().manual_seed(1)
+        xm = torch.randn(B, 80, frames, generator=g)
+        yw = torch.randn(B, 1, frames * 256, generator=g).clamp(-1, 1)
+        wav = G(xm)
+        wav.sum().backward()
+        rec = dict(B=B, frames=frames, G_checksums=checksums(G.state_dict()), G_out=sketch(wav),
+                   G_grads={n: sketch(p_.grad) for n, p_ in G.named_parameters()})
+        for D, nm in ((D1, "mpd"), (D2, "msd")):
+            o, fm = D(yw)
+            (sum((u * u).mean() for u in o) + sum(u.abs().mean() for fa in fm for u in fa)).backward()
+            rec[nm] = dict(checksums=checksums(D.state_dict()), out=[sketch(u) for u in o],
+                           fmaps=[[sketch(u) for u in fa] for fa in fm],
+                           grads={n: sketch(p_.grad) for n, p_ in D.named_parameters()})
+        fix["hifigan"][channels] = rec
+    torch.manual_seed(5)
+    x = torch.randn(3, 4096) * 0.1
+    fix["mel"] = dict(x=x, mel=MelSpectrogram()(x[:, None]).detach().clone())
+    for part, keys in (("sambert", ("sambert", "mel")), ("hifigan", ("hifigan",))):  # two files: each under 1 MiB
+        path = os.path.join(OUT, "check_cases_%s.pt" % part)
+        torch.save({k: fix[k] for k in keys}, path)
+        print(path, "bytes", os.path.getsize(path))
+
+
+def denorm_f0_case():
+    """denorm_f0 of the NSF acoustic models (kantts/bin/infer_sambert.py:26-56), both normalisations, on the input of
+    tests/test_entrypoints.py::test_nsf_f0_denormalisation_follows_the_reference."""
+    import numpy as np
+    from kantts.bin.infer_sambert import denorm_f0
+
+    g = np.random.default_rng(3)
+    mel = g.standard_normal((50, 82)).astype(np.float32)
+    mel[:, -1] = g.uniform(0, 1, 50)
+    mel[:, -2] = g.uniform(-0.2, 1.0, 50)
+    mvn = np.array([[210.0], [45.0]], dtype=np.float32)  # mvn.npy: mean row, std row
+    fix = {"mel": torch.from_numpy(mel.copy()),
+           "mean_std": torch.from_numpy(np.ascontiguousarray(denorm_f0(mel.copy(), norm_type="mean_std", f0_feature=mvn))),
+           "global": torch.from_numpy(np.ascontiguousarray(denorm_f0(mel.copy(), norm_type="global",
+                                                                     f0_feature=[730.0, 30.0])))}
+    torch.save(fix, os.path.join(OUT, "denorm_f0.pt"))
+    print("denorm_f0 bytes", os.path.getsize(os.path.join(OUT, "denorm_f0.pt")))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:  # python oracle/make_golden.py hifigan_v1_b32_case ...: only the named cases (no arguments)
         for name in sys.argv[1:]:
@@ -817,3 +906,5 @@ if __name__ == "__main__":
     msd_avgpool_case()
     relu_generator_case()
     dsp_melspec_case()
+    denorm_f0_case()
+    check_cases_case()

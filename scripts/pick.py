@@ -1,4 +1,5 @@
-"""stdin: a bench.py JSON line -> the few numbers an A/B needs (ms per step, forward ms, roofline fraction, loss)."""
+"""stdin: a bench.py JSON line -> the few numbers an A/B needs (ms per step, forward ms, roofline fraction, loss).
+Forward ms and roofline fraction are on the line of a `bench.py --full` run only (None otherwise)."""
 import json
 import sys
 

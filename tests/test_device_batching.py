@@ -144,7 +144,7 @@ def _trainer_items(n=8, seed=4):
     return items
 
 
-def _two_trainer_steps(device, feed):
+def _two_trainer_steps(device, feed, save_dir):
     """Two Sambert_Trainer steps on batches assembled by the host collate ("host") or on the device ("device")."""
     from test_trainer import _sambert_setup
 
@@ -154,7 +154,7 @@ def _two_trainer_steps(device, feed):
     items = _trainer_items()
     pad_ids = [146, 9, 7, 7, 35, 3]
     index_batches = [[0, 3, 5], [7, 1, 2]]
-    tr, _ = _sambert_setup(device, "/tmp/kantts_feeder_test", seed=0)
+    tr, _ = _sambert_setup(device, save_dir, seed=0)
     if feed == "device":
         loader = DeviceCorpusLoader(DeviceAMSet(items, 3, pad_ids, device), 3, batches=index_batches)
         assert len(loader) == 2
@@ -170,15 +170,15 @@ def _two_trainer_steps(device, feed):
     return losses, flat
 
 
-def _feeder_check(device):
-    la, wa = _two_trainer_steps(device, "host")
-    lb, wb = _two_trainer_steps(device, "device")
+def _feeder_check(device, save_dir):
+    la, wa = _two_trainer_steps(device, "host", save_dir)
+    lb, wb = _two_trainer_steps(device, "device", save_dir)
     if device == "cpu":
         assert la == lb and torch.equal(wa, wb)  # identical batches -> identical steps
     else:
         # on the device the weight gradients are fp32 atomics whose order differs from run to run: identical up to the
         # noise floor of two host-fed runs
-        lc, wc = _two_trainer_steps(device, "host")
+        lc, wc = _two_trainer_steps(device, "host", save_dir)
         floor = float((wa - wc).norm() / wa.norm())
         assert float((wa - wb).norm() / wa.norm()) <= max(3 * floor, 1e-6), floor
         assert all(abs(x - y) <= 1e-5 * max(1.0, abs(x)) for x, y in zip(la, lb))
@@ -192,11 +192,11 @@ def _feeder_check(device):
         assert b["band_width"] == band_width_of(b["durations"].cpu(), b["valid_input_lengths"].cpu(), 3)
 
 
-def test_trainer_steps_fed_from_the_device_corpus_equal_host_fed_steps_emulated():
+def test_trainer_steps_fed_from_the_device_corpus_equal_host_fed_steps_emulated(tmp_path):
     with emulation():
-        _feeder_check("cpu")
+        _feeder_check("cpu", str(tmp_path))
 
 
 @pytest.mark.gpu
-def test_trainer_steps_fed_from_the_device_corpus_equal_host_fed_steps_gpu():
-    _feeder_check("cuda")
+def test_trainer_steps_fed_from_the_device_corpus_equal_host_fed_steps_gpu(tmp_path):
+    _feeder_check("cuda", str(tmp_path))

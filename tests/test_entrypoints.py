@@ -8,7 +8,7 @@ import torch
 import yaml
 
 import torch_oracle as O
-from util import emulation
+from util import GOLDEN, emulation
 
 
 class _FakeLingUnit:
@@ -179,24 +179,10 @@ def test_infer_sambert_with_a_speaker_embedding_file_emulated(tmp_path):
     assert n > 0 and np.abs(mels[0][:n] - mels[1][:n]).max() > 1e-4  # the embedding reaches the decoder
 
 
-def _reference_denorm_f0():
-    """The reference's own ``denorm_f0`` (kantts/bin/infer_sambert.py:26-56), loaded from its source file when the checkout
-    is present (the build container); None on a box without it."""
-    import ast
-
-    path = "/root/reference/kantts/bin/infer_sambert.py"
-    if not os.path.exists(path):
-        return None
-    tree = ast.parse(open(path).read())
-    fn = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "denorm_f0"]
-    ns = {"np": np}
-    exec(compile(ast.Module(body=fn, type_ignores=[]), path, "exec"), ns)
-    return ns["denorm_f0"]
-
-
 def test_nsf_f0_denormalisation_follows_the_reference():
-    """``denorm_f0`` of the NSF acoustic models (reference :26-56): both normalisations, against the reference's function when
-    its checkout is here and against the definition (hand values) everywhere."""
+    """``denorm_f0`` of the NSF acoustic models (reference :26-56): both normalisations, against what the reference's function
+    returned on the same input (tests/golden/denorm_f0.pt, oracle/make_golden.py::denorm_f0_case) and against the
+    definition (hand values)."""
     from kantts.bin.infer_sambert import denorm_f0
 
     g = np.random.default_rng(3)
@@ -210,10 +196,10 @@ def test_nsf_f0_denormalisation_follows_the_reference():
     assert np.allclose(got_ms[:, -2], np.maximum(mel[:, -2] * 45.0 + 210.0, 30.0), atol=1e-4)
     assert np.allclose(got_gl[:, -2], np.maximum(mel[:, -2] * 700.0 + 30.0, 30.0), atol=1e-4)
     assert np.array_equal(got_gl[:, -1], (mel[:, -1] >= 0.6).astype(np.float32))
-    ref = _reference_denorm_f0()
-    if ref is not None:
-        assert np.allclose(got_ms, ref(mel.copy(), norm_type="mean_std", f0_feature=mvn), atol=1e-4)
-        assert np.allclose(got_gl, ref(mel.copy(), norm_type="global", f0_feature=[730.0, 30.0]), atol=1e-4)
+    ref = torch.load(os.path.join(GOLDEN, "denorm_f0.pt"))
+    assert np.array_equal(mel, ref["mel"].numpy())  # the recorded input is this one
+    assert np.allclose(got_ms, ref["mean_std"].numpy(), atol=1e-4)
+    assert np.allclose(got_gl, ref["global"].numpy(), atol=1e-4)
 
 
 def test_infer_sambert_accepts_an_nsf_acoustic_model_emulated(tmp_path):

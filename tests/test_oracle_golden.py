@@ -211,3 +211,107 @@ def test_lstm_aten_equals_the_time_loop():
         gb = torch.autograd.grad((h * w).sum(), [x] + list(P.values()))
         for a, b in zip(ga, gb):
             assert float((a - b).abs().max()) < 1e-5 * max(1.0, float(b.abs().max()))
+
+
+def _checksums_match(sd, ref, what):
+    assert list(sd.keys()) == list(ref.keys()), what
+    for k, (shape, s, a) in ref.items():
+        assert tuple(sd[k].shape) == tuple(shape), (what, k)
+        assert abs(float(sd[k].double().sum()) - s) <= 1e-9 * max(1.0, abs(a)), (what, k)
+
+
+def _like(t, ref, what, max_abs=None, rel_l2=None):
+    """``t`` against a make_golden.sketch() of the reference value, to the live check's bound on the whole tensor: the
+    largest elementwise difference (``max_abs``) or ||t - ref|| / ||ref|| (``rel_l2``).  For a sketch, what that bound
+    implies: on the sampled positions, the norm and the sum."""
+    t = t.detach().double()
+    assert tuple(t.shape) == tuple(ref["shape"]), (what, tuple(t.shape), ref["shape"])
+    if "full" in ref:
+        d, ref_norm = t - ref["full"].double(), float(ref["full"].double().norm())
+        ok = float(d.abs().max()) <= max_abs if max_abs is not None else float(d.norm()) <= rel_l2 * ref_norm + 1e-30
+        assert ok, (what, float(d.abs().max()), ref_norm)
+        return
+    flat = t.reshape(-1)
+    n = flat.numel()
+    d = flat[torch.linspace(0, n - 1, ref["sample"].numel()).long()] - ref["sample"].double()
+    dsum, dnorm = abs(float(flat.sum()) - ref["sum"]), abs(float(flat.norm()) - ref["norm"])
+    if max_abs is not None:
+        ok = float(d.abs().max()) <= max_abs and dsum <= max_abs * n and dnorm <= max_abs * n ** 0.5
+    else:
+        bound = rel_l2 * ref["norm"] + 1e-30
+        ok = float(d.norm()) <= bound and dnorm <= bound and dsum <= bound * n ** 0.5
+    assert ok, (what, float(d.abs().max()), dsum, dnorm, ref["norm"])
+
+
+def test_oracle_matches_reference_check_cases():
+    """What oracle/check_vs_reference.py compares live, against the reference's values recorded by
+    oracle/make_golden.py::check_cases_case: SAM-BERT at the tiny and the FULL configuration (outputs <= 2e-6, attention
+    maps <= 1e-6, losses, every parameter gradient rel-L2 <= 1e-5), HiFi-GAN G / MPD / MSD at 512 and 64 generator
+    channels (outputs <= 2e-6, feature maps <= 2e-5, every parameter gradient rel-L2 <= 1e-4) and a mel spectrogram
+    (<= 1e-6).  Weights are rebuilt from the seed by the product's classes and must be the reference's (checksums)."""
+    import audio_oracle as A
+    import hifigan_oracle as H
+    from kantts.models.hifigan.hifigan import Generator, MultiPeriodDiscriminator, MultiScaleDiscriminator
+    from kantts.models.sambert.kantts_sambert import KanTtsSAMBERT
+
+    fix = _load("check_cases_sambert")
+    assert set(fix["sambert"]) == {"tiny", "full"}
+    for name, rec in fix["sambert"].items():
+        cfg = O.sambert_config(tiny=rec["tiny"])
+        torch.manual_seed(0)
+        sd = KanTtsSAMBERT(dict(cfg)).state_dict()
+        _checksums_match(sd, rec["weight_checksums"], name)
+        P = {k: v.detach().clone().requires_grad_(v.is_floating_point()) for k, v in sd.items()}
+        batch = O.synthetic_sambert_batch(**rec["batch_args"])
+        out = O.sambert_forward(P, cfg, **batch)
+        for k, ref in rec["outputs"].items():
+            _like(out[k], ref, "%s %s" % (name, k), max_abs=2e-6)
+        assert torch.equal(out["LR_length_rounded"], rec["LR_length_rounded"]), name
+        assert out["x_band_width"] == rec["x_band_width"], name
+        for k, refs in rec["attn"].items():
+            assert len(out[k]) == len(refs), (name, k)
+            for i, (a, ref) in enumerate(zip(out[k], refs)):
+                _like(a, ref, "%s %s[%d]" % (name, k, i), max_abs=1e-6)
+        L = O.sambert_losses(out, batch["input_lengths"], batch["output_lengths"], batch["mel_targets"])
+        for k, v in rec["losses"].items():
+            assert abs(float(L[k]) - v) <= 2e-5 * max(1.0, abs(v)), (name, k)
+        L["total"].backward()
+        for k, ref in rec["grads"].items():
+            assert P[k].grad is not None, (name, k)
+            _like(P[k].grad, ref, "%s grad %s" % (name, k), rel_l2=1e-5)
+
+    fix = _load("check_cases_hifigan")
+    assert set(fix["hifigan"]) == {512, 64}
+    for channels, rec in fix["hifigan"].items():
+        torch.manual_seed(0)
+        G, D1, D2 = Generator(channels=channels), MultiPeriodDiscriminator(), MultiScaleDiscriminator()
+        _checksums_match(G.state_dict(), rec["G_checksums"], "G %d" % channels)
+        g = torch.Generator().manual_seed(1)
+        xm = torch.randn(rec["B"], 80, rec["frames"], generator=g)
+        yw = torch.randn(rec["B"], 1, rec["frames"] * 256, generator=g).clamp(-1, 1)
+        PG = {k: v.detach().clone().requires_grad_(True) for k, v in G.state_dict().items()}
+        wav = H.generator(PG, xm)
+        _like(wav, rec["G_out"], "G %d out" % channels, max_abs=2e-6)
+        wav.sum().backward()
+        for k, ref in rec["G_grads"].items():
+            _like(PG[k].grad, ref, "G %d grad %s" % (channels, k), rel_l2=1e-4)
+        for D, f, nm in ((D1, H.mpd, "mpd"), (D2, H.msd, "msd")):
+            r = rec[nm]
+            _checksums_match(D.state_dict(), r["checksums"], "%s %d" % (nm, channels))
+            P = {k: v.detach().clone().requires_grad_(v.is_floating_point()) for k, v in D.state_dict().items()}
+            o, fm = f(P, yw)
+            assert len(o) == len(r["out"]) and len(fm) == len(r["fmaps"]), nm
+            for i, (u, ref) in enumerate(zip(o, r["out"])):
+                _like(u, ref, "%s %d out %d" % (nm, channels, i), max_abs=2e-6)
+            for i, (fa, fb) in enumerate(zip(fm, r["fmaps"])):
+                assert len(fa) == len(fb), (nm, i)
+                for j, (u, ref) in enumerate(zip(fa, fb)):
+                    _like(u, ref, "%s %d fmap %d.%d" % (nm, channels, i, j), max_abs=2e-5)
+            (sum((u * u).mean() for u in o) + sum(u.abs().mean() for fa in fm for u in fa)).backward()
+            for k, ref in r["grads"].items():
+                _like(P[k].grad, ref, "%s %d grad %s" % (nm, channels, k), rel_l2=1e-4)
+
+    mel = _load("check_cases_sambert")["mel"]
+    got = A.mel_spectrogram(mel["x"])
+    assert got.numel() == mel["mel"].numel()
+    assert_close(got.reshape(mel["mel"].shape), mel["mel"], 1e-6, what="mel")
