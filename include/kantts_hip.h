@@ -1202,6 +1202,44 @@ typedef struct kantts_enc_attn_args {
 } kantts_enc_attn_args;
 int kantts_enc_attn_fwd(const kantts_enc_attn_args* args, void* stream);
 
+/* ---- Causal stride-1 dilated channels-last convolution WITH HISTORY (csrc/sconv.hip): the layer of chunked inference.
+ * S independent slots advance together by Tc rows; every slot carries the last H = (K - 1) * step input rows of the
+ * previous call.  Token rule:
+ *   out[s, q, n]      = post( bias[n] + sum_j sum_c pre( X[s, q - j*step, c] ) * w[j][n][c] ),   q in [0, Tc)
+ *   X[s, t, c]        = in[s, t, c]             for t >= 0
+ *                     = hist_in[s, H + t, c]    for -H <= t < 0
+ *   hist_out[s, h, c] = X[s, Tc - H + h, c]     for h in [0, H)   (the last H rows of [hist_in ; in], also when Tc < H)
+ *   pre(v)  = in_act  ? LeakyReLU(v, in_slope)  : v
+ *   post(v) = (out_act ? LeakyReLU(v, out_slope) : v) + res[s, q, n]
+ * Tap j reads j*step rows BACK (a torch Conv1d weight (N, Cin, K) left-padded by (K-1)*dilation is w[j] = W[:, :, K-1-j]).
+ * The polyphase form of a causal transposed convolution of stride u and the fused dual-path stage of the generator are this
+ * rule with step = 1, K = J taps and N = u * Cout (row q of out is the u output samples of input token q).
+ *   in (S, Tc, Cin), out / res (S, Tc, N), bias (N): fp32, dense.  hist_in / hist_out: fp32 raw (not activated) rows,
+ *   slot s at base + s * hist_ss floats, (H, Cin) dense inside a slot; two DIFFERENT buffers (ping-pong); hist_out is
+ *   written by extra workgroups of the same launch.  Both may be NULL when K == 1.
+ *   w (K, N, Cin): fp32 when precision == 0 or N == 1, bf16 when precision == 1 and N > 1.
+ * precision 0: fp32 operands on v_mfma_f32_16x16x4_f32; 1: bf16 operands (the activated input is rounded as it enters LDS)
+ * on v_mfma_f32_16x16x32_bf16, fp32 accumulation.  N == 1 is a direct fp32 dot product in both modes.
+ * KANTTS_E_UNSUPPORTED unless Cin % 8 == 0, 16 <= Cin <= 512, (N == 1 or 16 <= N <= 4096), 1 <= K <= 11, 1 <= step <= 7,
+ * all pointers 16-byte aligned and hist_ss % 4 == 0.  S <= 0 or Tc <= 0: nothing is launched, KANTTS_OK. */
+typedef struct {
+  const float* in;
+  const float* hist_in;
+  float* hist_out;
+  const void* w;
+  const float* bias;
+  const float* res;
+  float* out;
+  long long hist_ss;
+  int S, Tc, Cin, N, K, step;
+  float in_slope;
+  int in_act;
+  float out_slope;
+  int out_act;
+  int precision;
+} kantts_sconv_args;
+int kantts_sconv_launch(const kantts_sconv_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,17 @@ class ConvN1Args(Structure):
     ]
 
 
+class SConvArgs(Structure):
+    """kantts_sconv_args (include/kantts_hip.h); ``in_`` is the C field ``in``."""
+    _fields_ = [
+        ("in_", c_void_p), ("hist_in", c_void_p), ("hist_out", c_void_p), ("w", c_void_p), ("bias", c_void_p),
+        ("res", c_void_p), ("out", c_void_p), ("hist_ss", c_longlong),
+        ("S", c_int32), ("Tc", c_int32), ("Cin", c_int32), ("N", c_int32), ("K", c_int32), ("step", c_int32),
+        ("in_slope", c_float), ("in_act", c_int32), ("out_slope", c_float), ("out_act", c_int32),
+        ("precision", c_int32),
+    ]
+
+
 class CConvArgs(Structure):
     """kantts_cconv_args (include/kantts_hip.h); ``in_`` is the C field ``in``."""
     _fields_ = [
@@ -435,6 +446,7 @@ def lib():
         L.kantts_mean_many.argtypes = [POINTER(c_void_p), i, f, p, p, f, ll, p]
         L.kantts_scale_to_many.argtypes = [p, f, POINTER(c_void_p), i, ll, p]
         L.kantts_ragged_rows_i64.argtypes = [p, p, p, p, p, p, i, i, i, i, p]
+        L.kantts_sconv_launch.argtypes = [POINTER(SConvArgs), c_void_p]
         _lib = L
     return _lib
 
@@ -458,7 +470,7 @@ EXPORTED_SYMBOLS = [
     "kantts_pnca_block_fwd", "kantts_pnca_block_bwd", "kantts_pnca_block_bwd_ws_floats", "kantts_rows_sum_many",
     "kantts_melspec_tuning", "kantts_teacher_plan", "kantts_copy_roof", "kantts_pnca_attn_qkv_bwd",
     "kantts_pnca_decode_run", "kantts_pnca_decode_blob_sizes", "kantts_dur_ar_run", "kantts_dur_ar_run_f32", "kantts_ctc_attn", "kantts_ctc_attn_workspace", "kantts_enc_attn_fwd",
-    "kantts_launch_tuning",
+    "kantts_launch_tuning", "kantts_sconv_launch",
 ]
 
 
@@ -1225,6 +1237,31 @@ def conv_wgrad(x, dy, dw_tap, db, *, B, Tsrc, Tdst, groups, CR, NG, K, stride, d
                                                  gated=dy_gate is not None),
                               4.0 * (B * Tsrc * inner * groups * CR + B * Tdst * inner * groups * NG *
                                      (2 if dy_gate is not None else 1) + K * groups * NG * CR)))
+    return True
+
+
+E_UNSUPPORTED = -2
+
+
+def sconv(x, hist_in, hist_out, w, out, *, S, Tc, Cin, N, K, step, hist_ss, precision, bias=None, res=None, in_leaky=None,
+          out_leaky=None):
+    """Causal stride-1 dilated convolution with carried history (csrc/sconv.hip, kantts_sconv_launch; the token rule is
+    written out in include/kantts_hip.h).  x (S, Tc, Cin) fp32; hist_in / hist_out: fp32 tensors whose first element is
+    slot 0's state of this layer, ``hist_ss`` floats between slots; w (K, N, Cin), bf16 when precision == PREC_BF16 and
+    N > 1, else fp32; out / res (S, Tc, N) fp32.  Returns False when the kernel declines the shape."""
+    g = SConvArgs()
+    g.in_, g.hist_in, g.hist_out = ptr(x, torch.float32), ptr(hist_in, torch.float32), ptr(hist_out, torch.float32)
+    g.w = ptr(w, torch.bfloat16 if (precision == PREC_BF16 and N > 1) else torch.float32)
+    g.bias, g.res, g.out = ptr(bias, torch.float32), ptr(res, torch.float32), ptr(out, torch.float32)
+    g.hist_ss = int(hist_ss)
+    g.S, g.Tc, g.Cin, g.N, g.K, g.step = int(S), int(Tc), int(Cin), int(N), int(K), int(step)
+    g.in_slope, g.in_act = float(in_leaky or 0.0), int(in_leaky is not None)
+    g.out_slope, g.out_act = float(out_leaky or 0.0), int(out_leaky is not None)
+    g.precision = int(precision)
+    rc = lib().kantts_sconv_launch(ctypes.byref(g), stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "sconv")
     return True
 
 

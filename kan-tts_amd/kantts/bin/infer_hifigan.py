@@ -5,6 +5,10 @@ Mirrors kantts/bin/infer_hifigan.py:34-163 of the reference (same function names
 runs on the MI355X kernels (kantts/models/hifigan); wav files are written with scipy (soundfile is not a
 dependency here).  NSF generators take (T, C + 2) features whose last column (voiced flag) is re-binarised first, as in
 the reference (:52-63, :112-113); multi-band (PQMF) generators are refused.
+
+``--chunk_frames N``: the same outputs produced chunk by chunk through kantts.models.hifigan.chunked.ChunkedVocoder
+(carried convolution state; causal single-band generators without NSF), with the time to the first chunk logged beside
+the RTF.  Absent: the whole-utterance path, unchanged.
 """
 import argparse
 import glob
@@ -61,7 +65,7 @@ def _device():
     return torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
 
 
-def hifigan_infer(input_mel, ckpt_path, output_dir, config=None):
+def hifigan_infer(input_mel, ckpt_path, output_dir, config=None, chunk_frames=None):
     device = _device()
     config = _load_config(ckpt_path, config)
     os.makedirs(output_dir, exist_ok=True)
@@ -77,6 +81,11 @@ def hifigan_infer(input_mel, ckpt_path, output_dir, config=None):
     model = model.eval().to(device)
     sr = config["audio_config"]["sampling_rate"]
     pcm_len = 0
+    vocoder, first_chunk = None, []
+    if chunk_frames is not None:
+        from kantts.models.hifigan.chunked import ChunkedVocoder
+
+        vocoder = ChunkedVocoder(model, slots=1, graph=device.type == "cuda")  # refuses what it cannot play, loudly
     with torch.no_grad():
         start = time.time()
         for mel in mel_lst:
@@ -85,15 +94,28 @@ def hifigan_infer(input_mel, ckpt_path, output_dir, config=None):
             if model.nsf_enable:
                 feats = binarize(feats)
             mel_data = torch.from_numpy(np.ascontiguousarray(feats)).float().to(device)
-            y = model(mel_data.transpose(1, 0).unsqueeze(0))  # (T, C) -> (1, C, T)
-            if hasattr(model, "pqmf"):
-                y = model.pqmf.synthesis(y)
+            if vocoder is not None:
+                t0, parts = time.time(), []
+                for wav in vocoder.synthesize(mel_data.transpose(1, 0), chunk_frames=chunk_frames):
+                    parts.append(wav.reshape(-1).cpu())  # the copy to the host is when a chunk can be played
+                    if len(parts) == 1:
+                        first_chunk.append(time.time() - t0)
+                y = torch.cat(parts)
+            else:
+                y = model(mel_data.transpose(1, 0).unsqueeze(0))  # (T, C) -> (1, C, T)
+                if hasattr(model, "pqmf"):
+                    y = model.pqmf.synthesis(y)
             y = y.reshape(-1).cpu().numpy()
             pcm_len += len(y)
             wavfile.write(os.path.join(output_dir, "%s_gen.wav" % utt_id), sr,
                           (np.clip(y, -1.0, 1.0) * 32767.0).astype(np.int16))
         rtf = (time.time() - start) / max(pcm_len / sr, 1e-9)
-    logging.info("Finished generation of %d utterances (RTF = %.03f).", len(mel_lst), rtf)
+    if vocoder is not None and first_chunk:
+        logging.info("Finished chunked generation of %d utterances (%d frames per chunk, RTF = %.03f, time to first chunk: "
+                     "median %.2f ms, first utterance %.2f ms).", len(mel_lst), chunk_frames, rtf,
+                     1e3 * float(np.median(first_chunk)), 1e3 * first_chunk[0])
+    else:
+        logging.info("Finished generation of %d utterances (RTF = %.03f).", len(mel_lst), rtf)
     return rtf
 
 
@@ -104,5 +126,7 @@ if __name__ == "__main__":
                         help="Path to input mel file or directory containing mel files")
     parser.add_argument("--output_dir", type=str, required=True, help="Path to output directory")
     parser.add_argument("--config", type=str, default=None, help="Path to config file")
+    parser.add_argument("--chunk_frames", type=int, default=None,
+                        help="Generate chunk by chunk, this many mel frames at a time (carried convolution state)")
     args = parser.parse_args()
-    hifigan_infer(args.input_mel, args.ckpt, args.output_dir, args.config)
+    hifigan_infer(args.input_mel, args.ckpt, args.output_dir, args.config, chunk_frames=args.chunk_frames)

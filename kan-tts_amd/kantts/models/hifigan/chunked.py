@@ -1,0 +1,278 @@
+"""Chunked HiFi-GAN inference with carried convolution state.
+
+A causal ``Generator`` exists so that audio can be emitted while mel frames are still arriving (reference
+kantts/models/hifigan/layers.py:52-165, hifigan.py:59-60); ``Generator.forward`` takes a whole utterance.
+``ChunkedVocoder`` plays the same network chunk by chunk: every causal layer keeps the last ``H`` rows of its input
+between calls (csrc/sconv.hip, kantts_sconv_launch), so the concatenated chunk outputs are the one-shot output up to
+fp32 summation order.  A zero state is exactly the reference's zero left-pad, so a fresh slot needs no special case.
+
+    v = ChunkedVocoder(generator, slots=S, graph=True)    # generator: causal, eval, on the device
+    wav = v.step(mel)            # mel (S, C_mel, Tc), any Tc >= 1 -> wav (S, 1, Tc * prod(upsample_scales))
+    v.reset(slot=None)           # one slot or all: the next step starts from zero state
+    for wav in v.synthesize(mel_full, chunk_frames=8, slot=0): ...
+
+History rows per layer (at that layer's token rate): ``(k - 1) * dilation`` for a convolution, ``J - 1`` input tokens
+for an upsampling stage (J polyphase taps: the transposed convolution alone has kernel / stride, the fused dual-path
+stage of ``Generator._dual_path_weight`` max(kernel / stride, 1 + ceil(6 / stride))).
+"""
+import torch
+
+import kantts._hip as hip
+from kantts._hip import ops
+from kantts.models.hifigan.layers import CausalConv1d, CausalConvTranspose1d, effective_weight
+
+# what kantts_sconv_launch accepts (include/kantts_hip.h); checked here BEFORE anything is packed or launched
+_MAX_K, _MAX_STEP = 11, 7
+
+
+def sconv_supported(Cin, N, K, step):
+    return (Cin % 8 == 0 and 16 <= Cin <= 512 and (N == 1 or 16 <= N <= 4096) and 1 <= K <= _MAX_K
+            and 1 <= step <= _MAX_STEP)
+
+
+class _Layer:
+    """One stateful layer: geometry first (``plan``), packed weights later (``pack``)."""
+
+    def __init__(self, name, Cin, N, K, step, in_leaky):
+        self.name, self.Cin, self.N, self.K, self.step, self.in_leaky = name, Cin, N, K, step, in_leaky
+        self.H = (K - 1) * step
+        self.off = 0  # first float of this layer's state inside a slot of the arena
+        self.w = self.bias = None
+
+
+class ChunkedVocoder:
+    """Chunk-by-chunk inference of a causal single-band ``Generator`` on ``slots`` independent utterances that advance
+    together by ``Tc`` frames per ``step``.
+
+    The object is a SNAPSHOT of the generator: the effective (weight-normed, dual-path-fused) weights are computed and
+    packed once, here; build a new ``ChunkedVocoder`` after the generator's weights change.  The contraction mode is
+    ``kantts._hip.get_precision()`` at construction.
+
+    All state of all layers lives in one arena ``(2, slots, L)`` fp32 (ping and pong halves, slot-major); its size depends
+    on the model and ``slots`` only, so consecutive steps may use different chunk sizes.  A step reads half ``p`` and writes
+    half ``1 - p`` inside the convolution launches themselves.
+
+    ``graph=True``: a step is captured per distinct ``Tc`` -- one ``torch.cuda.CUDAGraph`` for each parity, on one stream
+    with no parallel branches -- and replayed; ``mel`` is copied into a static buffer.  ``graph=False`` issues the same
+    launches eagerly and gives identical bits.
+
+    Refused at construction: non-causal generators, NSF generators (the excitation's running phase and random draws need
+    a carried state of their own), ``out_channels > 1`` (PQMF synthesis), and channel counts / kernel sizes the kernel
+    declines (Cin a multiple of 8 in 16..512, k <= 11, dilation <= 7, upsampling N = scale * Cout <= 4096)."""
+
+    def __init__(self, generator, slots=1, graph=True, max_graphs=8):
+        g = generator
+        if not getattr(g, "causal", False):
+            raise ValueError("ChunkedVocoder needs a causal generator (causal=True): a symmetric convolution looks ahead")
+        if g.nsf_enable:
+            raise NotImplementedError("ChunkedVocoder: NSF generators are not supported (the source module's running phase "
+                                      "and random draws need a carried state of their own)")
+        if g.out_channels != 1:
+            raise NotImplementedError("ChunkedVocoder: out_channels > 1 (multi-band / PQMF) generators are not supported")
+        if g.training:
+            raise ValueError("ChunkedVocoder needs generator.eval()")
+        if int(slots) < 1:
+            raise ValueError("slots must be >= 1")
+        mode = hip.get_precision()
+        if mode not in ("fp32", "bf16"):
+            raise ValueError("ChunkedVocoder: precision %r has no chunked kernels" % mode)
+        self.precision = hip.PREC_BF16 if mode == "bf16" else hip.PREC_FP32
+        self.slots = int(slots)
+        self.slope = g.slope
+        self.scales = [int(s) for s in g.upsample_scales]
+        self.hop = 1
+        for s in self.scales:
+            self.hop *= s
+        self.num_kernels = g.num_kernels
+
+        # ---- geometry of every stateful layer, from the modules' shapes alone (nothing is computed or launched yet)
+        def conv_layer(name, m, in_leaky):
+            if not isinstance(m, CausalConv1d):
+                raise ValueError("ChunkedVocoder: %s is not a CausalConv1d" % name)
+            c = m.conv1d
+            if c.stride[0] != 1 or c.groups != 1:
+                raise NotImplementedError("ChunkedVocoder: %s has stride / groups != 1" % name)
+            return _Layer(name, c.in_channels, c.out_channels, c.kernel_size[0], c.dilation[0], in_leaky)
+
+        self.in_channels = g.conv_pre.conv1d.in_channels
+        self.pre = conv_layer("conv_pre", g.conv_pre, None)
+        self.stages = []
+        for i, s in enumerate(self.scales):
+            up = g.transpose_upsamples[i][1]
+            if not isinstance(up, CausalConvTranspose1d):
+                raise ValueError("ChunkedVocoder: transpose_upsamples[%d] is not causal" % i)
+            d = up.deconv
+            if d.kernel_size[0] % s:
+                raise NotImplementedError("ChunkedVocoder: upsampling kernel %d is not a multiple of its stride %d"
+                                          % (d.kernel_size[0], s))
+            J = d.kernel_size[0] // s
+            if g.repeat_upsample:
+                k7 = g.repeat_upsamples[i][2].conv1d.kernel_size[0]
+                J = max(J, 1 + -(-(k7 - 1) // s))
+            upl = _Layer("stage%d.up" % i, d.in_channels, s * d.out_channels, J, 1, self.slope)
+            stacks = []
+            for j, blk in enumerate(g.conv_blocks[i * g.num_kernels:(i + 1) * g.num_kernels]):
+                pairs = []
+                for n, (c1, c2) in enumerate(zip(blk.convs1, blk.convs2)):
+                    if blk.slope != self.slope:
+                        raise NotImplementedError("ChunkedVocoder: residual blocks with their own activation slope")
+                    pairs.append((conv_layer("stage%d.block%d.convs1.%d" % (i, j, n), c1, self.slope),
+                                  conv_layer("stage%d.block%d.convs2.%d" % (i, j, n), c2, self.slope)))
+                stacks.append(pairs)
+            self.stages.append((s, d.out_channels, upl, stacks))
+        self.post = conv_layer("conv_post", g.conv_post, 0.01)  # F.leaky_relu's default slope (reference hifigan.py:178)
+        self.layers = [self.pre]
+        for _, _, upl, stacks in self.stages:
+            self.layers.append(upl)
+            for pairs in stacks:
+                for c1, c2 in pairs:
+                    self.layers += [c1, c2]
+        self.layers.append(self.post)
+        for L in self.layers:
+            if not sconv_supported(L.Cin, L.N, L.K, L.step):
+                raise NotImplementedError(
+                    "ChunkedVocoder: layer %s (Cin %d, N %d, k %d, dilation %d) is outside what kantts_sconv_launch accepts "
+                    "(Cin a multiple of 8 in 16..512, N = 1 or 16..4096, k <= %d, dilation <= %d)"
+                    % (L.name, L.Cin, L.N, L.K, L.step, _MAX_K, _MAX_STEP))
+        off = 0
+        for L in self.layers:
+            L.off = off
+            off += L.H * L.Cin  # Cin % 8 == 0: every layer's state starts on a 16-byte boundary
+        self.state_floats = off
+
+        # ---- snapshot of the weights
+        self.device = next(g.parameters()).device
+        if graph and self.device.type != "cuda":
+            raise ValueError("graph=True needs the generator on the GPU")
+        self.graph = bool(graph)
+        wdt = torch.bfloat16 if self.precision == hip.PREC_BF16 else torch.float32
+
+        def pack(L, w_knc, bias):
+            assert tuple(w_knc.shape) == (L.K, L.N, L.Cin), (L.name, tuple(w_knc.shape), (L.K, L.N, L.Cin))
+            L.w = w_knc.detach().to(torch.float32 if L.N == 1 else wdt).contiguous().clone()
+            L.bias = None if bias is None else bias.detach().float().contiguous().clone()
+
+        def pack_conv(L, m):
+            w = effective_weight(m.conv1d)  # (Cout, Cin, k); tap j of the kernel reads j * dilation rows back = W[.., k-1-j]
+            pack(L, w.permute(2, 0, 1).flip(0), m.conv1d.bias)
+
+        with torch.no_grad():
+            pack_conv(self.pre, g.conv_pre)
+            for i, (s, Cout, upl, stacks) in enumerate(self.stages):
+                if g.repeat_upsample:
+                    w, b = g._dual_path_weight(i, s)  # (Cin, Cout, J*s)
+                else:
+                    d = g.transpose_upsamples[i][1].deconv
+                    w, b = effective_weight(d), d.bias
+                w2 = w.reshape(upl.Cin, Cout, upl.K, s).permute(2, 3, 1, 0).reshape(upl.K, s * Cout, upl.Cin)
+                pack(upl, w2, None if b is None else b.repeat(s))
+                blocks = g.conv_blocks[i * g.num_kernels:(i + 1) * g.num_kernels]
+                for pairs, blk in zip(stacks, blocks):
+                    for (l1, l2), c1, c2 in zip(pairs, blk.convs1, blk.convs2):
+                        pack_conv(l1, c1)
+                        pack_conv(l2, c2)
+            pack_conv(self.post, g.conv_post)
+        self.arena = torch.zeros(2, self.slots, max(self.state_floats, 4), device=self.device, dtype=torch.float32)
+        self._parity = 0
+        self._graphs = {}
+        self._max_graphs = int(max_graphs)
+
+    # ------------------------------------------------------------------------------------------------------------
+    def reset(self, slot=None):
+        """Zero state for one slot (others untouched) or for all: one fill launch."""
+        if slot is None:
+            self.arena.zero_()
+        else:
+            if not 0 <= int(slot) < self.slots:
+                raise IndexError("slot %r of %d" % (slot, self.slots))
+            self.arena[:, int(slot)].zero_()
+
+    def _conv(self, L, x, parity, res=None):
+        S, T, _ = x.shape
+        out = torch.empty((S, T, L.N), device=x.device, dtype=torch.float32)
+        hin = hout = None
+        if L.H:
+            hin = self.arena[parity, 0, L.off:L.off + L.H * L.Cin]
+            hout = self.arena[1 - parity, 0, L.off:L.off + L.H * L.Cin]
+        ok = hip.sconv(x, hin, hout, L.w, out, S=S, Tc=T, Cin=L.Cin, N=L.N, K=L.K, step=L.step,
+                       hist_ss=self.arena.shape[2], precision=self.precision, bias=L.bias, res=res, in_leaky=L.in_leaky)
+        if not ok:
+            raise RuntimeError("kantts_sconv_launch declined layer %s it was planned for" % L.name)
+        return out
+
+    def _run(self, mel, parity):
+        """The launches of one step: mel (S, C, Tc) fp32 -> wav (S, 1, Tc * hop).  Reads arena[parity], writes
+        arena[1 - parity]."""
+        with torch.no_grad():
+            h = self._conv(self.pre, mel.transpose(1, 2).contiguous(), parity)
+            for s, Cout, upl, stacks in self.stages:
+                h = ops.sin_add(h)
+                h = self._conv(upl, h, parity).view(h.shape[0], h.shape[1] * s, Cout)
+                ys = []
+                for pairs in stacks:  # sequential, as Generator._residual_stacks runs them under no_grad
+                    x = h
+                    for c1, c2 in pairs:
+                        x = self._conv(c2, self._conv(c1, x, parity), parity, res=x)
+                    ys.append(x)
+                h = ops.mean_many(ys) if len(ys) > 1 else ys[0]
+            h = self._conv(self.post, h, parity)
+            return torch.tanh(h).transpose(1, 2)
+
+    def _captured(self, Tc):
+        ent = self._graphs.pop(Tc, None)
+        if ent is None:
+            if len(self._graphs) >= self._max_graphs:
+                self._graphs.pop(next(iter(self._graphs)))  # least recently used
+            mel = torch.zeros(self.slots, self.in_channels, Tc, device=self.device, dtype=torch.float32)
+            # eager warm-up of both parities on a side stream (kernels loaded, allocator primed); the state it advances
+            # is put back afterwards
+            saved = self.arena.clone()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for p in (0, 1):
+                    self._run(mel, p)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            graphs, outs = [], []
+            for p in (0, 1):
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr, capture_error_mode="thread_local"):
+                    outs.append(self._run(mel, p))
+                graphs.append(gr)
+            self.arena.copy_(saved)
+            ent = (mel, graphs, outs)
+        self._graphs[Tc] = ent
+        return ent
+
+    def step(self, mel):
+        """mel (slots, C_mel, Tc), Tc >= 1 -> wav (slots, 1, Tc * prod(upsample_scales)); advances every slot by Tc."""
+        if mel.dim() != 3 or mel.shape[0] != self.slots or mel.shape[1] != self.in_channels or mel.shape[2] < 1:
+            raise ValueError("mel must be (slots=%d, %d, Tc >= 1), got %s" % (self.slots, self.in_channels, tuple(mel.shape)))
+        Tc = int(mel.shape[2])
+        if self.graph:
+            buf, graphs, outs = self._captured(Tc)
+            buf.copy_(mel)
+            graphs[self._parity].replay()
+            wav = outs[self._parity].clone()
+        else:
+            wav = self._run(mel.to(device=self.device, dtype=torch.float32), self._parity)
+        self._parity ^= 1
+        return wav
+
+    def synthesize(self, mel_full, chunk_frames=8, slot=0):
+        """Generator over the chunks of one utterance: mel_full (C_mel, T) or (1, C_mel, T) played on ``slot`` from zero
+        state (the other slots are fed zeros and advance with it).  The last partial chunk is padded with zero frames and
+        its output trimmed.  Yields (1, n_samples) tensors."""
+        if mel_full.dim() == 3:
+            mel_full = mel_full[0]
+        T = int(mel_full.shape[1])
+        n = int(chunk_frames)
+        if n < 1:
+            raise ValueError("chunk_frames must be >= 1")
+        self.reset(slot)
+        for t0 in range(0, T, n):
+            t1 = min(T, t0 + n)
+            mel = torch.zeros(self.slots, self.in_channels, n, device=self.device, dtype=torch.float32)
+            mel[slot, :, :t1 - t0] = mel_full[:, t0:t1]
+            yield self.step(mel)[slot, :, :(t1 - t0) * self.hop]
