@@ -89,7 +89,7 @@ __global__ __launch_bounds__(LG) void lstm_fwd_kernel(const float* __restrict__ 
   const int tid = threadIdx.x, j = tid >> 2, kq = tid & 3;
   const int b = blockIdx.x, dir = blockIdx.y;
   const bool rev = reverse_first ? true : (dir == 1);
-  const int len = lens ? min(lens[b], T) : T;
+  const int len = lens ? min(max(lens[b], 0), T) : T;  // clamped into [0, T]: the tail loops below start at len
   float w[BF16 ? 1 : 4 * 32];
   lstm_bf16x2 wq[BF16 ? 4 * 16 : 1];
 #pragma unroll
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restr
   const int tid = threadIdx.x, j = tid >> 1, p = tid & 1;
   const int b = blockIdx.x, dir = blockIdx.y;
   const bool rev = reverse_first ? true : (dir == 1);
-  const int len = lens ? min(lens[b], T) : T;
+  const int len = lens ? min(max(lens[b], 0), T) : T;  // clamped into [0, T]: the tail loops below start at len
   lstm_bf16x2 wq[4 * 32];
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(LG) void lstm_bwd_kernel(const float* __restrict__ 
   const int k = row * 4 + g2, kq = l >> 2;  // phase-A identity: cell, gate
   const int b = blockIdx.x, dir = blockIdx.y;
   const bool rev = reverse_first ? true : (dir == 1);
-  const int len = lens ? min(lens[b], T) : T;
+  const int len = lens ? min(max(lens[b], 0), T) : T;  // clamped into [0, T]: the tail loops below start at len
   // phase-B weights: slot s = W_hh[32 l + rr][4 row + (s ^ g2)], s < 4, rr < 32
   float w[BF16 ? 1 : 4 * 32];
   lstm_bf16x2 wq[BF16 ? 4 * 16 : 1];
@@ -515,7 +515,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_pair_kernel(const float* __restr
   const int k = row * 8 + g3, gp = l >> 3;  // phase-A identity: cell, gate pair
   const int b = blockIdx.x, dir = blockIdx.y;
   const bool rev = reverse_first ? true : (dir == 1);
-  const int len = lens ? min(lens[b], T) : T;
+  const int len = lens ? min(max(lens[b], 0), T) : T;  // clamped into [0, T]: the tail loops below start at len
   // phase-B weights: slot s = W_hh[32 l + rr][8 row + (s ^ g3)], s < 8, rr < 32 (pairs over rr)
   lstm_bf16x2 wq[8 * 16];
 #pragma unroll

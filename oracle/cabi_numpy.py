@@ -1194,7 +1194,7 @@ class EmulatedLib:
         for d in range(ndir):
             rev = bool(reverse_first) or d == 1
             for b in range(B):
-                n = min(int(ln[b]), T) if ln is not None else T
+                n = min(max(int(ln[b]), 0), T) if ln is not None else T
                 h = torch.zeros(H)
                 c = torch.zeros(H)
                 order = range(n - 1, -1, -1) if rev else range(n)
@@ -1223,7 +1223,7 @@ class EmulatedLib:
         for d in range(ndir):
             rev = bool(reverse_first) or d == 1
             for b in range(B):
-                n = min(int(ln[b]), T) if ln is not None else T
+                n = min(max(int(ln[b]), 0), T) if ln is not None else T
                 fwd_order = list(range(n - 1, -1, -1)) if rev else list(range(n))
                 dh = torch.zeros(H)
                 dc = torch.zeros(H)
