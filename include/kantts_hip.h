@@ -191,6 +191,16 @@ int kantts_lstm_fwd(const float* gx, const float* whh, const float* bhh, const i
 int kantts_lstm_bwd(const float* dout, const float* whh, const int32_t* lens, const float* gates_save,
                     const float* c_save, float* dgates, int B, int T, int H, int ndir, int reverse_first,
                     int precision, void* stream);
+/* Streaming form of kantts_lstm_fwd: steps [t0, min(t1, len)) of ONE forward direction (ndir == 2 or reverse_first:
+ * KANTTS_E_UNSUPPORTED) over the same full-length buffers, which persist between calls.  The state entering step t0 > 0 is
+ * h = out[b, t0 - 1], c = c_save[b, t0 - 1] (precision 1: h rounded to bf16 exactly as the step that produced it published
+ * it); it is zero at t0 == 0.  Only rows [t0, t1) of out / gates_save / c_save are written -- the zero tail of `out` for
+ * rows [max(len, t0), t1) -- and no row of gx at or after t1 is read (they need not exist yet).  Consecutive ranges give
+ * the bits of one kantts_lstm_fwd call.  t0 < 0, t1 > T or t0 > t1: KANTTS_E_BADARG; t0 == t1: no-op.  KANTTS_LSTM_PAIR=0
+ * selects the quad kernel here as it does for kantts_lstm_fwd. */
+int kantts_lstm_fwd_range(const float* gx, const float* whh, const float* bhh, const int32_t* lens, float* out,
+                          float* gates_save, float* c_save, int B, int T, int H, int ndir, int reverse_first, int t0,
+                          int t1, int precision, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Embedding gather-sum: out[row] = scale * sum_k table_k[ids[row,k]] (+ pos[row % T]);
@@ -257,6 +267,12 @@ int kantts_lr_gather_bwd(const float* dout, const int32_t* cs, const int64_t* va
  * computed (two calls on two streams: the filter gradient runs beside the backward pass's critical path). */
 int kantts_fsmn_dwconv_fwd(const float* x, const float* w, const float* res, const int64_t* lens, float* y, int B,
                            int T, int C, int K, int left_pad, void* stream);
+/* Rows [t0, t1) of y only (res is indexed like y), over the same full-length buffers: the x rows a result depends on are
+ * [t0 - left_pad, t1 + (K - 1 - left_pad)) inside [0, min(len, T)); later rows need not hold data yet, no other row of y is
+ * written, and a row equals the same row of kantts_fsmn_dwconv_fwd bit for bit.  t0 < 0, t1 > T or t0 > t1: KANTTS_E_BADARG;
+ * t0 == t1: no-op. */
+int kantts_fsmn_dwconv_fwd_rows(const float* x, const float* w, const float* res, const int64_t* lens, float* y, int B,
+                                int T, int C, int K, int left_pad, int t0, int t1, void* stream);
 int kantts_fsmn_dwconv_bwd(const float* dy, const float* x, const float* w, const int64_t* lens, float* dx,
                            float* dw_accum, float* workspace, long long ws_floats, int B, int T, int C, int K,
                            int left_pad, void* stream);
@@ -1115,6 +1131,12 @@ typedef struct kantts_decode_args {
   float eps;      /* of every LayerNorm */
 } kantts_decode_args;
 int kantts_pnca_decode_run(const kantts_decode_args* args, void* stream);
+/* Streaming form: decoder steps [t0, t1) of every sequence; kantts_pnca_decode_run is the range (0, L) of the same kernel.
+ * All buffers are the full-length ones above and persist between calls: the frame fed into step t0 > 0 is the last d_mel
+ * values of out[b, t0 - 1] (zero at t0 == 0), the K | V rows of earlier steps come from xkv.  Nothing outside rows [t0, t1)
+ * of out and xkv is written, nothing at or after row t1 of out is read.  A device-side band width above 127 poisons rows
+ * [t0, t1) of that sequence only.  t0 < 0, t1 > L or t0 > t1: KANTTS_E_BADARG; t0 == t1: no-op. */
+int kantts_pnca_decode_range(const kantts_decode_args* args, int t0, int t1, void* stream);
 int kantts_pnca_decode_blob_sizes(int d_mel, int d_mem, int d_out, int n_layer, long long* w_elems, long long* f_elems);
 
 /* kantts_dur_ar_run: the free-running duration predictor (VarRnnARPredictor.infer, kantts/models/sambert/adaptors.py:67-83):

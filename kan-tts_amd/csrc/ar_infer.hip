@@ -239,7 +239,9 @@ __host__ __device__ inline ArDecLayout ar_dec_layout(int d_mel, int d_mem, int d
   return y;
 }
 
-__global__ __launch_bounds__(AR_THREADS) void pnca_decode_run_kernel(const kantts_decode_args g) {
+// Steps [t0, t1) of every sequence (kantts_pnca_decode_range; kantts_pnca_decode_run is the range (0, L)).  Everything a later
+// step needs of an earlier one is in the full-length buffers: the K | V rows in xkv, the fed-back frame in out[b, t0 - 1].
+__global__ __launch_bounds__(AR_THREADS) void pnca_decode_run_kernel(const kantts_decode_args g, const int t0, const int t1) {
   __shared__ __attribute__((aligned(16))) __bf16 vA[AR_FF];
   __shared__ __attribute__((aligned(16))) __bf16 vB[AR_FF];
   __shared__ __attribute__((aligned(16))) float xs[AR_D];
@@ -257,19 +259,20 @@ __global__ __launch_bounds__(AR_THREADS) void pnca_decode_run_kernel(const kantt
   const int bw = g.bw_seq ? g.bw_seq[b] : g.bw;
   float* outb = g.out + (long long)b * L * d_out;
   if (bw + 1 > AR_KMAX || bw < 0) {  // only reachable with a device-side band width: poison instead of a wrong answer
-    for (long long i = tid; i < (long long)L * d_out; i += AR_THREADS) outb[i] = __builtin_nanf("");
+    for (long long i = (long long)t0 * d_out + tid; i < (long long)t1 * d_out; i += AR_THREADS) outb[i] = __builtin_nanf("");
     return;
   }
   const long long hkv_ld = (long long)NL * 256;
   const float* memb = g.memory + (long long)b * L * d_mem;
   const float* hkvb = g.hkv + (long long)b * L * hkv_ld;
-  if (tid < AR_D) frame[tid] = 0.f;
+  // the frame fed into step t0: the last d_mel values of the previous step's output row (zero in front of step 0)
+  if (tid < AR_D) frame[tid] = (t0 > 0 && tid < d_mel) ? outb[(long long)(t0 - 1) * d_out + (d_out - d_mel) + tid] : 0.f;
   __syncthreads();
   const ArLnParams lnf = ar_ln_load(F + lay.f_lnf);
 #ifdef AR_PROFILE
   unsigned long long ar_last = wall_clock64();
 #endif
-  for (int step = 0; step < L; ++step) {
+  for (int step = t0; step < t1; ++step) {
     const bool live = step < len;
     if (live) {
       // this step's memory row: in flight while the prenet runs
@@ -466,7 +469,18 @@ extern "C" int kantts_pnca_decode_run(const kantts_decode_args* a, void* stream)
     return KANTTS_E_UNSUPPORTED;
   if (!a->bw_seq && (a->bw < 0 || a->bw + 1 > AR_KMAX)) return KANTTS_E_UNSUPPORTED;
   if (a->B == 0 || a->L == 0) return KANTTS_OK;
-  hipLaunchKernelGGL(pnca_decode_run_kernel, dim3(a->B), dim3(AR_THREADS), 0, (hipStream_t)stream, *a);
+  hipLaunchKernelGGL(pnca_decode_run_kernel, dim3(a->B), dim3(AR_THREADS), 0, (hipStream_t)stream, *a, 0, a->L);
+  KANTTS_CHECK_LAUNCH();
+}
+
+extern "C" int kantts_pnca_decode_range(const kantts_decode_args* a, int t0, int t1, void* stream) {
+  if (!a || !a->w || !a->f || !a->memory || !a->hkv || !a->xkv || !a->out || a->B < 0 || a->L < 0) return KANTTS_E_BADARG;
+  if (t0 < 0 || t1 > a->L || t0 > t1) return KANTTS_E_BADARG;
+  if (a->d_mel < 1 || a->d_mel > AR_D || a->d_mem < 1 || a->d_mem + AR_D > 512 || a->d_out < a->d_mel || a->n_layer < 0)
+    return KANTTS_E_UNSUPPORTED;
+  if (!a->bw_seq && (a->bw < 0 || a->bw + 1 > AR_KMAX)) return KANTTS_E_UNSUPPORTED;
+  if (a->B == 0 || t0 == t1) return KANTTS_OK;
+  hipLaunchKernelGGL(pnca_decode_run_kernel, dim3(a->B), dim3(AR_THREADS), 0, (hipStream_t)stream, *a, t0, t1);
   KANTTS_CHECK_LAUNCH();
 }
 

@@ -78,18 +78,24 @@ __device__ __forceinline__ float lstm_quad_bcast(float v) {
 // no LDS exchange of gates, h double-buffered in LDS, ONE barrier per step.
 // BF16 = true (throughput mode): packed bf16 pairs with fp32 accumulation (v_dot2_f32_bf16); gates, cell state and
 // outputs stay fp32.
-template <bool BF16>
+// RANGE = true (kantts_lstm_fwd_range; one forward direction): steps [t0, min(t1, len)) from the state the full-length
+// buffers hold -- h = out[b, t0 - 1], c = c_out[b, t0 - 1] -- with the gx ring clamped to the last step of the RANGE (later
+// rows of gx do not exist yet) and the zero tail written for rows [max(len, t0), t1) only.  RANGE = false ignores t0 / t1:
+// every range expression below folds to the whole-sequence one at compile time, so the whole-sequence kernels (the pair form is
+// out of registers) pay nothing for the range form.
+template <bool BF16, bool RANGE>
 __global__ __launch_bounds__(LG) void lstm_fwd_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
                                                       const float* __restrict__ bhh, const int32_t* __restrict__ lens,
                                                       float* __restrict__ out, float* __restrict__ gates_out,
                                                       float* __restrict__ c_out, int B, int T, int ndir,
-                                                      int reverse_first) {
+                                                      int reverse_first, int t0, int t1) {
   __shared__ __attribute__((aligned(16))) float h_s[2][LH];
   __shared__ __attribute__((aligned(16))) __bf16 h_b[2][LH];
   const int tid = threadIdx.x, j = tid >> 2, kq = tid & 3;
   const int b = blockIdx.x, dir = blockIdx.y;
-  const bool rev = reverse_first ? true : (dir == 1);
+  const bool rev = RANGE ? false : (reverse_first ? true : (dir == 1));
   const int len = lens ? min(max(lens[b], 0), T) : T;  // clamped into [0, T]: the tail loops below start at len
+  const int s_beg = RANGE ? t0 : 0, s_end = RANGE ? min(len, t1) : len;  // the steps this launch runs
   float w[BF16 ? 1 : 4 * 32];
   lstm_bf16x2 wq[BF16 ? 4 * 16 : 1];
 #pragma unroll
@@ -121,20 +127,28 @@ __global__ __launch_bounds__(LG) void lstm_fwd_kernel(const float* __restrict__ 
   float* outb = out + (long long)b * T * ndir * LH + dir * LH;
   float* gob = gates_out + (((long long)dir * B + b) * T) * LG + 4 * j + kq;
   float* cob = c_out + (((long long)dir * B + b) * T) * LH;
+  if (RANGE && s_beg > 0 && s_beg < s_end) {  // resume: the state step t0 - 1 left behind (nothing to run: it stays zero)
+    const float h0 = outb[(s_beg - 1) * ndir * LH + j];
+    c = cob[(s_beg - 1) * LH + j];
+    if (kq == 0) {
+      h_s[0][j] = h0;
+      h_b[0][j] = (__bf16)h0;  // the rounding the producing step applied when it published h
+    }
+  }
   __syncthreads();
   // gx[t] comes from L2 / HBM (0.5-2 us) while a step is ~0.4 us: the values of the next chunk of steps are loaded --
   // unconditionally, steps clamped into the sequence -- at the top of a chunk and first touched a whole chunk later
   // (a load inside an `if`, or a ring interleaved with the steps, puts a vmcnt(0) / vmcnt(1) wait on every step).
   constexpr int PF = 8;
   float gq[PF], gn[PF];
-  const int last = len > 0 ? len - 1 : 0;
+  const int last = RANGE ? max(s_end - 1, s_beg) : (len > 0 ? len - 1 : 0);  // RANGE: row t0 exists (t0 < t1)
 #pragma unroll
   for (int u = 0; u < PF; ++u) {
-    const int su = min(u, last);
+    const int su = min(s_beg + u, last);
     gq[u] = gxb[(rev ? last - su : su) * gx_ld];
   }
   int cur = 0;
-  for (int step0 = 0; step0 < len; step0 += PF) {
+  for (int step0 = s_beg; step0 < s_end; step0 += PF) {
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
       const int sn = min(step0 + PF + u, last);
@@ -143,7 +157,7 @@ __global__ __launch_bounds__(LG) void lstm_fwd_kernel(const float* __restrict__ 
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
       const int step = step0 + u;
-      if (step >= len) break;
+      if (step >= s_end) break;
       const int t = rev ? len - 1 - step : step;
       float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
       if (BF16) {
@@ -203,7 +217,7 @@ __global__ __launch_bounds__(LG) void lstm_fwd_kernel(const float* __restrict__ 
     for (int u = 0; u < PF; ++u) gq[u] = gn[u];
   }
   // zero the padded tail (pad_packed_sequence) -- outputs only; saved state is never read there
-  for (int tt = len; tt < T; ++tt)
+  for (int tt = RANGE ? max(len, t0) : len; tt < (RANGE ? t1 : T); ++tt)
     if (tid < LH) outb[(long long)tt * ndir * LH + tid] = 0.f;
 }
 
@@ -221,16 +235,19 @@ __global__ __launch_bounds__(LG) void lstm_fwd_kernel(const float* __restrict__ 
 // finds its own cell in its own accumulator, B = h broadcast) issued between the 64 v_dot2 of (i, f), one MFMA per four
 // v_dot2: 0.70 us per step against 0.57 -- the step is a latency chain, not an issue-bound loop, and the accumulators of
 // four dependent 16-cycle MFMAs arrive later than the last v_dot2.
+// RANGE: as in lstm_fwd_kernel.
+template <bool RANGE>
 __global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
                                                            const float* __restrict__ bhh, const int32_t* __restrict__ lens,
                                                            float* __restrict__ out, float* __restrict__ gates_out,
                                                            float* __restrict__ c_out, int B, int T, int ndir,
-                                                           int reverse_first) {
+                                                           int reverse_first, int t0, int t1) {
   __shared__ __attribute__((aligned(16))) __bf16 h_b[2][LH];
   const int tid = threadIdx.x, j = tid >> 1, p = tid & 1;
   const int b = blockIdx.x, dir = blockIdx.y;
-  const bool rev = reverse_first ? true : (dir == 1);
+  const bool rev = RANGE ? false : (reverse_first ? true : (dir == 1));
   const int len = lens ? min(max(lens[b], 0), T) : T;  // clamped into [0, T]: the tail loops below start at len
+  const int s_beg = RANGE ? t0 : 0, s_end = RANGE ? min(len, t1) : len;  // the steps this launch runs
   lstm_bf16x2 wq[4 * 32];
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -254,6 +271,10 @@ __global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restr
   float* outb = out + (long long)b * T * ndir * LH + dir * LH;
   float* gob = gates_out + (((long long)dir * B + b) * T) * LG + 4 * j + 2 * p;
   float* cob = c_out + (((long long)dir * B + b) * T) * LH;
+  if (RANGE && s_beg > 0 && s_beg < s_end) {  // resume: the state step t0 - 1 left behind (nothing to run: it stays zero)
+    c = cob[(s_beg - 1) * LH + j];
+    if (p == 0) h_b[0][j] = (__bf16)outb[(s_beg - 1) * ndir * LH + j];  // the rounding the producing step published h with
+  }
   __syncthreads();
   // gx + bias of the next PF steps wait in ONE register ring: slot u is refilled, in place, by the step that has just read
   // it (the load for step + PF lands during the PF - 1 steps in between; the in-order vector-memory counter lets the next
@@ -262,10 +283,10 @@ __global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restr
   // (the h fragments of a step were read through four registers with a full LDS round trip exposed before the first product).
   constexpr int PF = 8;
   float gq0[PF], gq1[PF];
-  const int last = len > 0 ? len - 1 : 0;
+  const int last = RANGE ? max(s_end - 1, s_beg) : (len > 0 ? len - 1 : 0);  // RANGE: row t0 exists (t0 < t1)
 #pragma unroll
   for (int u = 0; u < PF; ++u) {
-    const int su = min(u, last);
+    const int su = min(s_beg + u, last);
     const int o = (rev ? last - su : su) * gx_ld;
     gq0[u] = gxb[o];
     gq1[u] = gxb[o + LH];
@@ -276,11 +297,11 @@ __global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restr
   const int opitch_sel = p;  // (pitch LH for lane 1, ndir * LH for lane 0: two scalar products and one select per step)
   int cur = 0;
   float p_sink = 0.f;  // (ablation builds only: keeps the chain alive when the stores are masked)
-  for (int step0 = 0; step0 < len; step0 += PF) {
+  for (int step0 = s_beg; step0 < s_end; step0 += PF) {
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
       const int step = step0 + u;
-      if (step < len) {  // uniform
+      if (step < s_end) {  // uniform
         const int t = rev ? len - 1 - step : step;
         float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
         const uint4* hp = reinterpret_cast<const uint4*>(&h_b[cur][p * 64]);
@@ -328,7 +349,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restr
       }
     }
   }
-  for (int tt = len; tt < T; ++tt)
+  for (int tt = RANGE ? max(len, t0) : len; tt < (RANGE ? t1 : T); ++tt)
     if (tid < LH) outb[(long long)tt * ndir * LH + tid] = 0.f;
   if ((LSTM_ABL & 1) && p_sink == 123.456f) outb[0] = p_sink;
 }
@@ -644,14 +665,38 @@ extern "C" int kantts_lstm_fwd(const float* gx, const float* whh, const float* b
   if (B == 0 || T == 0) return KANTTS_OK;
   static const char* env_pair = getenv("KANTTS_LSTM_PAIR");  // A/B switch (read once per process): 0 = the quad kernel
   if (precision == 1 && !(env_pair && atoi(env_pair) == 0))
-    hipLaunchKernelGGL(lstm_fwd_pair_kernel, dim3(B, ndir), dim3(256), 0, (hipStream_t)stream, gx, whh, bhh, lens, out,
-                       gates_save, c_save, B, T, ndir, reverse_first);
+    hipLaunchKernelGGL((lstm_fwd_pair_kernel<false>), dim3(B, ndir), dim3(256), 0, (hipStream_t)stream, gx, whh,
+                       bhh, lens, out, gates_save, c_save, B, T, ndir, reverse_first, 0, T);
   else if (precision == 1)
-    hipLaunchKernelGGL(lstm_fwd_kernel<true>, dim3(B, ndir), dim3(LG), 0, (hipStream_t)stream, gx, whh, bhh, lens, out,
-                       gates_save, c_save, B, T, ndir, reverse_first);
+    hipLaunchKernelGGL((lstm_fwd_kernel<true, false>), dim3(B, ndir), dim3(LG), 0, (hipStream_t)stream, gx, whh,
+                       bhh, lens, out, gates_save, c_save, B, T, ndir, reverse_first, 0, T);
   else
-    hipLaunchKernelGGL(lstm_fwd_kernel<false>, dim3(B, ndir), dim3(LG), 0, (hipStream_t)stream, gx, whh, bhh, lens, out,
-                       gates_save, c_save, B, T, ndir, reverse_first);
+    hipLaunchKernelGGL((lstm_fwd_kernel<false, false>), dim3(B, ndir), dim3(LG), 0, (hipStream_t)stream, gx, whh,
+                       bhh, lens, out, gates_save, c_save, B, T, ndir, reverse_first, 0, T);
+  KANTTS_CHECK_LAUNCH();
+}
+
+// Steps [t0, min(t1, len)) of ONE forward direction over full-length buffers that persist between calls (see the RANGE note
+// at lstm_fwd_kernel).  KANTTS_LSTM_PAIR=0 is honoured exactly as in kantts_lstm_fwd, so that a range and the whole-sequence
+// call it is compared with always run the same arithmetic.
+extern "C" int kantts_lstm_fwd_range(const float* gx, const float* whh, const float* bhh, const int32_t* lens, float* out,
+                                     float* gates_save, float* c_save, int B, int T, int H, int ndir, int reverse_first,
+                                     int t0, int t1, int precision, void* stream) {
+  if (!gx || !whh || !out || !gates_save || !c_save || B < 0 || T < 0 || ndir < 1 || ndir > 2) return KANTTS_E_BADARG;
+  if (t0 < 0 || t1 > T || t0 > t1) return KANTTS_E_BADARG;
+  if (H != LH || ndir != 1 || reverse_first) return KANTTS_E_UNSUPPORTED;
+  if ((long long)T * LG >= (1ll << 31)) return KANTTS_E_UNSUPPORTED;  // 32-bit offsets inside one sequence
+  if (B == 0 || t0 == t1) return KANTTS_OK;
+  static const char* env_pair = getenv("KANTTS_LSTM_PAIR");  // A/B switch (read once per process): 0 = the quad kernel
+  if (precision == 1 && !(env_pair && atoi(env_pair) == 0))
+    hipLaunchKernelGGL((lstm_fwd_pair_kernel<true>), dim3(B, 1), dim3(256), 0, (hipStream_t)stream, gx, whh, bhh,
+                       lens, out, gates_save, c_save, B, T, 1, 0, t0, t1);
+  else if (precision == 1)
+    hipLaunchKernelGGL((lstm_fwd_kernel<true, true>), dim3(B, 1), dim3(LG), 0, (hipStream_t)stream, gx, whh, bhh,
+                       lens, out, gates_save, c_save, B, T, 1, 0, t0, t1);
+  else
+    hipLaunchKernelGGL((lstm_fwd_kernel<false, true>), dim3(B, 1), dim3(LG), 0, (hipStream_t)stream, gx, whh, bhh,
+                       lens, out, gates_save, c_save, B, T, 1, 0, t0, t1);
   KANTTS_CHECK_LAUNCH();
 }
 

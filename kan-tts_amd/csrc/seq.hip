@@ -262,18 +262,22 @@ extern "C" int kantts_lr_gather_bwd(const float* dout, const int32_t* cs, const 
 // ------------------------------------------------------------------------------------------------
 // FSMN memory block (channels-last):  xm = x * keep;  y = keep * (sum_k w[c,k] xm[t+k-lp] + xm[t]) (+ res)
 // keep[b,t] = t < lens[b] (all ones when lens == NULL).  Block = one (b, 32-frame tile), thread = channel.
+// ROWS = true (kantts_fsmn_dwconv_fwd_rows): the tiles start at row r0 and only rows [r0, r1) are computed; a row sums its
+// taps in the same order wherever it sits in a tile, so it equals the same row of a whole call bit for bit.  ROWS = false
+// ignores r0 / r1.
 #define DW_TT 32
+template <bool ROWS>
 __global__ void fsmn_dwconv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                        const float* __restrict__ res, const int64_t* __restrict__ lens,
-                                       float* __restrict__ y, int B, int T, int C, int K, int lp) {
-  const int b = blockIdx.y, t0 = blockIdx.x * DW_TT;
+                                       float* __restrict__ y, int B, int T, int C, int K, int lp, int r0, int r1) {
+  const int b = blockIdx.y, t0 = (ROWS ? r0 : 0) + blockIdx.x * DW_TT;
   const int len = lens ? (int)min((long long)lens[b], (long long)T) : T;
   const float* xb = x + (long long)b * T * C;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     const float* wc = w + (long long)c * K;
     for (int tt = 0; tt < DW_TT; ++tt) {
       const int t = t0 + tt;
-      if (t >= T) break;
+      if (t >= (ROWS ? r1 : T)) break;
       float acc = 0.f;
       if (t < len) {
         for (int k = 0; k < K; ++k) {
@@ -343,11 +347,14 @@ __global__ void fsmn_dwconv_bwd_dw_kernel(const float* __restrict__ dy, const fl
 // wave reads 256 B per load.  FLIP turns the same code into the input-gradient FIR.
 #define FS_K 41
 #define FS_TT 16
-template <bool FLIP>
+// ROWS = true (kantts_fsmn_dwconv_fwd_rows; forward only): the 16-frame tiles start at row r0, rows at or after r1 are not
+// written, and no input row at or after r1 + (K - 1 - lp) is read -- in a streaming caller those rows do not exist yet.
+// ROWS = false ignores r0 / r1.
+template <bool FLIP, bool ROWS>
 __global__ __launch_bounds__(256, 2) void fsmn_fir41_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ res,
                                                         const int64_t* __restrict__ lens, float* __restrict__ y, int B,
-                                                        int T, int C, int lp, int xcd_order) {
+                                                        int T, int C, int lp, int xcd_order, int r0, int r1) {
   // [round 6] XCD-aware order: a block reads a 56-frame window for its 16 output frames, so neighbouring blocks share 40 of
   // their rows -- and consecutive block ids are dealt to the 8 XCDs in turn, each with its own L2: the counters showed
   // 2.6 x the input fetched from HBM / the memory-side cache (profiles/r06_runFINAL_fetch_pmc.txt: 52 MB for 20 MB at the
@@ -363,9 +370,11 @@ __global__ __launch_bounds__(256, 2) void fsmn_fir41_kernel(const float* __restr
       bx = vid - by * gx;
     }
   }
-  const int b = by, t0 = bx * FS_TT;
+  const int b = by, t0 = (ROWS ? r0 : 0) + bx * FS_TT;
   const int len = lens ? (int)min((long long)lens[b], (long long)T) : T;
   const int lpe = FLIP ? (FS_K - 1 - lp) : lp;
+  const int xlim = ROWS ? min(len, r1 + (FS_K - 1 - lpe)) : len;  // first input row that is not read
+  const int tlim = ROWS ? r1 : T;                                  // first output row that is not written
   const float* xb = x + (long long)b * T * C;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     float wk[FS_K];
@@ -375,7 +384,7 @@ __global__ __launch_bounds__(256, 2) void fsmn_fir41_kernel(const float* __restr
 #pragma unroll
     for (int n = 0; n < FS_TT + FS_K - 1; ++n) {
       const int ts = t0 + n - lpe;
-      const bool ok = (ts >= 0) && (ts < len);
+      const bool ok = (ts >= 0) && (ts < xlim);
       const float v = xb[(long long)(ok ? ts : 0) * C + c];
       xin[n] = ok ? v : 0.f;
     }
@@ -383,7 +392,7 @@ __global__ __launch_bounds__(256, 2) void fsmn_fir41_kernel(const float* __restr
 #pragma unroll
     for (int o = 0; o < FS_TT; ++o) {
       const int t = t0 + o;
-      const bool ok = t < len;
+      const bool ok = t < (ROWS ? min(len, r1) : len);
       const float v = xb[(long long)(ok ? t : 0) * C + c];
       ctr[o] = ok ? v : 0.f;
     }
@@ -393,7 +402,7 @@ __global__ __launch_bounds__(256, 2) void fsmn_fir41_kernel(const float* __restr
       float acc = ctr[o];
 #pragma unroll
       for (int k = 0; k < FS_K; ++k) acc = fmaf(wk[k], xin[o + k], acc);
-      if (t < T) {
+      if (t < tlim) {
         const long long oidx = ((long long)b * T + t) * C + c;
         float outv = (t < len) ? acc : 0.f;
         if (!FLIP && res) outv += res[oidx];  // (requesting these rows with the window was measured: 19.3 us against 15.9 --
@@ -506,11 +515,28 @@ extern "C" int kantts_fsmn_dwconv_fwd(const float* x, const float* w, const floa
   if (B == 0 || T == 0) return KANTTS_OK;
   const int threads = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
   if (K == FS_K) {
-    hipLaunchKernelGGL(fsmn_fir41_kernel<false>, dim3(kantts_cdiv(T, FS_TT), B), dim3(threads), 0, (hipStream_t)stream, x, w,
-                       res, lens, y, B, T, C, left_pad, fs_xcd_order());
+    hipLaunchKernelGGL((fsmn_fir41_kernel<false, false>), dim3(kantts_cdiv(T, FS_TT), B), dim3(threads), 0,
+                       (hipStream_t)stream, x, w, res, lens, y, B, T, C, left_pad, fs_xcd_order(), 0, T);
   } else {
-    hipLaunchKernelGGL(fsmn_dwconv_fwd_kernel, dim3(kantts_cdiv(T, DW_TT), B), dim3(threads), 0, (hipStream_t)stream, x, w,
-                       res, lens, y, B, T, C, K, left_pad);
+    hipLaunchKernelGGL(fsmn_dwconv_fwd_kernel<false>, dim3(kantts_cdiv(T, DW_TT), B), dim3(threads), 0, (hipStream_t)stream, x,
+                       w, res, lens, y, B, T, C, K, left_pad, 0, T);
+  }
+  KANTTS_CHECK_LAUNCH();
+}
+
+// Rows [t0, t1) of the same block over full-length buffers: reads x rows [t0 - left_pad, t1 + (K - 1 - left_pad)) inside
+// [0, min(len, T)) and nothing else, writes no other row of y (res is indexed like y).
+extern "C" int kantts_fsmn_dwconv_fwd_rows(const float* x, const float* w, const float* res, const int64_t* lens, float* y,
+                                           int B, int T, int C, int K, int left_pad, int t0, int t1, void* stream) {
+  if (!x || !w || !y || B < 0 || T < 0 || C < 1 || K < 1 || t0 < 0 || t1 > T || t0 > t1) return KANTTS_E_BADARG;
+  if (B == 0 || t0 == t1) return KANTTS_OK;
+  const int threads = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
+  if (K == FS_K) {
+    hipLaunchKernelGGL((fsmn_fir41_kernel<false, true>), dim3(kantts_cdiv(t1 - t0, FS_TT), B), dim3(threads), 0,
+                       (hipStream_t)stream, x, w, res, lens, y, B, T, C, left_pad, fs_xcd_order(), t0, t1);
+  } else {
+    hipLaunchKernelGGL(fsmn_dwconv_fwd_kernel<true>, dim3(kantts_cdiv(t1 - t0, DW_TT), B), dim3(threads), 0,
+                       (hipStream_t)stream, x, w, res, lens, y, B, T, C, K, left_pad, t0, t1);
   }
   KANTTS_CHECK_LAUNCH();
 }
@@ -528,8 +554,8 @@ extern "C" int kantts_fsmn_dwconv_bwd(const float* dy, const float* x, const flo
     const int nchunk = kantts_cdiv(T, FS_CH);
     if (dw_accum && (!workspace || ws_floats < (long long)B * nchunk * C * K)) return KANTTS_E_WORKSPACE;
     if (dx)
-      hipLaunchKernelGGL(fsmn_fir41_kernel<true>, dim3(kantts_cdiv(T, FS_TT), B), dim3(threads), 0, st, dy, w,
-                         (const float*)nullptr, lens, dx, B, T, C, left_pad, fs_xcd_order());
+      hipLaunchKernelGGL((fsmn_fir41_kernel<true, false>), dim3(kantts_cdiv(T, FS_TT), B), dim3(threads), 0, st, dy,
+                         w, (const float*)nullptr, lens, dx, B, T, C, left_pad, fs_xcd_order(), 0, T);
     if (dw_accum) {
       hipLaunchKernelGGL(fsmn_dw41_partial_kernel, dim3(nchunk, B, kantts_cdiv(C, 64)), dim3(256), 0, st, dy, x, lens,
                          workspace, B, T, C, left_pad);

@@ -447,6 +447,9 @@ def lib():
         L.kantts_scale_to_many.argtypes = [p, f, POINTER(c_void_p), i, ll, p]
         L.kantts_ragged_rows_i64.argtypes = [p, p, p, p, p, p, i, i, i, i, p]
         L.kantts_sconv_launch.argtypes = [POINTER(SConvArgs), c_void_p]
+        L.kantts_pnca_decode_range.argtypes = [POINTER(DecodeArgs), c_int, c_int, c_void_p]
+        L.kantts_lstm_fwd_range.argtypes = [p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, p]
+        L.kantts_fsmn_dwconv_fwd_rows.argtypes = [p, p, p, p, p, i, i, i, i, i, i, i, p]
         _lib = L
     return _lib
 
@@ -471,6 +474,7 @@ EXPORTED_SYMBOLS = [
     "kantts_melspec_tuning", "kantts_teacher_plan", "kantts_copy_roof", "kantts_pnca_attn_qkv_bwd",
     "kantts_pnca_decode_run", "kantts_pnca_decode_blob_sizes", "kantts_dur_ar_run", "kantts_dur_ar_run_f32", "kantts_ctc_attn", "kantts_ctc_attn_workspace", "kantts_enc_attn_fwd",
     "kantts_launch_tuning", "kantts_sconv_launch",
+    "kantts_pnca_decode_range", "kantts_lstm_fwd_range", "kantts_fsmn_dwconv_fwd_rows",
 ]
 
 
@@ -906,8 +910,10 @@ def decode_blob_sizes(d_mel, d_mem, d_out, n_layer):
     return None if rc != 0 else (int(w.value), int(f.value))
 
 
-def pnca_decode_run(w, f, memory, hkv, xkv, out, lens32, bw_seq, bw, d_mel, n_layer, in_scale, eps):
-    """Every step of the free-running mel decoder for every sequence in one launch (csrc/ar_infer.hip)."""
+def pnca_decode_run(w, f, memory, hkv, xkv, out, lens32, bw_seq, bw, d_mel, n_layer, in_scale, eps, steps=None):
+    """Every step of the free-running mel decoder for every sequence in one launch (csrc/ar_infer.hip).
+    ``steps=(t0, t1)``: only those steps, resuming from what earlier calls left in ``out`` / ``xkv``
+    (kantts_pnca_decode_range); returns the library's status code instead of raising."""
     B, L, d_mem = memory.shape
     g = DecodeArgs()
     g.w, g.f = ptr(w, torch.bfloat16), ptr(f, torch.float32)
@@ -917,7 +923,35 @@ def pnca_decode_run(w, f, memory, hkv, xkv, out, lens32, bw_seq, bw, d_mel, n_la
     g.in_scale, g.eps = float(in_scale), float(eps)
     for t in (memory, hkv, xkv, out):
         assert t.is_contiguous()
+    if steps is not None:
+        return lib().kantts_pnca_decode_range(ctypes.byref(g), int(steps[0]), int(steps[1]), stream())
     check(lib().kantts_pnca_decode_run(ctypes.byref(g), stream()), "pnca_decode_run")
+
+
+def range_entry_points():
+    """True when the loaded library exports the three streaming (range) entry points of ChunkedAcoustic."""
+    L = lib()
+    return all(hasattr(L, n) for n in ("kantts_pnca_decode_range", "kantts_lstm_fwd_range", "kantts_fsmn_dwconv_fwd_rows"))
+
+
+def lstm_fwd_range(gx, whh, bhh, lens32, out, gates, cst, t0, t1, precision, ndir=1, reverse_first=0):
+    """Steps [t0, t1) of the forward LSTM recurrence over full-length buffers (csrc/lstm.hip); returns the status code."""
+    B, T, H = out.shape[0], out.shape[1], whh.shape[-1]
+    for t in (gx, whh, out, gates, cst):
+        assert t.is_contiguous()
+    return lib().kantts_lstm_fwd_range(ptr(gx, torch.float32), ptr(whh, torch.float32), ptr(bhh), ptr(lens32), ptr(out),
+                                       ptr(gates), ptr(cst), int(B), int(T), int(H), int(ndir), int(reverse_first), int(t0),
+                                       int(t1), int(precision), stream())
+
+
+def fsmn_dwconv_fwd_rows(x, w, res, lens64, y, left_pad, t0, t1):
+    """Rows [t0, t1) of the FSMN memory block over full-length buffers (csrc/seq.hip); returns the status code."""
+    B, T, C = x.shape
+    for t in (x, w, y) + (() if res is None else (res,)):
+        assert t.is_contiguous()
+    return lib().kantts_fsmn_dwconv_fwd_rows(ptr(x, torch.float32), ptr(w, torch.float32), ptr(res), ptr(lens64), ptr(y),
+                                             int(B), int(T), int(C), int(w.shape[-1]), int(left_pad), int(t0), int(t1),
+                                             stream())
 
 
 def dur_ar_run(w, f, gc, out, lens32):

@@ -10,6 +10,7 @@ from the reference package layout if it is installed, or accepts any object with
 import argparse
 import logging
 import os
+import time
 
 import numpy as np
 import torch
@@ -19,7 +20,9 @@ logging.basicConfig(format="%(asctime)s, %(levelname)-4s [%(filename)s:%(lineno)
                     datefmt="%Y-%m-%d:%H:%M:%S", level=logging.INFO)
 
 
-def am_synthesis(symbol_seq, fsnet, ling_unit, device, se=None):
+def am_synthesis(symbol_seq, fsnet, ling_unit, device, se=None, chunked=None, chunk_steps=None, chunk_times=None):
+    """``chunked`` (a ChunkedAcoustic of ``fsnet``) with ``chunk_steps``: the same outputs through a streaming session;
+    the seconds after which each chunk's frames were on the host are appended to ``chunk_times``."""
     if ling_unit.using_byte():
         raise NotImplementedError("byte-index inputs (sambert_16k_MAS_byte.yaml) are outside the hot path")
     feats = ling_unit.encode_symbol_sequence(symbol_seq)
@@ -34,7 +37,16 @@ def am_synthesis(symbol_seq, fsnet, ling_unit, device, se=None):
     else:
         inputs_spk = spk.unsqueeze(0)[:, :-1]
     inputs_len = torch.full((1,), inputs_emo.size(1), dtype=torch.long, device=device)
-    res = fsnet(inputs_ling, inputs_emo, inputs_spk, inputs_len)
+    if chunked is not None:
+        t0 = time.time()
+        sess = chunked.open(inputs_ling, inputs_emo, inputs_spk, inputs_len)
+        for _, hi, mel in sess.stream(chunk_steps):
+            if mel.size(1) and chunk_times is not None:
+                mel.cpu()  # the copy to the host is when a chunk can be handed on
+                chunk_times.append(time.time() - t0)
+        res = sess.result()
+    else:
+        res = fsnet(inputs_ling, inputs_emo, inputs_spk, inputs_len)
     valid_length = int(res["LR_length_rounded"][0].item())
     dec_outputs = res["dec_outputs"][0, :valid_length, :].cpu().numpy()
     postnet_outputs = res["postnet_outputs"][0, :valid_length, :].cpu().numpy()
@@ -55,7 +67,7 @@ def denorm_f0(mel, scale, offset, f0_threshold=30.0, uv_threshold=0.6):
     return mel
 
 
-def am_infer(sentence, ckpt, output_dir, se_file=None, config=None, ling_unit=None):
+def am_infer(sentence, ckpt, output_dir, se_file=None, config=None, ling_unit=None, chunk_frames=None):
     device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
     if not isinstance(config, dict):
         path = config if config is not None else os.path.join(os.path.dirname(os.path.dirname(ckpt)), "config.yaml")
@@ -94,6 +106,14 @@ def am_infer(sentence, ckpt, output_dir, se_file=None, config=None, ling_unit=No
         # bf16 mode: each autoregressive loop is one launch (kantts/models/sambert/ar_kernels.py); otherwise one decoder
         # step = one hipGraph replay (kantts/models/sambert/decode_graph.py)
         fsnet.mel_decoder.decode_mode = "kernel"
+    chunked, chunk_steps, first_chunk, chunk_ms, totals = None, None, [], [], []
+    if chunk_frames is not None:
+        r = fsnet.mel_decoder.r
+        if chunk_frames < 1 or chunk_frames % r:
+            raise ValueError("--chunk_frames must be a positive multiple of outputs_per_step (%d), got %d" % (r, chunk_frames))
+        from kantts.models.sambert.chunked import ChunkedAcoustic
+
+        chunked, chunk_steps = ChunkedAcoustic(fsnet), chunk_frames // r  # refuses what it cannot stream, loudly
     with open(sentence, encoding="utf-8") as f:
         for line in f:
             line = line.strip().split("\t")
@@ -101,13 +121,24 @@ def am_infer(sentence, ckpt, output_dir, se_file=None, config=None, ling_unit=No
                 continue
             logging.info("Inference sentence: %s", line[0])
             with torch.no_grad():
-                _, mel_post, dur, f0, energy = am_synthesis(line[1], fsnet, ling_unit, device, se=se)
+                times = []
+                _, mel_post, dur, f0, energy = am_synthesis(line[1], fsnet, ling_unit, device, se=se, chunked=chunked,
+                                                            chunk_steps=chunk_steps, chunk_times=times)
+            if times:
+                first_chunk.append(times[0])
+                chunk_ms += list(np.diff([0.0] + times))
+                totals.append(times[-1])
             if nsf is not None:
                 mel_post = denorm_f0(mel_post, scale=nsf[0], offset=nsf[1])
             np.save("%s/%s_mel.npy" % (results_dir, line[0]), mel_post)
             np.savetxt("%s/%s_dur.txt" % (results_dir, line[0]), dur)
             np.savetxt("%s/%s_f0.txt" % (results_dir, line[0]), f0)
             np.savetxt("%s/%s_energy.txt" % (results_dir, line[0]), energy)
+    if chunked is not None and first_chunk:
+        logging.info("Finished chunked inference of %d utterances (%d frames per chunk, time to first chunk: median %.2f ms, "
+                     "first utterance %.2f ms; median chunk %.2f ms; total %.2f ms per utterance).", len(first_chunk),
+                     chunk_frames, 1e3 * float(np.median(first_chunk)), 1e3 * first_chunk[0],
+                     1e3 * float(np.median(chunk_ms)), 1e3 * float(np.mean(totals)))
 
 
 if __name__ == "__main__":
@@ -116,5 +147,15 @@ if __name__ == "__main__":
     parser.add_argument("--output_dir", type=str, required=True)
     parser.add_argument("--ckpt", type=str, required=True)
     parser.add_argument("--se_file", type=str, required=False)
+    parser.add_argument("--chunk_frames", type=int, default=None,
+                        help="Infer chunk by chunk through a streaming session, this many mel frames at a time (a multiple "
+                             "of outputs_per_step; bf16 mode)")
     args = parser.parse_args()
-    am_infer(args.sentence, args.ckpt, args.output_dir, args.se_file)
+    if args.chunk_frames is not None and args.chunk_frames < 1:
+        parser.error("--chunk_frames must be positive")
+    try:
+        am_infer(args.sentence, args.ckpt, args.output_dir, args.se_file, chunk_frames=args.chunk_frames)
+    except ValueError as e:
+        if "--chunk_frames" not in str(e):
+            raise
+        parser.error(str(e))

@@ -10,6 +10,7 @@ deliberate (documented in DESIGN.md):
     FP / byte-input variants raise NotImplementedError.
 """
 import contextlib
+import types
 
 import torch
 import torch.nn as nn
@@ -622,9 +623,17 @@ class KanTtsSAMBERT(nn.Module):
             plan["dec_prenet"] = self.mel_decoder.mel_dec.prenet(plan["dec_input"])  # reads the target frames only
         return plan
 
-    def forward(self, inputs_ling, inputs_emotion, inputs_speaker, input_lengths, output_lengths=None,
-                mel_targets=None, duration_targets=None, pitch_targets=None, energy_targets=None, attn_priors=None,
-                fp_label=None):
+    _TOKEN_SIDE_FIELDS = ("batch_size", "is_training", "tplan", "memory", "bw_int", "bw_dev", "x_band_width", "h_band_width",
+                          "lfr_info", "out_info", "enc_sla_attn_lst", "LR_length_rounded", "log_duration_predictions",
+                          "pitch_predictions", "energy_predictions", "duration_targets", "pitch_targets", "energy_targets",
+                          "inter_lengths", "LR_text_outputs", "LR_emo_outputs", "LR_spk_outputs", "ling_embedding",
+                          "attn_soft", "attn_hard", "attn_logprob")
+
+    def _token_side(self, inputs_ling, inputs_emotion, inputs_speaker, input_lengths, output_lengths=None,
+                    mel_targets=None, duration_targets=None, pitch_targets=None, energy_targets=None, attn_priors=None):
+        """Everything of ``forward`` in front of the mel decoder: text encoder, variance adaptor (duration loop), length
+        regulator, the decoder's memory, masks and band widths.  It fixes the utterance's frame count before the first
+        decoder step; ``forward`` and the streaming session of chunked.py (ChunkedAcoustic.open) both start here."""
         batch_size = inputs_ling.size(0)
         r = self.mel_decoder.r
         T_in = inputs_ling.size(1)
@@ -723,6 +732,16 @@ class KanTtsSAMBERT(nn.Module):
             bw_int = 0
         else:
             x_band_width = h_band_width = bw_int = int(bw_val)  # host sync, as in the reference (:981-993)
+        here = locals()
+        return types.SimpleNamespace(**{k: here[k] for k in self._TOKEN_SIDE_FIELDS})
+
+    def forward(self, inputs_ling, inputs_emotion, inputs_speaker, input_lengths, output_lengths=None,
+                mel_targets=None, duration_targets=None, pitch_targets=None, energy_targets=None, attn_priors=None,
+                fp_label=None):
+        ts = self._token_side(inputs_ling, inputs_emotion, inputs_speaker, input_lengths, output_lengths, mel_targets,
+                              duration_targets, pitch_targets, energy_targets, attn_priors)
+        batch_size, tplan, memory, bw_int, bw_dev = ts.batch_size, ts.tplan, ts.memory, ts.bw_int, ts.bw_dev
+        lfr_info, out_info = ts.lfr_info, ts.out_info
         from kantts._hip import ops_bf16
 
         bound_before = ops_bf16.BAND_BOUND["max"]
@@ -743,43 +762,47 @@ class KanTtsSAMBERT(nn.Module):
                                                                                          dec_outputs.size(1))
         deferred = getattr(self.variance_adaptor, "deferred", None)
         if deferred is not None and not _PREDICTORS_AFTER_POSTNET:
-            log_duration_predictions, pitch_predictions, energy_predictions = deferred()
+            ts.log_duration_predictions, ts.pitch_predictions, ts.energy_predictions = deferred()
         # postnet residual add + final masking ride in the epilogue of the last GEMM
         postnet_outputs = self.mel_postnet(dec_outputs, post_info, res=dec_outputs, zero_rows=post_info.mask)
         if deferred is not None and _PREDICTORS_AFTER_POSTNET:
-            log_duration_predictions, pitch_predictions, energy_predictions = deferred()
+            ts.log_duration_predictions, ts.pitch_predictions, ts.energy_predictions = deferred()
         self.variance_adaptor.deferred = None
         ops.side_branch.join()  # the predictors' outputs are read from here on (losses)
+        return self._result(ts, mel_targets, dec_outputs, postnet_outputs, pnca_x_attn_lst, pnca_h_attn_lst)
+
+    def _result(self, ts, mel_targets, dec_outputs, postnet_outputs, pnca_x_attn_lst, pnca_h_attn_lst):
+        """The dictionary ``forward`` returns, from the token side ``ts`` and the decoder / post-net outputs."""
         res = {
-            "x_band_width": x_band_width,
-            "h_band_width": h_band_width,
-            "enc_slf_attn_lst": enc_sla_attn_lst,
+            "x_band_width": ts.x_band_width,
+            "h_band_width": ts.h_band_width,
+            "enc_slf_attn_lst": ts.enc_sla_attn_lst,
             "pnca_x_attn_lst": pnca_x_attn_lst,
             "pnca_h_attn_lst": pnca_h_attn_lst,
             "dec_outputs": dec_outputs,
             "postnet_outputs": postnet_outputs,
-            "LR_length_rounded": LR_length_rounded,
-            "log_duration_predictions": log_duration_predictions,
-            "pitch_predictions": pitch_predictions,
-            "energy_predictions": energy_predictions,
-            "duration_targets": duration_targets,
-            "pitch_targets": pitch_targets,
-            "energy_targets": energy_targets,
+            "LR_length_rounded": ts.LR_length_rounded,
+            "log_duration_predictions": ts.log_duration_predictions,
+            "pitch_predictions": ts.pitch_predictions,
+            "energy_predictions": ts.energy_predictions,
+            "duration_targets": ts.duration_targets,
+            "pitch_targets": ts.pitch_targets,
+            "energy_targets": ts.energy_targets,
             "fp_predictions": None,
-            "valid_inter_lengths": inter_lengths,
+            "valid_inter_lengths": ts.inter_lengths,
         }
-        if bw_dev is not None and bw_dev.numel() == batch_size and mel_targets is None:
+        if ts.bw_dev is not None and ts.bw_dev.numel() == ts.batch_size and mel_targets is None:
             # batched inference: every sequence keeps the band width its own utterance would have had (an extra key; the
             # reference infers one utterance at a time, where x_band_width is this value)
-            res["band_width_per_sequence"] = bw_dev
-        res["LR_text_outputs"] = LR_text_outputs
-        res["LR_emo_outputs"] = LR_emo_outputs
-        res["LR_spk_outputs"] = LR_spk_outputs
-        res["ling_embedding"] = ling_embedding
-        if self.MAS and is_training:
-            res["attn_soft"] = attn_soft
-            res["attn_hard"] = attn_hard
-            res["attn_logprob"] = attn_logprob
+            res["band_width_per_sequence"] = ts.bw_dev
+        res["LR_text_outputs"] = ts.LR_text_outputs
+        res["LR_emo_outputs"] = ts.LR_emo_outputs
+        res["LR_spk_outputs"] = ts.LR_spk_outputs
+        res["ling_embedding"] = ts.ling_embedding
+        if self.MAS and ts.is_training:
+            res["attn_soft"] = ts.attn_soft
+            res["attn_hard"] = ts.attn_hard
+            res["attn_logprob"] = ts.attn_logprob
         return res
 
 
