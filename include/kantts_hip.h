@@ -1264,6 +1264,43 @@ typedef struct {
 } kantts_sconv_args;
 int kantts_sconv_launch(const kantts_sconv_args* args, void* stream);
 
+/* ---- The same layer with a PER-SLOT ROW COUNT: the slots of a call advance independently (continuous batching of a
+ * chunked vocoder: utterances of different lengths, a paused slot, a slot that takes the next request).
+ *   rows (S) int32, DEVICE memory (read by the kernel: a captured launch stays valid while the counts change), in units of
+ *   the frame rate of the step; row_mul: rows of THIS layer per frame (1 for the first layer, the running product of the
+ *   upsampling scales behind each stage).  Slot s has
+ *     n_s = clamp(rows[s], 0, Tc / row_mul) * row_mul          (clamped from both sides)
+ *   live rows.  Token rule:
+ *   out[s, q, n]      for q <  n_s: the rule of kantts_sconv_launch, same arithmetic and summation order (the tiles are
+ *                     chosen from Tc, as there), with X[s, t] read for t < n_s only
+ *   out[s, q, n]      for q >= n_s: not written; written as 0.0f when zero_tail != 0
+ *   hist_out[s, h, c] = X[s, n_s - H + h, c]   for h in [0, H)   (the last H rows of [hist_in[s] ; in[s, 0:n_s]], also when
+ *                     n_s < H; n_s == 0: a copy of hist_in[s] -- the caller flips its ping-pong halves for every slot)
+ * No row >= n_s of in or res is loaded: such rows may hold NaN or uninitialised memory.
+ * The fields before `rows` are those of kantts_sconv_args, in the same order; shape contract and alignment rules as there.
+ * zero_tail is supported for N == 1 only (KANTTS_E_UNSUPPORTED otherwise).
+ * KANTTS_E_BADARG: rows == NULL, row_mul < 1, Tc % row_mul != 0. */
+typedef struct {
+  const float* in;
+  const float* hist_in;
+  float* hist_out;
+  const void* w;
+  const float* bias;
+  const float* res;
+  float* out;
+  long long hist_ss;
+  int S, Tc, Cin, N, K, step;
+  float in_slope;
+  int in_act;
+  float out_slope;
+  int out_act;
+  int precision;
+  const int32_t* rows;
+  int row_mul;
+  int zero_tail;
+} kantts_sconv_rows_args;
+int kantts_sconv_rows_launch(const kantts_sconv_rows_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

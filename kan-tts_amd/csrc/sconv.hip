@@ -22,6 +22,15 @@
 // slot s to hist_out (a different buffer: nobody reads what they write).  The state therefore travels in the SAME launch
 // as the convolution: carrying it costs a chunk step no launch of its own.
 //
+// Per-slot row counts (kantts_sconv_rows_launch; the ROWS = true instantiations).  Slot s advances by
+//   n_s = clamp(rows[s], 0, Tc / row_mul) * row_mul
+// rows instead of Tc (rows: device memory, so that a captured launch stays valid while the counts change).  The grid is
+// still sized by Tc.  A compute workgroup reads rows[s] once (a uniform load), returns before its first load and its
+// first barrier when its tile starts at or after n_s, and bounds a partly live tile by n_s where the plain kernel bounds
+// it by Tc: no row >= n_s of in / res is loaded, no row >= n_s of out is written.  The state workgroup copies the last
+// H rows of [hist_in ; in[0:n_s]] -- for n_s == 0 that is hist_in itself.  The ROWS = false instantiations are the
+// kernels of kantts_sconv_launch, instruction for instruction.
+//
 // Reference: CausalConv1d / CausalConvTranspose1d, kantts/models/hifigan/layers.py:52-165 (their left zero pad is the
 // zero state of a fresh slot).
 #include "common.h"
@@ -42,15 +51,24 @@ __device__ __forceinline__ const float* sc_row(const kantts_sconv_args& g, int s
                : g.in + ((long long)s * g.Tc + t) * g.Cin;
 }
 
-// hist_out[s] = the last H rows of [hist_in[s] ; in[s]] -- one workgroup per slot, a plain float4 copy
-__device__ __forceinline__ void sc_copy_state(const kantts_sconv_args& g, int s) {
+// live rows of slot s: the count is clamped from BOTH sides (cap = Tc / row_mul, computed by the host)
+__device__ __forceinline__ int sc_live(const int32_t* rowsp, int s, int cap, int row_mul) {
+  return min(max(rowsp[s], 0), cap) * row_mul;
+}
+
+// hist_out[s] = the last H rows of [hist_in[s] ; in[s, 0:n]], n = Tc or (ROWS) the slot's live rows -- one workgroup per
+// slot, a plain float4 copy
+template <bool ROWS>
+__device__ __forceinline__ void sc_copy_state(const kantts_sconv_args& g, int s, const int32_t* rowsp, int cap, int row_mul) {
+  int n = 0;
+  if constexpr (ROWS) n = sc_live(rowsp, s, cap, row_mul);
   const int H = (g.K - 1) * g.step;
   const int c4n = g.Cin >> 2;
   float* dst = g.hist_out + (long long)s * g.hist_ss;
   for (int i = threadIdx.x; i < H * c4n; i += SC_THREADS) {
     const int h = i / c4n, c = (i - h * c4n) * 4;
     *reinterpret_cast<float4*>(dst + (long long)h * g.Cin + c) =
-        *reinterpret_cast<const float4*>(sc_row(g, s, g.Tc - H + h, H) + c);
+        *reinterpret_cast<const float4*>(sc_row(g, s, (ROWS ? n : g.Tc) - H + h, H) + c);
   }
 }
 
@@ -65,8 +83,9 @@ struct sc_bfrag<false> {
   float4 lo, hi;
 };
 
-template <bool BF16, int WM, int MREP, int NFR>
-__global__ __launch_bounds__(SC_THREADS) void sconv_kernel(const kantts_sconv_args g, const int ntm, const int ntn) {
+template <bool BF16, int WM, int MREP, int NFR, bool ROWS>
+__global__ __launch_bounds__(SC_THREADS) void sconv_kernel(const kantts_sconv_args g, const int ntm, const int ntn,
+                                                           const int32_t* rowsp, const int row_cap, const int row_mul) {
   constexpr int WN = 4 / WM;
   constexpr int BQ = WM * MREP * 16;
   constexpr int BN = WN * NFR * 16;
@@ -77,7 +96,7 @@ __global__ __launch_bounds__(SC_THREADS) void sconv_kernel(const kantts_sconv_ar
 
   int bid = blockIdx.x;
   if (bid < g.S) {
-    if (g.K > 1) sc_copy_state(g, bid);
+    if (g.K > 1) sc_copy_state<ROWS>(g, bid, rowsp, row_cap, row_mul);
     return;
   }
   bid -= g.S;
@@ -88,7 +107,12 @@ __global__ __launch_bounds__(SC_THREADS) void sconv_kernel(const kantts_sconv_ar
   const int wm = wave % WM, wn = wave / WM;
   const int H = (g.K - 1) * g.step;
   const int q0 = tm * BQ;
-  const int rows = min(BQ, g.Tc - q0);  // live output rows of this tile (>= 1)
+  int nlive = g.Tc;  // rows of this slot that exist in this call
+  if constexpr (ROWS) {
+    nlive = sc_live(rowsp, s, row_cap, row_mul);  // one uniform load per workgroup
+    if (q0 >= nlive) return;                      // a dead tile: workgroup-uniform, before any load and any barrier
+  }
+  const int rows = min(BQ, nlive - q0);  // live output rows of this tile (>= 1)
   const int W = rows + H;               // window rows
   const int ncol0 = tn * BN + wn * (NFR * 16);
   const bool wave_live = ncol0 < g.N && wm * (MREP * 16) < rows;  // wave-uniform
@@ -246,16 +270,25 @@ __global__ __launch_bounds__(SC_THREADS) void sconv_kernel(const kantts_sconv_ar
 }
 
 // N == 1 (conv_post): one thread per output row, a K x Cin fp32 dot product over rows its neighbours share through L1.
-__global__ __launch_bounds__(SC_THREADS) void sconv_n1_kernel(const kantts_sconv_args g) {
+// ROWS: a dead row (q >= n_s) loads nothing; it is left alone, or written as 0 with zero_tail.
+template <bool ROWS>
+__global__ __launch_bounds__(SC_THREADS) void sconv_n1_kernel(const kantts_sconv_args g, const int32_t* rowsp,
+                                                              const int row_cap, const int row_mul, const int zero_tail) {
   int bid = blockIdx.x;
   if (bid < g.S) {
-    if (g.K > 1) sc_copy_state(g, bid);
+    if (g.K > 1) sc_copy_state<ROWS>(g, bid, rowsp, row_cap, row_mul);
     return;
   }
   bid -= g.S;
   const long long e = (long long)bid * SC_THREADS + threadIdx.x;
   if (e >= (long long)g.S * g.Tc) return;
   const int s = (int)(e / g.Tc), q = (int)(e - (long long)s * g.Tc);
+  if constexpr (ROWS) {
+    if (q >= sc_live(rowsp, s, row_cap, row_mul)) {
+      if (zero_tail) g.out[e] = 0.f;
+      return;
+    }
+  }
   const int H = (g.K - 1) * g.step;
   const float* w = reinterpret_cast<const float*>(g.w);
   float acc = 0.f;
@@ -276,8 +309,14 @@ __global__ __launch_bounds__(SC_THREADS) void sconv_n1_kernel(const kantts_sconv
   g.out[e] = acc;
 }
 
-template <bool BF16, int WM, int MREP, int NFR>
-static int sc_launch(const kantts_sconv_args& g, hipStream_t st) {
+// the per-slot counts of kantts_sconv_rows_launch as the kernels take them (all unused by the ROWS = false instantiations)
+struct sc_rows {
+  const int32_t* p;
+  int cap, mul, zero_tail;
+};
+
+template <bool BF16, int WM, int MREP, int NFR, bool ROWS>
+static int sc_launch(const kantts_sconv_args& g, const sc_rows& r, hipStream_t st) {
   constexpr int BQ = WM * MREP * 16;
   constexpr int BN = (4 / WM) * NFR * 16;
   constexpr int LDW = BF16 ? 128 + 8 : 64 + 4;
@@ -286,7 +325,8 @@ static int sc_launch(const kantts_sconv_args& g, hipStream_t st) {
   const long long blocks = (long long)g.S * ntm * ntn + g.S;
   if (blocks > 0x7fffffffLL) return KANTTS_E_UNSUPPORTED;
   const size_t lds = (size_t)(BQ + H) * LDW * (BF16 ? 2 : 4);  // <= (128 + 70) * 272 B = 52.6 KB
-  hipLaunchKernelGGL((sconv_kernel<BF16, WM, MREP, NFR>), dim3((unsigned)blocks), dim3(SC_THREADS), lds, st, g, ntm, ntn);
+  hipLaunchKernelGGL((sconv_kernel<BF16, WM, MREP, NFR, ROWS>), dim3((unsigned)blocks), dim3(SC_THREADS), lds, st, g, ntm, ntn,
+                     r.p, r.cap, r.mul);
   KANTTS_CHECK_LAUNCH();
 }
 
@@ -295,26 +335,29 @@ static int sc_launch(const kantts_sconv_args& g, hipStream_t st) {
 // chunk-sized problem is bound by the latency of streaming its weights (K * N * Cin elements that no cache level holds
 // across the 78 layers of a step), so the narrowest tile is taken until the grid has a workgroup or two per CU -- every
 // workgroup then streams a 1/ntn slice of the weights with 16 (bf16) iterations of fragments in flight per wave.
-template <bool BF16, int WM, int MREP>
-static int sc_pick_n(const kantts_sconv_args& g, hipStream_t st) {
+// With per-slot counts the choice is still made from Tc (the counts are not known on the host): the same tiles, and
+// therefore the same bits, as the plain launch of the same Tc.
+template <bool BF16, int WM, int MREP, bool ROWS>
+static int sc_pick_n(const kantts_sconv_args& g, const sc_rows& r, hipStream_t st) {
   constexpr int BQ = WM * MREP * 16, WN = 4 / WM;
   const long long mt = (long long)g.S * kantts_cdiv(g.Tc, BQ);
   auto blocks = [&](int nfr) { return mt * kantts_cdiv(g.N, WN * nfr * 16); };
-  if (g.N > WN * 32 && blocks(4) >= 384) return sc_launch<BF16, WM, MREP, 4>(g, st);
-  if (g.N > WN * 16 && blocks(2) >= 384) return sc_launch<BF16, WM, MREP, 2>(g, st);
-  return sc_launch<BF16, WM, MREP, 1>(g, st);
+  if (g.N > WN * 32 && blocks(4) >= 384) return sc_launch<BF16, WM, MREP, 4, ROWS>(g, r, st);
+  if (g.N > WN * 16 && blocks(2) >= 384) return sc_launch<BF16, WM, MREP, 2, ROWS>(g, r, st);
+  return sc_launch<BF16, WM, MREP, 1, ROWS>(g, r, st);
 }
 
-template <bool BF16>
-static int sc_dispatch(const kantts_sconv_args& g, hipStream_t st) {
-  if (g.Tc <= 16) return sc_pick_n<BF16, 1, 1>(g, st);
-  if (g.Tc <= 64) return sc_pick_n<BF16, 4, 1>(g, st);
-  return sc_pick_n<BF16, 4, 2>(g, st);
+template <bool BF16, bool ROWS>
+static int sc_dispatch(const kantts_sconv_args& g, const sc_rows& r, hipStream_t st) {
+  if (g.Tc <= 16) return sc_pick_n<BF16, 1, 1, ROWS>(g, r, st);
+  if (g.Tc <= 64) return sc_pick_n<BF16, 4, 1, ROWS>(g, r, st);
+  return sc_pick_n<BF16, 4, 2, ROWS>(g, r, st);
 }
 
-extern "C" int kantts_sconv_launch(const kantts_sconv_args* a, void* stream) {
-  if (!a || !a->in || !a->w || !a->out) return KANTTS_E_BADARG;
-  kantts_sconv_args g = *a;
+// argument checks, clamping and launch of both entry points
+template <bool ROWS>
+static int sc_run(kantts_sconv_args g, const sc_rows& r, void* stream) {
+  if (!g.in || !g.w || !g.out) return KANTTS_E_BADARG;
   if (g.K < 1 || g.step < 1 || g.Cin < 1 || g.N < 1 || (g.precision != 0 && g.precision != 1)) return KANTTS_E_BADARG;
   if (g.K > 1 && (!g.hist_in || !g.hist_out || g.hist_in == g.hist_out)) return KANTTS_E_BADARG;
   if (g.K > SC_MAXK || g.step > SC_MAXSTEP || (g.Cin & 7) || g.Cin < 16 || g.Cin > 512 ||
@@ -331,8 +374,28 @@ extern "C" int kantts_sconv_launch(const kantts_sconv_args* a, void* stream) {
   if (g.N == 1) {
     const long long blocks = ((long long)g.S * g.Tc + SC_THREADS - 1) / SC_THREADS + g.S;
     if (blocks > 0x7fffffffLL) return KANTTS_E_UNSUPPORTED;
-    hipLaunchKernelGGL(sconv_n1_kernel, dim3((unsigned)blocks), dim3(SC_THREADS), 0, st, g);
+    hipLaunchKernelGGL(sconv_n1_kernel<ROWS>, dim3((unsigned)blocks), dim3(SC_THREADS), 0, st, g, r.p, r.cap, r.mul,
+                       r.zero_tail);
     KANTTS_CHECK_LAUNCH();
   }
-  return g.precision == 1 ? sc_dispatch<true>(g, st) : sc_dispatch<false>(g, st);
+  return g.precision == 1 ? sc_dispatch<true, ROWS>(g, r, st) : sc_dispatch<false, ROWS>(g, r, st);
+}
+
+extern "C" int kantts_sconv_launch(const kantts_sconv_args* a, void* stream) {
+  if (!a) return KANTTS_E_BADARG;
+  return sc_run<false>(*a, sc_rows{nullptr, 0, 1, 0}, stream);
+}
+
+extern "C" int kantts_sconv_rows_launch(const kantts_sconv_rows_args* a, void* stream) {
+  if (!a || !a->rows || a->row_mul < 1) return KANTTS_E_BADARG;
+  kantts_sconv_args g;
+  g.in = a->in, g.hist_in = a->hist_in, g.hist_out = a->hist_out, g.w = a->w, g.bias = a->bias, g.res = a->res;
+  g.out = a->out, g.hist_ss = a->hist_ss;
+  g.S = a->S, g.Tc = a->Tc, g.Cin = a->Cin, g.N = a->N, g.K = a->K, g.step = a->step;
+  g.in_slope = a->in_slope, g.in_act = a->in_act, g.out_slope = a->out_slope, g.out_act = a->out_act;
+  g.precision = a->precision;
+  const int Tc = g.Tc > 0 ? g.Tc : 0;
+  if (Tc % a->row_mul != 0) return KANTTS_E_BADARG;
+  if (a->zero_tail && g.N != 1) return KANTTS_E_UNSUPPORTED;  // the zero tail exists in the N == 1 kernel only
+  return sc_run<true>(g, sc_rows{a->rows, Tc / a->row_mul, a->row_mul, a->zero_tail != 0}, stream);
 }

@@ -110,6 +110,11 @@ class SConvArgs(Structure):
     ]
 
 
+class SConvRowsArgs(Structure):
+    """kantts_sconv_rows_args (include/kantts_hip.h): the fields of kantts_sconv_args, then the per-slot row counts."""
+    _fields_ = SConvArgs._fields_ + [("rows", c_void_p), ("row_mul", c_int32), ("zero_tail", c_int32)]
+
+
 class CConvArgs(Structure):
     """kantts_cconv_args (include/kantts_hip.h); ``in_`` is the C field ``in``."""
     _fields_ = [
@@ -447,6 +452,7 @@ def lib():
         L.kantts_scale_to_many.argtypes = [p, f, POINTER(c_void_p), i, ll, p]
         L.kantts_ragged_rows_i64.argtypes = [p, p, p, p, p, p, i, i, i, i, p]
         L.kantts_sconv_launch.argtypes = [POINTER(SConvArgs), c_void_p]
+        L.kantts_sconv_rows_launch.argtypes = [POINTER(SConvRowsArgs), c_void_p]
         L.kantts_pnca_decode_range.argtypes = [POINTER(DecodeArgs), c_int, c_int, c_void_p]
         L.kantts_lstm_fwd_range.argtypes = [p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, p]
         L.kantts_fsmn_dwconv_fwd_rows.argtypes = [p, p, p, p, p, i, i, i, i, i, i, i, p]
@@ -473,7 +479,7 @@ EXPORTED_SYMBOLS = [
     "kantts_pnca_block_fwd", "kantts_pnca_block_bwd", "kantts_pnca_block_bwd_ws_floats", "kantts_rows_sum_many",
     "kantts_melspec_tuning", "kantts_teacher_plan", "kantts_copy_roof", "kantts_pnca_attn_qkv_bwd",
     "kantts_pnca_decode_run", "kantts_pnca_decode_blob_sizes", "kantts_dur_ar_run", "kantts_dur_ar_run_f32", "kantts_ctc_attn", "kantts_ctc_attn_workspace", "kantts_enc_attn_fwd",
-    "kantts_launch_tuning", "kantts_sconv_launch",
+    "kantts_launch_tuning", "kantts_sconv_launch", "kantts_sconv_rows_launch",
     "kantts_pnca_decode_range", "kantts_lstm_fwd_range", "kantts_fsmn_dwconv_fwd_rows",
 ]
 
@@ -1278,12 +1284,16 @@ E_UNSUPPORTED = -2
 
 
 def sconv(x, hist_in, hist_out, w, out, *, S, Tc, Cin, N, K, step, hist_ss, precision, bias=None, res=None, in_leaky=None,
-          out_leaky=None):
+          out_leaky=None, rows=None, row_mul=1, zero_tail=False):
     """Causal stride-1 dilated convolution with carried history (csrc/sconv.hip, kantts_sconv_launch; the token rule is
     written out in include/kantts_hip.h).  x (S, Tc, Cin) fp32; hist_in / hist_out: fp32 tensors whose first element is
     slot 0's state of this layer, ``hist_ss`` floats between slots; w (K, N, Cin), bf16 when precision == PREC_BF16 and
-    N > 1, else fp32; out / res (S, Tc, N) fp32.  Returns False when the kernel declines the shape."""
-    g = SConvArgs()
+    N > 1, else fp32; out / res (S, Tc, N) fp32.  Returns False when the kernel declines the shape.
+
+    ``rows``: an int32 device tensor of S per-slot counts -- kantts_sconv_rows_launch: slot s advances by
+    n_s = clamp(rows[s], 0, Tc / row_mul) * row_mul rows only (0: its state is carried over unchanged); rows >= n_s of
+    ``out`` are left alone, or zeroed with ``zero_tail`` (N == 1 only).  ``rows=None`` is the plain entry point."""
+    g = SConvArgs() if rows is None else SConvRowsArgs()
     g.in_, g.hist_in, g.hist_out = ptr(x, torch.float32), ptr(hist_in, torch.float32), ptr(hist_out, torch.float32)
     g.w = ptr(w, torch.bfloat16 if (precision == PREC_BF16 and N > 1) else torch.float32)
     g.bias, g.res, g.out = ptr(bias, torch.float32), ptr(res, torch.float32), ptr(out, torch.float32)
@@ -1292,7 +1302,13 @@ def sconv(x, hist_in, hist_out, w, out, *, S, Tc, Cin, N, K, step, hist_ss, prec
     g.in_slope, g.in_act = float(in_leaky or 0.0), int(in_leaky is not None)
     g.out_slope, g.out_act = float(out_leaky or 0.0), int(out_leaky is not None)
     g.precision = int(precision)
-    rc = lib().kantts_sconv_launch(ctypes.byref(g), stream())
+    if rows is None:
+        rc = lib().kantts_sconv_launch(ctypes.byref(g), stream())
+    else:
+        if rows.numel() != int(S):
+            raise ValueError("rows must hold S = %d counts, got %d" % (int(S), rows.numel()))
+        g.rows, g.row_mul, g.zero_tail = ptr(rows, torch.int32), int(row_mul), int(bool(zero_tail))
+        rc = lib().kantts_sconv_rows_launch(ctypes.byref(g), stream())
     if rc == E_UNSUPPORTED:
         return False
     check(rc, "sconv")

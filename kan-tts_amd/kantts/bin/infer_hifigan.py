@@ -8,7 +8,8 @@ the reference (:52-63, :112-113); multi-band (PQMF) generators are refused.
 
 ``--chunk_frames N``: the same outputs produced chunk by chunk through kantts.models.hifigan.chunked.ChunkedVocoder
 (carried convolution state; causal single-band generators without NSF), with the time to the first chunk logged beside
-the RTF.  Absent: the whole-utterance path, unchanged.
+the RTF.  Absent: the whole-utterance path, unchanged.  ``--slots S`` (with ``--chunk_frames``): S utterances at a time,
+each slot taking the next file as soon as its utterance ends (``ChunkedVocoder.play_many``); the same files are written.
 """
 import argparse
 import glob
@@ -65,7 +66,47 @@ def _device():
     return torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
 
 
-def hifigan_infer(input_mel, ckpt_path, output_dir, config=None, chunk_frames=None):
+def _write_wav(output_dir, utt_id, sr, y):
+    wavfile.write(os.path.join(output_dir, "%s_gen.wav" % utt_id), sr, (np.clip(y, -1.0, 1.0) * 32767.0).astype(np.int16))
+
+
+def _load_feats(model, path, device):
+    feats = np.load(path)
+    if model.nsf_enable:
+        feats = binarize(feats)
+    return torch.from_numpy(np.ascontiguousarray(feats)).float().to(device)
+
+
+def _infer_many(model, mel_lst, output_dir, sr, chunk_frames, slots, device):
+    """The directory through ``slots`` vocoder slots with continuous batching; an utterance's file is written when its last
+    chunk has arrived."""
+    from kantts.models.hifigan.chunked import ChunkedVocoder
+
+    vocoder = ChunkedVocoder(model, slots=slots, graph=device.type == "cuda")  # refuses what it cannot play, loudly
+    pcm_len = 0
+    with torch.no_grad():
+        start = time.time()
+        mels = [_load_feats(model, mel, device).transpose(1, 0) for mel in mel_lst]
+        parts, got = {}, {}
+        for i, wav in vocoder.play_many(mels, chunk_frames=chunk_frames):
+            parts.setdefault(i, []).append(wav.reshape(-1).cpu())
+            got[i] = got.get(i, 0) + wav.shape[-1] // vocoder.hop
+            if got[i] >= mels[i].shape[1]:
+                y = torch.cat(parts.pop(i)).numpy()
+                pcm_len += len(y)
+                _write_wav(output_dir, os.path.splitext(os.path.basename(mel_lst[i]))[0], sr, y)
+        rtf = (time.time() - start) / max(pcm_len / sr, 1e-9)
+    logging.info("Finished chunked generation of %d utterances on %d slots (%d frames per chunk, RTF = %.03f).",
+                 len(mel_lst), slots, chunk_frames, rtf)
+    return rtf
+
+
+def hifigan_infer(input_mel, ckpt_path, output_dir, config=None, chunk_frames=None, slots=1):
+    slots = int(slots)
+    if slots < 1:
+        raise ValueError("slots must be >= 1")
+    if slots > 1 and chunk_frames is None:
+        raise ValueError("slots > 1 needs chunk_frames (the slots belong to the chunked vocoder)")
     device = _device()
     config = _load_config(ckpt_path, config)
     os.makedirs(output_dir, exist_ok=True)
@@ -80,6 +121,8 @@ def hifigan_infer(input_mel, ckpt_path, output_dir, config=None, chunk_frames=No
     model.remove_weight_norm()
     model = model.eval().to(device)
     sr = config["audio_config"]["sampling_rate"]
+    if slots > 1:
+        return _infer_many(model, mel_lst, output_dir, sr, chunk_frames, slots, device)
     pcm_len = 0
     vocoder, first_chunk = None, []
     if chunk_frames is not None:
@@ -119,7 +162,7 @@ def hifigan_infer(input_mel, ckpt_path, output_dir, config=None, chunk_frames=No
     return rtf
 
 
-if __name__ == "__main__":
+def main(argv=None):
     parser = argparse.ArgumentParser(description="Infer hifigan model")
     parser.add_argument("--ckpt", type=str, required=True, help="Path to model checkpoint")
     parser.add_argument("--input_mel", type=str, required=True,
@@ -128,5 +171,14 @@ if __name__ == "__main__":
     parser.add_argument("--config", type=str, default=None, help="Path to config file")
     parser.add_argument("--chunk_frames", type=int, default=None,
                         help="Generate chunk by chunk, this many mel frames at a time (carried convolution state)")
-    args = parser.parse_args()
-    hifigan_infer(args.input_mel, args.ckpt, args.output_dir, args.config, chunk_frames=args.chunk_frames)
+    parser.add_argument("--slots", type=int, default=1,
+                        help="With --chunk_frames: play this many utterances at a time (continuous batching)")
+    args = parser.parse_args(argv)
+    if args.slots < 1 or (args.slots > 1 and args.chunk_frames is None):
+        parser.error("--slots needs --chunk_frames and a value >= 1")
+    return hifigan_infer(args.input_mel, args.ckpt, args.output_dir, args.config, chunk_frames=args.chunk_frames,
+                         slots=args.slots)
+
+
+if __name__ == "__main__":
+    main()

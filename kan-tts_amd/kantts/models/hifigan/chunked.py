@@ -11,10 +11,19 @@ fp32 summation order.  A zero state is exactly the reference's zero left-pad, so
     v.reset(slot=None)           # one slot or all: the next step starts from zero state
     for wav in v.synthesize(mel_full, chunk_frames=8, slot=0): ...
 
+The slots need not move in lockstep: ``step(mel, rows=counts)`` advances slot ``s`` by ``counts[s]`` frames only (0 holds
+its state bit for bit; frames of ``mel`` past a slot's count are never read), through the per-slot row counts of
+kantts_sconv_rows_launch.  ``play_many`` builds continuous batching on it:
+
+    wav = v.step(mel, rows=[8, 3, 0, 8])                  # samples at and after rows[s] * hop of slot s are 0.0
+    for index, wav in v.play_many(mels, chunk_frames=8): ...   # utterances of any lengths through all slots
+
 History rows per layer (at that layer's token rate): ``(k - 1) * dilation`` for a convolution, ``J - 1`` input tokens
 for an upsampling stage (J polyphase taps: the transposed convolution alone has kernel / stride, the fused dual-path
 stage of ``Generator._dual_path_weight`` max(kernel / stride, 1 + ceil(6 / stride))).
 """
+import operator
+
 import torch
 
 import kantts._hip as hip
@@ -42,7 +51,7 @@ class _Layer:
 
 class ChunkedVocoder:
     """Chunk-by-chunk inference of a causal single-band ``Generator`` on ``slots`` independent utterances that advance
-    together by ``Tc`` frames per ``step``.
+    by ``Tc`` frames per ``step`` -- together, or each by its own count of at most ``Tc`` (``step(mel, rows=...)``).
 
     The object is a SNAPSHOT of the generator: the effective (weight-normed, dual-path-fused) weights are computed and
     packed once, here; build a new ``ChunkedVocoder`` after the generator's weights change.  The contraction mode is
@@ -54,7 +63,9 @@ class ChunkedVocoder:
 
     ``graph=True``: a step is captured per distinct ``Tc`` -- one ``torch.cuda.CUDAGraph`` for each parity, on one stream
     with no parallel branches -- and replayed; ``mel`` is copied into a static buffer.  ``graph=False`` issues the same
-    launches eagerly and gives identical bits.
+    launches eagerly and gives identical bits.  The ``rows`` form of a step has graphs of its own (also per ``Tc``): the
+    counts live in one int32 device buffer that the captured launches read, so they change between replays without a
+    new capture (``captures`` counts the captures of the object).
 
     Refused at construction: non-causal generators, NSF generators (the excitation's running phase and random draws need
     a carried state of their own), ``out_channels > 1`` (PQMF synthesis), and channel counts / kernel sizes the kernel
@@ -173,9 +184,11 @@ class ChunkedVocoder:
                         pack_conv(l2, c2)
             pack_conv(self.post, g.conv_post)
         self.arena = torch.zeros(2, self.slots, max(self.state_floats, 4), device=self.device, dtype=torch.float32)
+        self._rows = torch.zeros(self.slots, device=self.device, dtype=torch.int32)  # per-slot counts of step(rows=...)
         self._parity = 0
         self._graphs = {}
         self._max_graphs = int(max_graphs)
+        self.captures = 0
 
     # ------------------------------------------------------------------------------------------------------------
     def reset(self, slot=None):
@@ -187,7 +200,7 @@ class ChunkedVocoder:
                 raise IndexError("slot %r of %d" % (slot, self.slots))
             self.arena[:, int(slot)].zero_()
 
-    def _conv(self, L, x, parity, res=None):
+    def _conv(self, L, x, parity, res=None, rows=None, row_mul=1, zero_tail=False):
         S, T, _ = x.shape
         out = torch.empty((S, T, L.N), device=x.device, dtype=torch.float32)
         hin = hout = None
@@ -195,31 +208,38 @@ class ChunkedVocoder:
             hin = self.arena[parity, 0, L.off:L.off + L.H * L.Cin]
             hout = self.arena[1 - parity, 0, L.off:L.off + L.H * L.Cin]
         ok = hip.sconv(x, hin, hout, L.w, out, S=S, Tc=T, Cin=L.Cin, N=L.N, K=L.K, step=L.step,
-                       hist_ss=self.arena.shape[2], precision=self.precision, bias=L.bias, res=res, in_leaky=L.in_leaky)
+                       hist_ss=self.arena.shape[2], precision=self.precision, bias=L.bias, res=res, in_leaky=L.in_leaky,
+                       **({} if rows is None else dict(rows=rows, row_mul=row_mul, zero_tail=zero_tail)))
         if not ok:
             raise RuntimeError("kantts_sconv_launch declined layer %s it was planned for" % L.name)
         return out
 
-    def _run(self, mel, parity):
+    def _run(self, mel, parity, rows=None):
         """The launches of one step: mel (S, C, Tc) fp32 -> wav (S, 1, Tc * hop).  Reads arena[parity], writes
-        arena[1 - parity]."""
+        arena[1 - parity].  ``rows``: the int32 device buffer of per-slot frame counts (every layer passes its own rows
+        per frame; the element-wise launches run over the whole buffers -- what they do to dead rows is never read)."""
         with torch.no_grad():
-            h = self._conv(self.pre, mel.transpose(1, 2).contiguous(), parity)
+            mul = 1  # rows of the current layer per mel frame
+            h = self._conv(self.pre, mel.transpose(1, 2).contiguous(), parity, rows=rows, row_mul=mul)
             for s, Cout, upl, stacks in self.stages:
                 h = ops.sin_add(h)
-                h = self._conv(upl, h, parity).view(h.shape[0], h.shape[1] * s, Cout)
+                h = self._conv(upl, h, parity, rows=rows, row_mul=mul).view(h.shape[0], h.shape[1] * s, Cout)
+                mul *= s
                 ys = []
                 for pairs in stacks:  # sequential, as Generator._residual_stacks runs them under no_grad
                     x = h
                     for c1, c2 in pairs:
-                        x = self._conv(c2, self._conv(c1, x, parity), parity, res=x)
+                        x = self._conv(c2, self._conv(c1, x, parity, rows=rows, row_mul=mul), parity, res=x, rows=rows,
+                                       row_mul=mul)
                     ys.append(x)
                 h = ops.mean_many(ys) if len(ys) > 1 else ys[0]
-            h = self._conv(self.post, h, parity)
+            h = self._conv(self.post, h, parity, rows=rows, row_mul=mul, zero_tail=True)  # tanh(0) == 0: a silent tail
             return torch.tanh(h).transpose(1, 2)
 
-    def _captured(self, Tc):
-        ent = self._graphs.pop(Tc, None)
+    def _captured(self, Tc, with_rows=False):
+        key = ("rows", Tc) if with_rows else Tc
+        rows = self._rows if with_rows else None
+        ent = self._graphs.pop(key, None)
         if ent is None:
             if len(self._graphs) >= self._max_graphs:
                 self._graphs.pop(next(iter(self._graphs)))  # least recently used
@@ -231,32 +251,63 @@ class ChunkedVocoder:
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 for p in (0, 1):
-                    self._run(mel, p)
+                    self._run(mel, p, rows)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             graphs, outs = [], []
             for p in (0, 1):
                 gr = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-                    outs.append(self._run(mel, p))
+                    outs.append(self._run(mel, p, rows))
                 graphs.append(gr)
             self.arena.copy_(saved)
+            self.captures += 1
             ent = (mel, graphs, outs)
-        self._graphs[Tc] = ent
+        self._graphs[key] = ent
         return ent
 
-    def step(self, mel):
-        """mel (slots, C_mel, Tc), Tc >= 1 -> wav (slots, 1, Tc * prod(upsample_scales)); advances every slot by Tc."""
+    def _set_rows(self, rows, Tc):
+        """Validate per-slot counts and copy them into the persistent device buffer the launches read."""
+        if torch.is_tensor(rows):
+            if rows.dtype.is_floating_point or rows.dtype.is_complex or rows.dtype == torch.bool:
+                raise ValueError("rows must be integers, got dtype %s" % rows.dtype)
+            if tuple(rows.shape) != (self.slots,):
+                raise ValueError("rows must have shape (%d,), got %s" % (self.slots, tuple(rows.shape)))
+            if rows.device.type == "cpu":
+                rows = rows.tolist()
+            else:  # not read back: the kernel clamps what it finds
+                self._rows.copy_(rows)
+                return
+        try:
+            vals = [operator.index(r) for r in rows]
+        except TypeError:
+            raise ValueError("rows must be a sequence of %d ints or an integer tensor" % self.slots) from None
+        if len(vals) != self.slots:
+            raise ValueError("rows must hold one count per slot (%d), got %d" % (self.slots, len(vals)))
+        if any(r < 0 or r > Tc for r in vals):
+            raise ValueError("rows must lie in [0, Tc = %d], got %s" % (Tc, vals))
+        self._rows.copy_(torch.tensor(vals, dtype=torch.int32))
+
+    def step(self, mel, rows=None):
+        """mel (slots, C_mel, Tc), Tc >= 1 -> wav (slots, 1, Tc * prod(upsample_scales)); advances every slot by Tc.
+
+        ``rows``: ``slots`` ints in [0, Tc] (a sequence, or an integer tensor of shape (slots,) on the host or on the
+        device; device values are clamped by the kernel, not read back).  Slot ``s`` advances by ``rows[s]`` frames: frames
+        of ``mel`` at and after ``rows[s]`` are not read (they may hold anything), samples of ``wav`` at and after
+        ``rows[s] * hop`` are 0.0, and a slot with ``rows[s] == 0`` keeps its state bit for bit."""
         if mel.dim() != 3 or mel.shape[0] != self.slots or mel.shape[1] != self.in_channels or mel.shape[2] < 1:
             raise ValueError("mel must be (slots=%d, %d, Tc >= 1), got %s" % (self.slots, self.in_channels, tuple(mel.shape)))
         Tc = int(mel.shape[2])
+        if rows is not None:
+            self._set_rows(rows, Tc)
         if self.graph:
-            buf, graphs, outs = self._captured(Tc)
+            buf, graphs, outs = self._captured(Tc, rows is not None)
             buf.copy_(mel)
             graphs[self._parity].replay()
             wav = outs[self._parity].clone()
         else:
-            wav = self._run(mel.to(device=self.device, dtype=torch.float32), self._parity)
+            wav = self._run(mel.to(device=self.device, dtype=torch.float32), self._parity,
+                            None if rows is None else self._rows)
         self._parity ^= 1
         return wav
 
@@ -276,3 +327,43 @@ class ChunkedVocoder:
             mel = torch.zeros(self.slots, self.in_channels, n, device=self.device, dtype=torch.float32)
             mel[slot, :, :t1 - t0] = mel_full[:, t0:t1]
             yield self.step(mel)[slot, :, :(t1 - t0) * self.hop]
+
+    def play_many(self, mels, chunk_frames=8):
+        """Continuous batching: a generator that plays the utterances ``mels`` -- a sequence of (C_mel, T_i) tensors,
+        T_i >= 1 -- through all slots, yielding ``(index, wav)`` with wav (1, n * hop) for the ``n`` frames utterance
+        ``index`` advanced by.  The schedule: ``reset()`` once; the slots take utterances in input order; every step has
+        room for ``chunk_frames`` frames per slot and slot ``s`` feeds min(chunk_frames, remaining) of its utterance (0
+        without one); after the step the live slots yield in slot order; a slot whose utterance has ended is
+        ``reset(slot)`` and takes the next unassigned utterance before the next step.  The concatenated chunks of an
+        utterance equal ``synthesize`` of it bit for bit."""
+        n = int(chunk_frames)
+        if n < 1:
+            raise ValueError("chunk_frames must be >= 1")
+        mels = list(mels)
+        for i, m in enumerate(mels):
+            if m.dim() != 2 or m.shape[0] != self.in_channels or m.shape[1] < 1:
+                raise ValueError("mels[%d] must be (%d, T >= 1), got %s" % (i, self.in_channels, tuple(m.shape)))
+        self.reset()
+        cur, pos, nxt = [None] * self.slots, [0] * self.slots, 0
+        buf = torch.zeros(self.slots, self.in_channels, n, device=self.device, dtype=torch.float32)
+        while True:
+            for s in range(self.slots):
+                if cur[s] is None and nxt < len(mels):
+                    cur[s], pos[s], nxt = nxt, 0, nxt + 1
+            if all(c is None for c in cur):
+                return
+            counts = [0] * self.slots
+            for s, c in enumerate(cur):
+                if c is not None:
+                    counts[s] = min(n, int(mels[c].shape[1]) - pos[s])
+                    buf[s, :, :counts[s]] = mels[c][:, pos[s]:pos[s] + counts[s]]
+            wav = self.step(buf, rows=counts)
+            for s, c in enumerate(cur):
+                if c is not None:
+                    yield c, wav[s, :, :counts[s] * self.hop]
+            for s, c in enumerate(cur):
+                if c is not None:
+                    pos[s] += counts[s]
+                    if pos[s] >= int(mels[c].shape[1]):
+                        self.reset(s)
+                        cur[s] = None

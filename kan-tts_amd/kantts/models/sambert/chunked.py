@@ -23,6 +23,11 @@ layer is position-wise or causal.  Shipped configuration: 4 layers x rp 3 = 12 f
     res = sess.result()                              # the dictionary forward() returns
 
 Sequences of a batch advance in lockstep, each with its own length and band width, as in batched one-shot inference.
+Rows past a sequence's own frame count are padding; ``sess.live_rows(lo, hi)`` says how many of the rows [lo, hi) each
+sequence really has, which is what a multi-slot vocoder takes as its per-slot counts:
+
+    wav = vocoder.step(mel.transpose(1, 2), rows=sess.live_rows(lo, hi))     # every slot stops at its own last frame
+
 Not here: graph capture of a step, independently advancing slots, an fp32-mode decoder range.
 """
 import torch
@@ -40,6 +45,12 @@ _NO_RANGE = ("the loaded C ABI has no range entry points (kantts_pnca_decode_ran
 def _check(rc, what):
     if rc != 0:
         raise RuntimeError("libkantts_hip: %s failed with code %d" % (what, rc))
+
+
+def live_rows(frames, lo, hi):
+    """How many of the rows [lo, hi) exist in sequences of ``frames`` frames each: int32 clamp(frames - lo, 0, hi - lo)
+    (pure; ``frames``: a tensor on any device, or a sequence of ints)."""
+    return (torch.as_tensor(frames) - int(lo)).clamp(0, max(int(hi) - int(lo), 0)).to(torch.int32)
 
 
 class ChunkedPostNet:
@@ -207,6 +218,10 @@ class _AcousticSession:
             self.t = t1
         lo, hi = self.post.advance(self.t * self.r)
         return lo, hi, self.post.y[:, lo:hi]
+
+    def live_rows(self, lo, hi):
+        """Per sequence, how many of the rows [lo, hi) of a chunk are frames of that sequence (int32, on the device)."""
+        return live_rows(self.frames, lo, hi)
 
     def stream(self, chunk_steps):
         while not self.finished:

@@ -3,6 +3,12 @@ the existing kernels): extracts the device code object of each (llvm-objdump --o
 the instruction streams kernel by kernel.
 
     python scripts/isa_diff.py /tmp/gemm_bf16.o.before kan-tts_amd/csrc/gemm_bf16.o
+
+Kernels are matched by symbol.  When the edit renamed them (a template parameter was added), give one or more
+``--rename REGEX REPLACEMENT``: the symbols of BOTH files are demangled, their parameter lists dropped, and every rename is
+applied to the names of the second file before matching:
+
+    python scripts/isa_diff.py /tmp/sconv.o.before kan-tts_amd/csrc/sconv.o --rename ', false>$' '>' --rename '<false>$' ''
 """
 import os
 import re
@@ -31,11 +37,27 @@ def kernels(obj):
             out[cur] = []
         elif cur is not None and "\t" in ln and ln.strip() != "...":  # "..." = padding between functions
             out[cur].append(ln.split("//")[0].strip())
+    for ins in out.values():  # s_nop behind the last s_endpgm: alignment padding up to the next function or the section's end
+        while len(ins) > 1 and ins[-1].split(":")[-1].split() == ["s_nop", "0"]:
+            ins.pop()
     return out
 
 
-def main(a_path, b_path):
+def demangled(ks, renames):
+    names = subprocess.run(["c++filt"], input="\n".join(ks), capture_output=True, text=True, check=True).stdout.splitlines()
+    out = {}
+    for k, n in zip(ks, names):
+        n = re.sub(r"^void ", "", re.sub(r"\(.*", "", n))
+        for pat, repl in renames:
+            n = re.sub(pat, repl, n)
+        out[n] = ks[k]
+    return out
+
+
+def main(a_path, b_path, renames=None):
     a, b = kernels(a_path), kernels(b_path)
+    if renames is not None:
+        a, b = demangled(a, []), demangled(b, renames)
     same = True
     for k in sorted(set(a) | set(b)):
         if k not in b:
@@ -52,4 +74,9 @@ def main(a_path, b_path):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    argv, ren = sys.argv[1:], []
+    while "--rename" in argv:
+        i = argv.index("--rename")
+        ren.append((argv[i + 1], argv[i + 2]))
+        del argv[i:i + 3]
+    sys.exit(main(argv[0], argv[1], ren or None))
