@@ -201,6 +201,14 @@ int kantts_lstm_bwd(const float* dout, const float* whh, const int32_t* lens, co
 int kantts_lstm_fwd_range(const float* gx, const float* whh, const float* bhh, const int32_t* lens, float* out,
                           float* gates_save, float* c_save, int B, int T, int H, int ndir, int reverse_first, int t0,
                           int t1, int precision, void* stream);
+/* kantts_lstm_fwd_range (one forward direction) with a range per sequence: t0 / t1 are DEVICE int32[B], clamped by the
+ * kernel to c0 = clamp(t0[b], 0, T), c1 = clamp(t1[b], c0, T) and never read back.  Sequence b runs steps
+ * [c0, min(c1, len)) from out[b, c0 - 1] / c_save[b, c0 - 1] and writes the zero tail for rows [max(len, c0), c1): the bits
+ * of kantts_lstm_fwd_range(..., c0, c1, ...) for that sequence; c0 == c1 reads and writes nothing.  KANTTS_LSTM_PAIR=0
+ * selects the quad kernel as above.  t0 == NULL or t1 == NULL: KANTTS_E_BADARG. */
+int kantts_lstm_fwd_slots(const float* gx, const float* whh, const float* bhh, const int32_t* lens, float* out,
+                          float* gates_save, float* c_save, int B, int T, int H, const int32_t* t0, const int32_t* t1,
+                          int precision, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Embedding gather-sum: out[row] = scale * sum_k table_k[ids[row,k]] (+ pos[row % T]);
@@ -273,6 +281,14 @@ int kantts_fsmn_dwconv_fwd(const float* x, const float* w, const float* res, con
  * t0 == t1: no-op. */
 int kantts_fsmn_dwconv_fwd_rows(const float* x, const float* w, const float* res, const int64_t* lens, float* y, int B,
                                 int T, int C, int K, int left_pad, int t0, int t1, void* stream);
+/* kantts_fsmn_dwconv_fwd_rows with a window per sequence: t0 / t1 are DEVICE int32[B], clamped by the kernel to
+ * c0 = clamp(t0[b], 0, T), c1 = min(clamp(t1[b], c0, T), c0 + max_rows) and never read back.  max_rows (host-known, >= 0)
+ * sizes the grid; a tile that starts at or after c1 exits.  Rows [c0, c1) of y equal the same rows of
+ * kantts_fsmn_dwconv_fwd_rows(..., c0, c1) bit for bit (41-tap and generic kernel), no other row is written.
+ * t0 == NULL, t1 == NULL or max_rows < 0: KANTTS_E_BADARG. */
+int kantts_fsmn_dwconv_fwd_slots(const float* x, const float* w, const float* res, const int64_t* lens, float* y, int B,
+                                 int T, int C, int K, int left_pad, const int32_t* t0, const int32_t* t1, int max_rows,
+                                 void* stream);
 int kantts_fsmn_dwconv_bwd(const float* dy, const float* x, const float* w, const int64_t* lens, float* dx,
                            float* dw_accum, float* workspace, long long ws_floats, int B, int T, int C, int K,
                            int left_pad, void* stream);
@@ -1083,6 +1099,12 @@ int kantts_ragged_rows_f32(const float* src, const int64_t* row_off, const int32
                            const float* pad, float* out, int B, int Tmax, int C, int transpose, void* stream);
 int kantts_ragged_rows_i64(const int64_t* src, const int64_t* row_off, const int32_t* start, const int32_t* len,
                            const int64_t* pad, int64_t* out, int B, int Tmax, int C, int transpose, void* stream);
+/* The inverse of kantts_ragged_rows_f32 (no transpose): in (B, Tmax, C) packed rows go back to the flat (rows, C) buffer,
+ *   dst[(row_off[b] + start[b] + t) * C + c] = in[b][t][c]      for t < min(len[b], Tmax)
+ * and nothing else of dst is written (start may be NULL).  16-byte accesses when C % 4 == 0 and both bases are 16-byte
+ * aligned.  The caller guarantees that the addressed rows exist. */
+int kantts_scatter_rows_f32(const float* in, const int64_t* row_off, const int32_t* start, const int32_t* len, float* dst,
+                            int B, int Tmax, int C, void* stream);
 
 /* Launch-shape knobs for sweeps and tests -- they never change a result.  tn_tile: output tile of kantts_bgemm_tn* as
  * BN * 1000 + BK (64128 / 128128 / 64256 / 128256; anything else = the library's rule; the code + 1, e.g. 64129, selects
@@ -1137,6 +1159,13 @@ int kantts_pnca_decode_run(const kantts_decode_args* args, void* stream);
  * of out and xkv is written, nothing at or after row t1 of out is read.  A device-side band width above 127 poisons rows
  * [t0, t1) of that sequence only.  t0 < 0, t1 > L or t0 > t1: KANTTS_E_BADARG; t0 == t1: no-op. */
 int kantts_pnca_decode_range(const kantts_decode_args* args, int t0, int t1, void* stream);
+/* Pool form (kantts/models/sambert/slots.py): every sequence advances over its own range.  t0 / t1: DEVICE int32[B]; the
+ * kernel clamps them -- c0 = clamp(t0[b], 0, L), c1 = clamp(t1[b], c0, L) -- and the host never reads them back (the
+ * convention of `rows` in kantts_sconv_rows_launch).  Rows [c0, c1) of out and xkv of sequence b are bit for bit what
+ * kantts_pnca_decode_range(args, c0, c1) writes there; nothing else of that sequence is written, no row of out at or after
+ * c1 is read, and a sequence with c0 == c1 reads and writes nothing.  A device-side band width above 127 poisons rows
+ * [c0, c1) of that sequence only.  t0 == NULL or t1 == NULL: KANTTS_E_BADARG. */
+int kantts_pnca_decode_slots(const kantts_decode_args* args, const int32_t* t0, const int32_t* t1, void* stream);
 int kantts_pnca_decode_blob_sizes(int d_mel, int d_mem, int d_out, int n_layer, long long* w_elems, long long* f_elems);
 
 /* kantts_dur_ar_run: the free-running duration predictor (VarRnnARPredictor.infer, kantts/models/sambert/adaptors.py:67-83):

@@ -241,7 +241,19 @@ __host__ __device__ inline ArDecLayout ar_dec_layout(int d_mel, int d_mem, int d
 
 // Steps [t0, t1) of every sequence (kantts_pnca_decode_range; kantts_pnca_decode_run is the range (0, L)).  Everything a later
 // step needs of an earlier one is in the full-length buffers: the K | V rows in xkv, the fed-back frame in out[b, t0 - 1].
-__global__ __launch_bounds__(AR_THREADS) void pnca_decode_run_kernel(const kantts_decode_args g, const int t0, const int t1) {
+// SLOTS = true (kantts_pnca_decode_slots): every sequence has its own range, read once from t0_seq[b] / t1_seq[b] and clamped
+// into 0 <= t0 <= t1 <= L; a workgroup whose range is empty leaves before it touches a buffer.  SLOTS = false ignores the two
+// arrays, so the (t0, t1) form is the code it was.
+template <bool SLOTS>
+__global__ __launch_bounds__(AR_THREADS) void pnca_decode_run_kernel(const kantts_decode_args g, const int t0_all, const int t1_all,
+                                                                     const int32_t* __restrict__ t0_seq,
+                                                                     const int32_t* __restrict__ t1_seq) {
+  int t0 = t0_all, t1 = t1_all;
+  if (SLOTS) {
+    t0 = min(max(t0_seq[blockIdx.x], 0), g.L);
+    t1 = min(max(t1_seq[blockIdx.x], t0), g.L);
+    if (t0 == t1) return;
+  }
   __shared__ __attribute__((aligned(16))) __bf16 vA[AR_FF];
   __shared__ __attribute__((aligned(16))) __bf16 vB[AR_FF];
   __shared__ __attribute__((aligned(16))) float xs[AR_D];
@@ -469,7 +481,8 @@ extern "C" int kantts_pnca_decode_run(const kantts_decode_args* a, void* stream)
     return KANTTS_E_UNSUPPORTED;
   if (!a->bw_seq && (a->bw < 0 || a->bw + 1 > AR_KMAX)) return KANTTS_E_UNSUPPORTED;
   if (a->B == 0 || a->L == 0) return KANTTS_OK;
-  hipLaunchKernelGGL(pnca_decode_run_kernel, dim3(a->B), dim3(AR_THREADS), 0, (hipStream_t)stream, *a, 0, a->L);
+  hipLaunchKernelGGL((pnca_decode_run_kernel<false>), dim3(a->B), dim3(AR_THREADS), 0, (hipStream_t)stream, *a, 0, a->L, nullptr,
+                     nullptr);
   KANTTS_CHECK_LAUNCH();
 }
 
@@ -480,7 +493,21 @@ extern "C" int kantts_pnca_decode_range(const kantts_decode_args* a, int t0, int
     return KANTTS_E_UNSUPPORTED;
   if (!a->bw_seq && (a->bw < 0 || a->bw + 1 > AR_KMAX)) return KANTTS_E_UNSUPPORTED;
   if (a->B == 0 || t0 == t1) return KANTTS_OK;
-  hipLaunchKernelGGL(pnca_decode_run_kernel, dim3(a->B), dim3(AR_THREADS), 0, (hipStream_t)stream, *a, t0, t1);
+  hipLaunchKernelGGL((pnca_decode_run_kernel<false>), dim3(a->B), dim3(AR_THREADS), 0, (hipStream_t)stream, *a, t0, t1, nullptr,
+                     nullptr);
+  KANTTS_CHECK_LAUNCH();
+}
+
+// Sequence b runs its own steps [t0[b], t1[b]) (device arrays, clamped by the kernel, never read back): the pool form of
+// kantts_pnca_decode_range.
+extern "C" int kantts_pnca_decode_slots(const kantts_decode_args* a, const int32_t* t0, const int32_t* t1, void* stream) {
+  if (!a || !a->w || !a->f || !a->memory || !a->hkv || !a->xkv || !a->out || a->B < 0 || a->L < 0 || !t0 || !t1)
+    return KANTTS_E_BADARG;
+  if (a->d_mel < 1 || a->d_mel > AR_D || a->d_mem < 1 || a->d_mem + AR_D > 512 || a->d_out < a->d_mel || a->n_layer < 0)
+    return KANTTS_E_UNSUPPORTED;
+  if (!a->bw_seq && (a->bw < 0 || a->bw + 1 > AR_KMAX)) return KANTTS_E_UNSUPPORTED;
+  if (a->B == 0 || a->L == 0) return KANTTS_OK;
+  hipLaunchKernelGGL((pnca_decode_run_kernel<true>), dim3(a->B), dim3(AR_THREADS), 0, (hipStream_t)stream, *a, 0, 0, t0, t1);
   KANTTS_CHECK_LAUNCH();
 }
 

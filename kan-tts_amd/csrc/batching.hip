@@ -52,3 +52,41 @@ extern "C" int kantts_ragged_rows_i64(const int64_t* src, const int64_t* row_off
                               reinterpret_cast<const long long*>(pad), reinterpret_cast<long long*>(out), B, Tmax, C,
                               transpose, stream);
 }
+
+// The inverse of ragged_rows_kernel for fp32 rows: the first min(len[b], Tmax) rows of in[b] go back to rows
+// row_off[b] + start[b] + t of a flat (rows, C) destination; nothing else of dst is written.  One thread per VEC consecutive
+// channels of a row (VEC = 4: 16-byte loads and stores, for C % 4 == 0 and 16-byte aligned bases).
+template <int VEC>
+__global__ __launch_bounds__(256) void scatter_rows_kernel(const float* __restrict__ in, const long long* __restrict__ row_off,
+                                                          const int* __restrict__ start, const int* __restrict__ len,
+                                                          float* __restrict__ dst, int Tmax, int C) {
+  const int b = blockIdx.y;
+  const int cv = C / VEC;
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long long)Tmax * cv) return;
+  const int t = (int)(e / cv), c = (int)(e - (long long)t * cv) * VEC;
+  if (t >= len[b]) return;
+  const float* s = in + ((long long)b * Tmax + t) * C + c;
+  float* d = dst + (row_off[b] + (start ? start[b] : 0) + t) * C + c;
+  if (VEC == 4)
+    *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(s);
+  else
+    *d = *s;
+}
+
+extern "C" int kantts_scatter_rows_f32(const float* in, const int64_t* row_off, const int32_t* start, const int32_t* len,
+                                       float* dst, int B, int Tmax, int C, void* stream) {
+  if (!in || !row_off || !len || !dst || B < 0 || Tmax < 0 || C < 1) return KANTTS_E_BADARG;
+  if (B == 0 || Tmax == 0) return KANTTS_OK;
+  if (B > 65535) return KANTTS_E_UNSUPPORTED;
+  const long long* ro = reinterpret_cast<const long long*>(row_off);
+  const bool vec = C % 4 == 0 && (reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(dst)) % 16 == 0;
+  if (vec) {
+    dim3 grid((unsigned)kantts_cdiv((long long)Tmax * (C / 4), 256), B);
+    hipLaunchKernelGGL((scatter_rows_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, in, ro, start, len, dst, Tmax, C);
+  } else {
+    dim3 grid((unsigned)kantts_cdiv((long long)Tmax * C, 256), B);
+    hipLaunchKernelGGL((scatter_rows_kernel<1>), grid, dim3(256), 0, (hipStream_t)stream, in, ro, start, len, dst, Tmax, C);
+  }
+  KANTTS_CHECK_LAUNCH();
+}

@@ -83,12 +83,22 @@ __device__ __forceinline__ float lstm_quad_bcast(float v) {
 // rows of gx do not exist yet) and the zero tail written for rows [max(len, t0), t1) only.  RANGE = false ignores t0 / t1:
 // every range expression below folds to the whole-sequence one at compile time, so the whole-sequence kernels (the pair form is
 // out of registers) pay nothing for the range form.
-template <bool BF16, bool RANGE>
+// RANGE = 2 (kantts_lstm_fwd_slots): the range form with every sequence's own [t0, t1), read once from t0_seq[b] / t1_seq[b] and
+// clamped into 0 <= t0 <= t1 <= T; a workgroup whose range is empty leaves before it touches a buffer.  RANGE = 0 / 1 ignore
+// the two arrays.
+template <bool BF16, int RANGE>
 __global__ __launch_bounds__(LG) void lstm_fwd_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
                                                       const float* __restrict__ bhh, const int32_t* __restrict__ lens,
                                                       float* __restrict__ out, float* __restrict__ gates_out,
                                                       float* __restrict__ c_out, int B, int T, int ndir,
-                                                      int reverse_first, int t0, int t1) {
+                                                      int reverse_first, int t0, int t1,
+                                                      const int32_t* __restrict__ t0_seq,
+                                                      const int32_t* __restrict__ t1_seq) {
+  if (RANGE == 2) {
+    t0 = min(max(t0_seq[blockIdx.x], 0), T);
+    t1 = min(max(t1_seq[blockIdx.x], t0), T);
+    if (t0 == t1) return;
+  }
   __shared__ __attribute__((aligned(16))) float h_s[2][LH];
   __shared__ __attribute__((aligned(16))) __bf16 h_b[2][LH];
   const int tid = threadIdx.x, j = tid >> 2, kq = tid & 3;
@@ -236,12 +246,19 @@ __global__ __launch_bounds__(LG) void lstm_fwd_kernel(const float* __restrict__ 
 // v_dot2: 0.70 us per step against 0.57 -- the step is a latency chain, not an issue-bound loop, and the accumulators of
 // four dependent 16-cycle MFMAs arrive later than the last v_dot2.
 // RANGE: as in lstm_fwd_kernel.
-template <bool RANGE>
+template <int RANGE>
 __global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
                                                            const float* __restrict__ bhh, const int32_t* __restrict__ lens,
                                                            float* __restrict__ out, float* __restrict__ gates_out,
                                                            float* __restrict__ c_out, int B, int T, int ndir,
-                                                           int reverse_first, int t0, int t1) {
+                                                           int reverse_first, int t0, int t1,
+                                                           const int32_t* __restrict__ t0_seq,
+                                                           const int32_t* __restrict__ t1_seq) {
+  if (RANGE == 2) {
+    t0 = min(max(t0_seq[blockIdx.x], 0), T);
+    t1 = min(max(t1_seq[blockIdx.x], t0), T);
+    if (t0 == t1) return;
+  }
   __shared__ __attribute__((aligned(16))) __bf16 h_b[2][LH];
   const int tid = threadIdx.x, j = tid >> 1, p = tid & 1;
   const int b = blockIdx.x, dir = blockIdx.y;
@@ -665,14 +682,14 @@ extern "C" int kantts_lstm_fwd(const float* gx, const float* whh, const float* b
   if (B == 0 || T == 0) return KANTTS_OK;
   static const char* env_pair = getenv("KANTTS_LSTM_PAIR");  // A/B switch (read once per process): 0 = the quad kernel
   if (precision == 1 && !(env_pair && atoi(env_pair) == 0))
-    hipLaunchKernelGGL((lstm_fwd_pair_kernel<false>), dim3(B, ndir), dim3(256), 0, (hipStream_t)stream, gx, whh,
-                       bhh, lens, out, gates_save, c_save, B, T, ndir, reverse_first, 0, T);
+    hipLaunchKernelGGL((lstm_fwd_pair_kernel<0>), dim3(B, ndir), dim3(256), 0, (hipStream_t)stream, gx, whh,
+                       bhh, lens, out, gates_save, c_save, B, T, ndir, reverse_first, 0, T, (const int32_t*)nullptr, (const int32_t*)nullptr);
   else if (precision == 1)
-    hipLaunchKernelGGL((lstm_fwd_kernel<true, false>), dim3(B, ndir), dim3(LG), 0, (hipStream_t)stream, gx, whh,
-                       bhh, lens, out, gates_save, c_save, B, T, ndir, reverse_first, 0, T);
+    hipLaunchKernelGGL((lstm_fwd_kernel<true, 0>), dim3(B, ndir), dim3(LG), 0, (hipStream_t)stream, gx, whh,
+                       bhh, lens, out, gates_save, c_save, B, T, ndir, reverse_first, 0, T, (const int32_t*)nullptr, (const int32_t*)nullptr);
   else
-    hipLaunchKernelGGL((lstm_fwd_kernel<false, false>), dim3(B, ndir), dim3(LG), 0, (hipStream_t)stream, gx, whh,
-                       bhh, lens, out, gates_save, c_save, B, T, ndir, reverse_first, 0, T);
+    hipLaunchKernelGGL((lstm_fwd_kernel<false, 0>), dim3(B, ndir), dim3(LG), 0, (hipStream_t)stream, gx, whh,
+                       bhh, lens, out, gates_save, c_save, B, T, ndir, reverse_first, 0, T, (const int32_t*)nullptr, (const int32_t*)nullptr);
   KANTTS_CHECK_LAUNCH();
 }
 
@@ -689,14 +706,35 @@ extern "C" int kantts_lstm_fwd_range(const float* gx, const float* whh, const fl
   if (B == 0 || t0 == t1) return KANTTS_OK;
   static const char* env_pair = getenv("KANTTS_LSTM_PAIR");  // A/B switch (read once per process): 0 = the quad kernel
   if (precision == 1 && !(env_pair && atoi(env_pair) == 0))
-    hipLaunchKernelGGL((lstm_fwd_pair_kernel<true>), dim3(B, 1), dim3(256), 0, (hipStream_t)stream, gx, whh, bhh,
-                       lens, out, gates_save, c_save, B, T, 1, 0, t0, t1);
+    hipLaunchKernelGGL((lstm_fwd_pair_kernel<1>), dim3(B, 1), dim3(256), 0, (hipStream_t)stream, gx, whh, bhh,
+                       lens, out, gates_save, c_save, B, T, 1, 0, t0, t1, (const int32_t*)nullptr, (const int32_t*)nullptr);
   else if (precision == 1)
-    hipLaunchKernelGGL((lstm_fwd_kernel<true, true>), dim3(B, 1), dim3(LG), 0, (hipStream_t)stream, gx, whh, bhh,
-                       lens, out, gates_save, c_save, B, T, 1, 0, t0, t1);
+    hipLaunchKernelGGL((lstm_fwd_kernel<true, 1>), dim3(B, 1), dim3(LG), 0, (hipStream_t)stream, gx, whh, bhh,
+                       lens, out, gates_save, c_save, B, T, 1, 0, t0, t1, (const int32_t*)nullptr, (const int32_t*)nullptr);
   else
-    hipLaunchKernelGGL((lstm_fwd_kernel<false, true>), dim3(B, 1), dim3(LG), 0, (hipStream_t)stream, gx, whh, bhh,
-                       lens, out, gates_save, c_save, B, T, 1, 0, t0, t1);
+    hipLaunchKernelGGL((lstm_fwd_kernel<false, 1>), dim3(B, 1), dim3(LG), 0, (hipStream_t)stream, gx, whh, bhh,
+                       lens, out, gates_save, c_save, B, T, 1, 0, t0, t1, (const int32_t*)nullptr, (const int32_t*)nullptr);
+  KANTTS_CHECK_LAUNCH();
+}
+
+// kantts_lstm_fwd_range with a range per sequence: [t0[b], t1[b]) from device arrays, clamped by the kernel (RANGE = 2).
+extern "C" int kantts_lstm_fwd_slots(const float* gx, const float* whh, const float* bhh, const int32_t* lens, float* out,
+                                     float* gates_save, float* c_save, int B, int T, int H, const int32_t* t0,
+                                     const int32_t* t1, int precision, void* stream) {
+  if (!gx || !whh || !out || !gates_save || !c_save || B < 0 || T < 0 || !t0 || !t1) return KANTTS_E_BADARG;
+  if (H != LH) return KANTTS_E_UNSUPPORTED;
+  if ((long long)T * LG >= (1ll << 31)) return KANTTS_E_UNSUPPORTED;  // 32-bit offsets inside one sequence
+  if (B == 0 || T == 0) return KANTTS_OK;
+  static const char* env_pair = getenv("KANTTS_LSTM_PAIR");  // A/B switch (read once per process): 0 = the quad kernel
+  if (precision == 1 && !(env_pair && atoi(env_pair) == 0))
+    hipLaunchKernelGGL((lstm_fwd_pair_kernel<2>), dim3(B, 1), dim3(256), 0, (hipStream_t)stream, gx, whh, bhh,
+                       lens, out, gates_save, c_save, B, T, 1, 0, 0, 0, t0, t1);
+  else if (precision == 1)
+    hipLaunchKernelGGL((lstm_fwd_kernel<true, 2>), dim3(B, 1), dim3(LG), 0, (hipStream_t)stream, gx, whh, bhh,
+                       lens, out, gates_save, c_save, B, T, 1, 0, 0, 0, t0, t1);
+  else
+    hipLaunchKernelGGL((lstm_fwd_kernel<false, 2>), dim3(B, 1), dim3(LG), 0, (hipStream_t)stream, gx, whh, bhh,
+                       lens, out, gates_save, c_save, B, T, 1, 0, 0, 0, t0, t1);
   KANTTS_CHECK_LAUNCH();
 }
 

@@ -264,12 +264,20 @@ extern "C" int kantts_lr_gather_bwd(const float* dout, const int32_t* cs, const 
 // keep[b,t] = t < lens[b] (all ones when lens == NULL).  Block = one (b, 32-frame tile), thread = channel.
 // ROWS = true (kantts_fsmn_dwconv_fwd_rows): the tiles start at row r0 and only rows [r0, r1) are computed; a row sums its
 // taps in the same order wherever it sits in a tile, so it equals the same row of a whole call bit for bit.  ROWS = false
-// ignores r0 / r1.
+// ignores r0 / r1.  ROWS = 2 (kantts_fsmn_dwconv_fwd_slots): the rows form with every sequence's own window, read once from
+// r0_seq[b] / r1_seq[b] and clamped into 0 <= r0 <= r1 <= min(T, r0 + max_rows); a tile that starts at or after r1 exits.
 #define DW_TT 32
-template <bool ROWS>
+template <int ROWS>
 __global__ void fsmn_dwconv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                        const float* __restrict__ res, const int64_t* __restrict__ lens,
-                                       float* __restrict__ y, int B, int T, int C, int K, int lp, int r0, int r1) {
+                                       float* __restrict__ y, int B, int T, int C, int K, int lp, int r0, int r1,
+                                       const int32_t* __restrict__ r0_seq, const int32_t* __restrict__ r1_seq,
+                                       int max_rows) {
+  if (ROWS == 2) {
+    r0 = min(max(r0_seq[blockIdx.y], 0), T);
+    r1 = min(min(max(r1_seq[blockIdx.y], r0), T), r0 + max_rows);
+    if (r0 + (int)blockIdx.x * DW_TT >= r1) return;
+  }
   const int b = blockIdx.y, t0 = (ROWS ? r0 : 0) + blockIdx.x * DW_TT;
   const int len = lens ? (int)min((long long)lens[b], (long long)T) : T;
   const float* xb = x + (long long)b * T * C;
@@ -349,12 +357,14 @@ __global__ void fsmn_dwconv_bwd_dw_kernel(const float* __restrict__ dy, const fl
 #define FS_TT 16
 // ROWS = true (kantts_fsmn_dwconv_fwd_rows; forward only): the 16-frame tiles start at row r0, rows at or after r1 are not
 // written, and no input row at or after r1 + (K - 1 - lp) is read -- in a streaming caller those rows do not exist yet.
-// ROWS = false ignores r0 / r1.
-template <bool FLIP, bool ROWS>
+// ROWS = false ignores r0 / r1.  ROWS = 2: per-sequence windows, as in fsmn_dwconv_fwd_kernel.
+template <bool FLIP, int ROWS>
 __global__ __launch_bounds__(256, 2) void fsmn_fir41_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ res,
                                                         const int64_t* __restrict__ lens, float* __restrict__ y, int B,
-                                                        int T, int C, int lp, int xcd_order, int r0, int r1) {
+                                                        int T, int C, int lp, int xcd_order, int r0, int r1,
+                                                        const int32_t* __restrict__ r0_seq,
+                                                        const int32_t* __restrict__ r1_seq, int max_rows) {
   // [round 6] XCD-aware order: a block reads a 56-frame window for its 16 output frames, so neighbouring blocks share 40 of
   // their rows -- and consecutive block ids are dealt to the 8 XCDs in turn, each with its own L2: the counters showed
   // 2.6 x the input fetched from HBM / the memory-side cache (profiles/r06_runFINAL_fetch_pmc.txt: 52 MB for 20 MB at the
@@ -369,6 +379,11 @@ __global__ __launch_bounds__(256, 2) void fsmn_fir41_kernel(const float* __restr
       by = vid / gx;
       bx = vid - by * gx;
     }
+  }
+  if (ROWS == 2) {
+    r0 = min(max(r0_seq[by], 0), T);
+    r1 = min(min(max(r1_seq[by], r0), T), r0 + max_rows);
+    if (r0 + bx * FS_TT >= r1) return;
   }
   const int b = by, t0 = (ROWS ? r0 : 0) + bx * FS_TT;
   const int len = lens ? (int)min((long long)lens[b], (long long)T) : T;
@@ -515,11 +530,12 @@ extern "C" int kantts_fsmn_dwconv_fwd(const float* x, const float* w, const floa
   if (B == 0 || T == 0) return KANTTS_OK;
   const int threads = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
   if (K == FS_K) {
-    hipLaunchKernelGGL((fsmn_fir41_kernel<false, false>), dim3(kantts_cdiv(T, FS_TT), B), dim3(threads), 0,
-                       (hipStream_t)stream, x, w, res, lens, y, B, T, C, left_pad, fs_xcd_order(), 0, T);
+    hipLaunchKernelGGL((fsmn_fir41_kernel<false, 0>), dim3(kantts_cdiv(T, FS_TT), B), dim3(threads), 0,
+                       (hipStream_t)stream, x, w, res, lens, y, B, T, C, left_pad, fs_xcd_order(), 0, T,
+                       (const int32_t*)nullptr, (const int32_t*)nullptr, 0);
   } else {
-    hipLaunchKernelGGL(fsmn_dwconv_fwd_kernel<false>, dim3(kantts_cdiv(T, DW_TT), B), dim3(threads), 0, (hipStream_t)stream, x,
-                       w, res, lens, y, B, T, C, K, left_pad, 0, T);
+    hipLaunchKernelGGL(fsmn_dwconv_fwd_kernel<0>, dim3(kantts_cdiv(T, DW_TT), B), dim3(threads), 0, (hipStream_t)stream, x,
+                       w, res, lens, y, B, T, C, K, left_pad, 0, T, (const int32_t*)nullptr, (const int32_t*)nullptr, 0);
   }
   KANTTS_CHECK_LAUNCH();
 }
@@ -532,11 +548,32 @@ extern "C" int kantts_fsmn_dwconv_fwd_rows(const float* x, const float* w, const
   if (B == 0 || t0 == t1) return KANTTS_OK;
   const int threads = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
   if (K == FS_K) {
-    hipLaunchKernelGGL((fsmn_fir41_kernel<false, true>), dim3(kantts_cdiv(t1 - t0, FS_TT), B), dim3(threads), 0,
-                       (hipStream_t)stream, x, w, res, lens, y, B, T, C, left_pad, fs_xcd_order(), t0, t1);
+    hipLaunchKernelGGL((fsmn_fir41_kernel<false, 1>), dim3(kantts_cdiv(t1 - t0, FS_TT), B), dim3(threads), 0,
+                       (hipStream_t)stream, x, w, res, lens, y, B, T, C, left_pad, fs_xcd_order(), t0, t1,
+                       (const int32_t*)nullptr, (const int32_t*)nullptr, 0);
   } else {
-    hipLaunchKernelGGL(fsmn_dwconv_fwd_kernel<true>, dim3(kantts_cdiv(t1 - t0, DW_TT), B), dim3(threads), 0,
-                       (hipStream_t)stream, x, w, res, lens, y, B, T, C, K, left_pad, t0, t1);
+    hipLaunchKernelGGL(fsmn_dwconv_fwd_kernel<1>, dim3(kantts_cdiv(t1 - t0, DW_TT), B), dim3(threads), 0,
+                       (hipStream_t)stream, x, w, res, lens, y, B, T, C, K, left_pad, t0, t1, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr, 0);
+  }
+  KANTTS_CHECK_LAUNCH();
+}
+
+// kantts_fsmn_dwconv_fwd_rows with a window per sequence: rows [t0[b], t1[b]) from device arrays, clamped by the kernel to
+// 0 <= t0 <= t1 <= min(T, t0 + max_rows).  max_rows is what the host knows: it sizes the grid, so it is part of the contract.
+extern "C" int kantts_fsmn_dwconv_fwd_slots(const float* x, const float* w, const float* res, const int64_t* lens, float* y,
+                                            int B, int T, int C, int K, int left_pad, const int32_t* t0, const int32_t* t1,
+                                            int max_rows, void* stream) {
+  if (!x || !w || !y || B < 0 || T < 0 || C < 1 || K < 1 || !t0 || !t1 || max_rows < 0) return KANTTS_E_BADARG;
+  if (max_rows > T) max_rows = T;
+  if (B == 0 || max_rows == 0) return KANTTS_OK;
+  const int threads = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
+  if (K == FS_K) {
+    hipLaunchKernelGGL((fsmn_fir41_kernel<false, 2>), dim3(kantts_cdiv(max_rows, FS_TT), B), dim3(threads), 0,
+                       (hipStream_t)stream, x, w, res, lens, y, B, T, C, left_pad, fs_xcd_order(), 0, 0, t0, t1, max_rows);
+  } else {
+    hipLaunchKernelGGL(fsmn_dwconv_fwd_kernel<2>, dim3(kantts_cdiv(max_rows, DW_TT), B), dim3(threads), 0,
+                       (hipStream_t)stream, x, w, res, lens, y, B, T, C, K, left_pad, 0, 0, t0, t1, max_rows);
   }
   KANTTS_CHECK_LAUNCH();
 }
@@ -554,8 +591,9 @@ extern "C" int kantts_fsmn_dwconv_bwd(const float* dy, const float* x, const flo
     const int nchunk = kantts_cdiv(T, FS_CH);
     if (dw_accum && (!workspace || ws_floats < (long long)B * nchunk * C * K)) return KANTTS_E_WORKSPACE;
     if (dx)
-      hipLaunchKernelGGL((fsmn_fir41_kernel<true, false>), dim3(kantts_cdiv(T, FS_TT), B), dim3(threads), 0, st, dy,
-                         w, (const float*)nullptr, lens, dx, B, T, C, left_pad, fs_xcd_order(), 0, T);
+      hipLaunchKernelGGL((fsmn_fir41_kernel<true, 0>), dim3(kantts_cdiv(T, FS_TT), B), dim3(threads), 0, st, dy,
+                         w, (const float*)nullptr, lens, dx, B, T, C, left_pad, fs_xcd_order(), 0, T, (const int32_t*)nullptr,
+                         (const int32_t*)nullptr, 0);
     if (dw_accum) {
       hipLaunchKernelGGL(fsmn_dw41_partial_kernel, dim3(nchunk, B, kantts_cdiv(C, 64)), dim3(256), 0, st, dy, x, lens,
                          workspace, B, T, C, left_pad);

@@ -456,6 +456,10 @@ def lib():
         L.kantts_pnca_decode_range.argtypes = [POINTER(DecodeArgs), c_int, c_int, c_void_p]
         L.kantts_lstm_fwd_range.argtypes = [p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, p]
         L.kantts_fsmn_dwconv_fwd_rows.argtypes = [p, p, p, p, p, i, i, i, i, i, i, i, p]
+        L.kantts_pnca_decode_slots.argtypes = [POINTER(DecodeArgs), p, p, c_void_p]
+        L.kantts_lstm_fwd_slots.argtypes = [p, p, p, p, p, p, p, i, i, i, p, p, i, p]
+        L.kantts_fsmn_dwconv_fwd_slots.argtypes = [p, p, p, p, p, i, i, i, i, i, p, p, i, p]
+        L.kantts_scatter_rows_f32.argtypes = [p, p, p, p, p, i, i, i, p]
         _lib = L
     return _lib
 
@@ -481,6 +485,7 @@ EXPORTED_SYMBOLS = [
     "kantts_pnca_decode_run", "kantts_pnca_decode_blob_sizes", "kantts_dur_ar_run", "kantts_dur_ar_run_f32", "kantts_ctc_attn", "kantts_ctc_attn_workspace", "kantts_enc_attn_fwd",
     "kantts_launch_tuning", "kantts_sconv_launch", "kantts_sconv_rows_launch",
     "kantts_pnca_decode_range", "kantts_lstm_fwd_range", "kantts_fsmn_dwconv_fwd_rows",
+    "kantts_pnca_decode_slots", "kantts_lstm_fwd_slots", "kantts_fsmn_dwconv_fwd_slots", "kantts_scatter_rows_f32",
 ]
 
 
@@ -916,10 +921,12 @@ def decode_blob_sizes(d_mel, d_mem, d_out, n_layer):
     return None if rc != 0 else (int(w.value), int(f.value))
 
 
-def pnca_decode_run(w, f, memory, hkv, xkv, out, lens32, bw_seq, bw, d_mel, n_layer, in_scale, eps, steps=None):
+def pnca_decode_run(w, f, memory, hkv, xkv, out, lens32, bw_seq, bw, d_mel, n_layer, in_scale, eps, steps=None, slots=None):
     """Every step of the free-running mel decoder for every sequence in one launch (csrc/ar_infer.hip).
     ``steps=(t0, t1)``: only those steps, resuming from what earlier calls left in ``out`` / ``xkv``
-    (kantts_pnca_decode_range); returns the library's status code instead of raising."""
+    (kantts_pnca_decode_range); returns the library's status code instead of raising.
+    ``slots=(t0, t1)``: int32 device tensors (or None) of B per-sequence ranges (kantts_pnca_decode_slots); returns the
+    status code."""
     B, L, d_mem = memory.shape
     g = DecodeArgs()
     g.w, g.f = ptr(w, torch.bfloat16), ptr(f, torch.float32)
@@ -929,6 +936,10 @@ def pnca_decode_run(w, f, memory, hkv, xkv, out, lens32, bw_seq, bw, d_mel, n_la
     g.in_scale, g.eps = float(in_scale), float(eps)
     for t in (memory, hkv, xkv, out):
         assert t.is_contiguous()
+    if slots is not None:
+        for t in slots:
+            assert t is None or t.numel() == int(B)
+        return lib().kantts_pnca_decode_slots(ctypes.byref(g), ptr(slots[0], torch.int32), ptr(slots[1], torch.int32), stream())
     if steps is not None:
         return lib().kantts_pnca_decode_range(ctypes.byref(g), int(steps[0]), int(steps[1]), stream())
     check(lib().kantts_pnca_decode_run(ctypes.byref(g), stream()), "pnca_decode_run")
@@ -958,6 +969,50 @@ def fsmn_dwconv_fwd_rows(x, w, res, lens64, y, left_pad, t0, t1):
     return lib().kantts_fsmn_dwconv_fwd_rows(ptr(x, torch.float32), ptr(w, torch.float32), ptr(res), ptr(lens64), ptr(y),
                                              int(B), int(T), int(C), int(w.shape[-1]), int(left_pad), int(t0), int(t1),
                                              stream())
+
+
+def slot_entry_points():
+    """True when the loaded library exports the four per-slot entry points of AcousticSlots."""
+    L = lib()
+    return all(hasattr(L, n) for n in ("kantts_pnca_decode_slots", "kantts_lstm_fwd_slots", "kantts_fsmn_dwconv_fwd_slots",
+                                       "kantts_scatter_rows_f32"))
+
+
+def lstm_fwd_slots(gx, whh, bhh, lens32, out, gates, cst, t0, t1, precision):
+    """Steps [t0[b], t1[b]) of the forward LSTM recurrence per sequence (int32 device tensors of B entries, clamped by the
+    kernel) over full-length buffers (csrc/lstm.hip); returns the status code."""
+    B, T, H = out.shape[0], out.shape[1], whh.shape[-1]
+    for t in (gx, whh, out, gates, cst):
+        assert t.is_contiguous()
+    for t in (t0, t1):
+        assert t is None or t.numel() == int(B)
+    return lib().kantts_lstm_fwd_slots(ptr(gx, torch.float32), ptr(whh, torch.float32), ptr(bhh), ptr(lens32), ptr(out),
+                                       ptr(gates), ptr(cst), int(B), int(T), int(H), ptr(t0, torch.int32), ptr(t1, torch.int32),
+                                       int(precision), stream())
+
+
+def fsmn_dwconv_fwd_slots(x, w, res, lens64, y, left_pad, t0, t1, max_rows):
+    """Rows [t0[b], min(t1[b], t0[b] + max_rows)) of the FSMN memory block per sequence (int32 device tensors of B entries,
+    clamped by the kernel) over full-length buffers (csrc/seq.hip); returns the status code."""
+    B, T, C = x.shape
+    for t in (x, w, y) + (() if res is None else (res,)):
+        assert t.is_contiguous()
+    for t in (t0, t1):
+        assert t is None or t.numel() == int(B)
+    return lib().kantts_fsmn_dwconv_fwd_slots(ptr(x, torch.float32), ptr(w, torch.float32), ptr(res), ptr(lens64), ptr(y),
+                                              int(B), int(T), int(C), int(w.shape[-1]), int(left_pad), ptr(t0, torch.int32),
+                                              ptr(t1, torch.int32), int(max_rows), stream())
+
+
+def scatter_rows(packed, row_off, lens, dst, *, start=None):
+    """The inverse of ``ragged_rows`` (csrc/batching.hip): dst[row_off[b] + start[b] + t] = packed[b, t] for
+    t < min(lens[b], Tmax); ``packed`` (B, Tmax, C) and ``dst`` (rows, C) fp32, nothing else of ``dst`` is written.  The
+    caller guarantees that the addressed rows exist.  Returns the status code."""
+    B, Tmax, C = packed.shape
+    assert packed.is_contiguous() and dst.is_contiguous() and int(dst.shape[-1]) == int(C)
+    assert int(row_off.numel()) == int(B) and int(lens.numel()) == int(B)
+    return lib().kantts_scatter_rows_f32(ptr(packed, torch.float32), ptr(row_off, torch.int64), ptr(start, torch.int32),
+                                         ptr(lens, torch.int32), ptr(dst, torch.float32), int(B), int(Tmax), int(C), stream())
 
 
 def dur_ar_run(w, f, gc, out, lens32):

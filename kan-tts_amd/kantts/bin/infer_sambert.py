@@ -20,9 +20,8 @@ logging.basicConfig(format="%(asctime)s, %(levelname)-4s [%(filename)s:%(lineno)
                     datefmt="%Y-%m-%d:%H:%M:%S", level=logging.INFO)
 
 
-def am_synthesis(symbol_seq, fsnet, ling_unit, device, se=None, chunked=None, chunk_steps=None, chunk_times=None):
-    """``chunked`` (a ChunkedAcoustic of ``fsnet``) with ``chunk_steps``: the same outputs through a streaming session;
-    the seconds after which each chunk's frames were on the host are appended to ``chunk_times``."""
+def am_inputs(symbol_seq, ling_unit, device, se=None):
+    """(inputs_ling, inputs_emotion, inputs_speaker, input_lengths) of one sentence, batch 1."""
     if ling_unit.using_byte():
         raise NotImplementedError("byte-index inputs (sambert_16k_MAS_byte.yaml) are outside the hot path")
     feats = ling_unit.encode_symbol_sequence(symbol_seq)
@@ -37,6 +36,25 @@ def am_synthesis(symbol_seq, fsnet, ling_unit, device, se=None, chunked=None, ch
     else:
         inputs_spk = spk.unsqueeze(0)[:, :-1]
     inputs_len = torch.full((1,), inputs_emo.size(1), dtype=torch.long, device=device)
+    return inputs_ling, inputs_emo, inputs_spk, inputs_len
+
+
+def am_outputs(res):
+    """What am_synthesis returns, from the dictionary the model (or a streaming session) returns for one utterance."""
+    valid_length = int(res["LR_length_rounded"][0].item())
+    dec_outputs = res["dec_outputs"][0, :valid_length, :].cpu().numpy()
+    postnet_outputs = res["postnet_outputs"][0, :valid_length, :].cpu().numpy()
+    duration_predictions = (torch.exp(res["log_duration_predictions"]) - 1 + 0.5).long().squeeze().cpu().numpy()
+    pitch_predictions = res["pitch_predictions"].squeeze().cpu().numpy()
+    energy_predictions = res["energy_predictions"].squeeze().cpu().numpy()
+    logging.info("x_band_width:%s, h_band_width: %s", res["x_band_width"], res["h_band_width"])
+    return dec_outputs, postnet_outputs, duration_predictions, pitch_predictions, energy_predictions
+
+
+def am_synthesis(symbol_seq, fsnet, ling_unit, device, se=None, chunked=None, chunk_steps=None, chunk_times=None):
+    """``chunked`` (a ChunkedAcoustic of ``fsnet``) with ``chunk_steps``: the same outputs through a streaming session;
+    the seconds after which each chunk's frames were on the host are appended to ``chunk_times``."""
+    inputs_ling, inputs_emo, inputs_spk, inputs_len = am_inputs(symbol_seq, ling_unit, device, se=se)
     if chunked is not None:
         t0 = time.time()
         sess = chunked.open(inputs_ling, inputs_emo, inputs_spk, inputs_len)
@@ -47,14 +65,7 @@ def am_synthesis(symbol_seq, fsnet, ling_unit, device, se=None, chunked=None, ch
         res = sess.result()
     else:
         res = fsnet(inputs_ling, inputs_emo, inputs_spk, inputs_len)
-    valid_length = int(res["LR_length_rounded"][0].item())
-    dec_outputs = res["dec_outputs"][0, :valid_length, :].cpu().numpy()
-    postnet_outputs = res["postnet_outputs"][0, :valid_length, :].cpu().numpy()
-    duration_predictions = (torch.exp(res["log_duration_predictions"]) - 1 + 0.5).long().squeeze().cpu().numpy()
-    pitch_predictions = res["pitch_predictions"].squeeze().cpu().numpy()
-    energy_predictions = res["energy_predictions"].squeeze().cpu().numpy()
-    logging.info("x_band_width:%s, h_band_width: %s", res["x_band_width"], res["h_band_width"])
-    return dec_outputs, postnet_outputs, duration_predictions, pitch_predictions, energy_predictions
+    return am_outputs(res)
 
 
 def denorm_f0(mel, scale, offset, f0_threshold=30.0, uv_threshold=0.6):
@@ -67,7 +78,11 @@ def denorm_f0(mel, scale, offset, f0_threshold=30.0, uv_threshold=0.6):
     return mel
 
 
-def am_infer(sentence, ckpt, output_dir, se_file=None, config=None, ling_unit=None, chunk_frames=None):
+def am_infer(sentence, ckpt, output_dir, se_file=None, config=None, ling_unit=None, chunk_frames=None, slots=None,
+             slot_steps=1024):
+    """``slots`` (with ``chunk_frames``): the sentences play through a pool of that many independently advancing streaming
+    slots (AcousticSlots.play_many, buffers of ``slot_steps`` decoder steps per slot) instead of one session each; the
+    files written are the same."""
     device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
     if not isinstance(config, dict):
         path = config if config is not None else os.path.join(os.path.dirname(os.path.dirname(ckpt)), "config.yaml")
@@ -114,26 +129,55 @@ def am_infer(sentence, ckpt, output_dir, se_file=None, config=None, ling_unit=No
         from kantts.models.sambert.chunked import ChunkedAcoustic
 
         chunked, chunk_steps = ChunkedAcoustic(fsnet), chunk_frames // r  # refuses what it cannot stream, loudly
+    if slots is not None:
+        if chunk_frames is None:
+            raise ValueError("--slots needs --chunk_frames")
+        if slots < 1:
+            raise ValueError("--slots must be positive, got %d" % slots)
+        from kantts.models.sambert.slots import AcousticSlots
+
+        pool = AcousticSlots(fsnet, slots=slots, max_steps=slot_steps)  # refuses what it cannot stream, loudly
     with open(sentence, encoding="utf-8") as f:
-        for line in f:
-            line = line.strip().split("\t")
-            if len(line) < 2:
-                continue
+        lines = [ln for ln in (line.strip().split("\t") for line in f) if len(ln) >= 2]
+    if slots is not None:
+        with torch.no_grad():
+            requests = [am_inputs(line[1], ling_unit, device, se=se) for line in lines]
+            results, t0, first = {}, time.time(), {}
+            for index, _, _, mel in pool.play_many(requests, chunk_steps, results=results):
+                if index not in first:
+                    mel.cpu()  # the copy to the host is when a chunk can be handed on
+                    first[index] = time.time() - t0
+        for index, line in enumerate(lines):
             logging.info("Inference sentence: %s", line[0])
-            with torch.no_grad():
-                times = []
-                _, mel_post, dur, f0, energy = am_synthesis(line[1], fsnet, ling_unit, device, se=se, chunked=chunked,
-                                                            chunk_steps=chunk_steps, chunk_times=times)
-            if times:
-                first_chunk.append(times[0])
-                chunk_ms += list(np.diff([0.0] + times))
-                totals.append(times[-1])
+            _, mel_post, dur, f0, energy = am_outputs(results[index])
             if nsf is not None:
                 mel_post = denorm_f0(mel_post, scale=nsf[0], offset=nsf[1])
             np.save("%s/%s_mel.npy" % (results_dir, line[0]), mel_post)
             np.savetxt("%s/%s_dur.txt" % (results_dir, line[0]), dur)
             np.savetxt("%s/%s_f0.txt" % (results_dir, line[0]), f0)
             np.savetxt("%s/%s_energy.txt" % (results_dir, line[0]), energy)
+        if first:
+            logging.info("Finished inference of %d utterances through %d slots (%d frames per chunk, time from the start to an "
+                         "utterance's first chunk: median %.2f ms, worst %.2f ms; total %.2f ms).", len(lines), slots,
+                         chunk_frames, 1e3 * float(np.median(list(first.values()))), 1e3 * max(first.values()),
+                         1e3 * (time.time() - t0))
+        return
+    for line in lines:
+        logging.info("Inference sentence: %s", line[0])
+        with torch.no_grad():
+            times = []
+            _, mel_post, dur, f0, energy = am_synthesis(line[1], fsnet, ling_unit, device, se=se, chunked=chunked,
+                                                        chunk_steps=chunk_steps, chunk_times=times)
+        if times:
+            first_chunk.append(times[0])
+            chunk_ms += list(np.diff([0.0] + times))
+            totals.append(times[-1])
+        if nsf is not None:
+            mel_post = denorm_f0(mel_post, scale=nsf[0], offset=nsf[1])
+        np.save("%s/%s_mel.npy" % (results_dir, line[0]), mel_post)
+        np.savetxt("%s/%s_dur.txt" % (results_dir, line[0]), dur)
+        np.savetxt("%s/%s_f0.txt" % (results_dir, line[0]), f0)
+        np.savetxt("%s/%s_energy.txt" % (results_dir, line[0]), energy)
     if chunked is not None and first_chunk:
         logging.info("Finished chunked inference of %d utterances (%d frames per chunk, time to first chunk: median %.2f ms, "
                      "first utterance %.2f ms; median chunk %.2f ms; total %.2f ms per utterance).", len(first_chunk),
@@ -147,15 +191,23 @@ if __name__ == "__main__":
     parser.add_argument("--output_dir", type=str, required=True)
     parser.add_argument("--ckpt", type=str, required=True)
     parser.add_argument("--se_file", type=str, required=False)
+    parser.add_argument("--slots", type=int, default=None,
+                        help="With --chunk_frames: play the sentences through a pool of this many independently advancing "
+                             "streaming slots (continuous batching)")
+    parser.add_argument("--slot_steps", type=int, default=1024,
+                        help="With --slots: decoder steps the buffers of a slot hold (the longest utterance it can take)")
     parser.add_argument("--chunk_frames", type=int, default=None,
                         help="Infer chunk by chunk through a streaming session, this many mel frames at a time (a multiple "
                              "of outputs_per_step; bf16 mode)")
     args = parser.parse_args()
     if args.chunk_frames is not None and args.chunk_frames < 1:
         parser.error("--chunk_frames must be positive")
+    if args.slots is not None and args.chunk_frames is None:
+        parser.error("--slots needs --chunk_frames")
     try:
-        am_infer(args.sentence, args.ckpt, args.output_dir, args.se_file, chunk_frames=args.chunk_frames)
+        am_infer(args.sentence, args.ckpt, args.output_dir, args.se_file, chunk_frames=args.chunk_frames, slots=args.slots,
+                 slot_steps=args.slot_steps)
     except ValueError as e:
-        if "--chunk_frames" not in str(e):
+        if "--chunk_frames" not in str(e) and "--slots" not in str(e):
             raise
         parser.error(str(e))

@@ -28,7 +28,8 @@ sequence really has, which is what a multi-slot vocoder takes as its per-slot co
 
     wav = vocoder.step(mel.transpose(1, 2), rows=sess.live_rows(lo, hi))     # every slot stops at its own last frame
 
-Not here: graph capture of a step, independently advancing slots, an fp32-mode decoder range.
+Independently advancing slots (continuous batching) are kantts/models/sambert/slots.py.  Not here: graph capture of a step,
+an fp32-mode decoder range.
 """
 import torch
 import torch.nn as nn
