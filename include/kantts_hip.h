@@ -1330,6 +1330,89 @@ typedef struct {
 } kantts_sconv_rows_args;
 int kantts_sconv_rows_launch(const kantts_sconv_rows_args* args, void* stream);
 
+/* ---- The NSF excitation of chunked inference (csrc/nsf_source.hip): a sine source that can be cut at any frame boundary
+ * and the strided one-channel convolutions that bring it to every upsampling stage's rate.  Both entry points are per slot
+ * and read the same device `rows` buffer as kantts_sconv_rows_launch:
+ *   n_s = clamp(rows[s], 0, Tc) live FRAMES of slot s (rows == NULL: n_s = Tc for every slot);
+ *   nothing at or after frame n_s of a slot's inputs is loaded (such frames may hold NaN), nothing at or after it is written;
+ *   a slot with n_s == 0 has its state copied bit for bit.
+ * fp32 arithmetic in both precision modes; no alignment rules beyond the 8 bytes of the state.
+ *
+ * kantts_nsf_source_rows: frame-level f0 (Hz) and voicing -> the projected excitation, SourceModule.forward_cl in one launch.
+ * Sample j of frame k of slot s (sample k * hop + j of the call, absolute sample n = cursor + k * hop + j of the utterance):
+ *   inc_k[h]   = round(frac((h + 1) * f0[s, k] / sr) * 2^32)            (fp64, then a wrapping uint32)
+ *   P_0        = state_in.phase,   P_{k+1} = P_k + hop * inc_k          (uint32, wrap-around == the reference's `% 1`)
+ *   theta      = 2 pi * (int32)(P_k[h] + (j + 1) * inc_k[h]) / 2^32     (a signed fraction of a cycle: [-pi, pi))
+ *   x_h        = uv[s, k] * (alpha * sin(theta + phase0[h]) + z_h) + (1 - uv[s, k]) * (alpha / 3 / sigma) * z_h
+ *   e[s, k * hop + j] = tanh(bias[0] + sum_h w[h] * x_h),               h in [0, H1), H1 = nb_harmonics + 1
+ *   z_h        = noise[s, k * hop + j, h] when noise != NULL (used as it is: the caller's N(0, sigma) draws), else
+ *                sigma * N(0, 1) by Box-Muller on the 64-bit hash of common.h keyed by (state.key, 8 * n + h / 2): one hash
+ *                gives the pair (cos, sin) for harmonics 2i and 2i + 1.  Same key and same n: same bits, whatever the chunking.
+ *   harm[s, k * hop + j, h] = x_h when harm != NULL (the excitation before its projection).
+ * Frame indexing is exact (sample n belongs to frame n / hop): the float-scale rounding of
+ * torch.nn.functional.interpolate(mode="nearest"), which can pick the neighbouring frame at a frame boundary when hop is no
+ * power of two, is NOT reproduced.
+ * State: KANTTS_NSF_STATE_WORDS 32-bit words per slot, slot s at base + s * state_ss words, two DIFFERENT buffers
+ * (ping-pong; state_out is written by extra workgroups of the same launch):
+ *   words  0..15  uint32 phase[16]    running phase per harmonic, 2^32 = one cycle
+ *   words 16..31  float  phase0[16]   initial phase per harmonic (the reference has phase0[0] == 0)
+ *   words 32..33  uint64 cursor       absolute sample index of the slot's utterance
+ *   words 34..35  uint64 key          noise key
+ *   state_out = {P_{n_s}, phase0, cursor + n_s * hop, key}.
+ *   f0, uv (S, Tc); noise, harm (S, Tc * hop, H1); w (H1); bias (1) or NULL; e (S, Tc * hop): fp32, dense.
+ * KANTTS_E_BADARG: a NULL required pointer (f0, uv, w, state_in, state_out, e), state_in == state_out, Tc < 1, hop < 1,
+ * H1 < 1, sr <= 0, sigma <= 0, state_ss < KANTTS_NSF_STATE_WORDS with S > 1.  KANTTS_E_UNSUPPORTED: H1 > 16, a state that is
+ * not 8-byte aligned or an odd state_ss, S * Tc * hop >= 2^31.  S <= 0: nothing is launched, KANTTS_OK. */
+#define KANTTS_NSF_STATE_WORDS 36
+typedef struct {
+  const float* f0;
+  const float* uv;
+  const float* noise;
+  const float* w;
+  const float* bias;
+  const int32_t* state_in;
+  int32_t* state_out;
+  float* e;
+  float* harm;
+  const int32_t* rows;
+  long long state_ss;
+  int S, Tc, hop, H1;
+  float sr, alpha, sigma;
+} kantts_nsf_source_args;
+int kantts_nsf_source_rows(const kantts_nsf_source_args* args, void* stream);
+
+/* kantts_nsf_downs_rows: all source_downs convolutions of a generator in one launch.  Stage i (i < nstages <= 8) has stride
+ * u[i] (a divisor of hop), k[i] taps and C[i] output channels:
+ *   d_i[s, q, c]   = bias_i[c] + sum_j w_i[j][c] * E[s, q * u[i] - (k[i] - 1) + j],     q in [0, n_s * hop / u[i])
+ *   E[s, t]        = e[s, t]                 for t >= 0
+ *                  = hist_in[s, Hh + t]      for -Hh <= t < 0,    Hh = max_i (k[i] - 1)
+ *   hist_out[s, h] = E[s, n_s * hop - Hh + h]   for h in [0, Hh)  (the last Hh samples of [hist_in[s] ; e[s, 0 : n_s * hop]];
+ *                    n_s == 0: a copy of hist_in[s])
+ * A torch Conv1d weight (C, 1, k) left-padded by k - 1 is w_i[j][c] = W[c, 0, j].  The generator's stages have
+ * u[i] = hop / prod(scales[:i+1]), k[i] = 2 * u[i] (the last, u = 1: k = 1, the 1x1 convolution), so Hh = 2 * u[0] - 1 < hop;
+ * zero history == the reference's zero left pad.
+ *   e (S, Tc * hop); w_i (k[i], C[i]) tap-major; bias_i (C[i]) or NULL; out_i (S, Tc * hop / u[i], C[i]) -- byte for byte the
+ *   (S, rows, scale * Cout) `res` of the polyphase up-layer that adds it; hist_in / hist_out: slot s at base + s * hist_ss
+ *   floats, two DIFFERENT buffers (NULL allowed when Hh == 0).  All fp32, dense.
+ * KANTTS_E_BADARG: e == NULL, Tc < 1, hop < 1, nstages < 1, a stage with a NULL w / out or u, k, C < 1, missing or equal
+ * history buffers with Hh > 0, hist_ss < Hh with S > 1.  KANTTS_E_UNSUPPORTED: nstages > 8, a stage whose u does not divide
+ * hop, k[i] > 8192 (the window of a one-row tile must fit its LDS buffer).  S <= 0: nothing is launched. */
+typedef struct {
+  const float* e;
+  const float* hist_in;
+  float* hist_out;
+  const int32_t* rows;
+  const float* w[8];
+  const float* bias[8];
+  float* out[8];
+  long long hist_ss;
+  int S, Tc, hop, nstages;
+  int u[8];
+  int k[8];
+  int C[8];
+} kantts_nsf_downs_args;
+int kantts_nsf_downs_rows(const kantts_nsf_downs_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

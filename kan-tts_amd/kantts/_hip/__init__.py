@@ -115,6 +115,30 @@ class SConvRowsArgs(Structure):
     _fields_ = SConvArgs._fields_ + [("rows", c_void_p), ("row_mul", c_int32), ("zero_tail", c_int32)]
 
 
+NSF_STATE_WORDS = 36  # KANTTS_NSF_STATE_WORDS: phase[16] u32, phase0[16] f32, cursor u64, key u64
+NSF_MAX_H1, NSF_MAX_STAGES, NSF_MAX_K = 16, 8, 8192
+
+
+class NsfSourceArgs(Structure):
+    """kantts_nsf_source_args (include/kantts_hip.h)."""
+    _fields_ = [
+        ("f0", c_void_p), ("uv", c_void_p), ("noise", c_void_p), ("w", c_void_p), ("bias", c_void_p),
+        ("state_in", c_void_p), ("state_out", c_void_p), ("e", c_void_p), ("harm", c_void_p), ("rows", c_void_p),
+        ("state_ss", c_longlong), ("S", c_int32), ("Tc", c_int32), ("hop", c_int32), ("H1", c_int32),
+        ("sr", c_float), ("alpha", c_float), ("sigma", c_float),
+    ]
+
+
+class NsfDownsArgs(Structure):
+    """kantts_nsf_downs_args (include/kantts_hip.h)."""
+    _fields_ = [
+        ("e", c_void_p), ("hist_in", c_void_p), ("hist_out", c_void_p), ("rows", c_void_p),
+        ("w", c_void_p * 8), ("bias", c_void_p * 8), ("out", c_void_p * 8), ("hist_ss", c_longlong),
+        ("S", c_int32), ("Tc", c_int32), ("hop", c_int32), ("nstages", c_int32),
+        ("u", c_int32 * 8), ("k", c_int32 * 8), ("C", c_int32 * 8),
+    ]
+
+
 class CConvArgs(Structure):
     """kantts_cconv_args (include/kantts_hip.h); ``in_`` is the C field ``in``."""
     _fields_ = [
@@ -460,6 +484,8 @@ def lib():
         L.kantts_lstm_fwd_slots.argtypes = [p, p, p, p, p, p, p, i, i, i, p, p, i, p]
         L.kantts_fsmn_dwconv_fwd_slots.argtypes = [p, p, p, p, p, i, i, i, i, i, p, p, i, p]
         L.kantts_scatter_rows_f32.argtypes = [p, p, p, p, p, i, i, i, p]
+        L.kantts_nsf_source_rows.argtypes = [POINTER(NsfSourceArgs), c_void_p]
+        L.kantts_nsf_downs_rows.argtypes = [POINTER(NsfDownsArgs), c_void_p]
         _lib = L
     return _lib
 
@@ -486,6 +512,7 @@ EXPORTED_SYMBOLS = [
     "kantts_launch_tuning", "kantts_sconv_launch", "kantts_sconv_rows_launch",
     "kantts_pnca_decode_range", "kantts_lstm_fwd_range", "kantts_fsmn_dwconv_fwd_rows",
     "kantts_pnca_decode_slots", "kantts_lstm_fwd_slots", "kantts_fsmn_dwconv_fwd_slots", "kantts_scatter_rows_f32",
+    "kantts_nsf_source_rows", "kantts_nsf_downs_rows",
 ]
 
 
@@ -1367,6 +1394,55 @@ def sconv(x, hist_in, hist_out, w, out, *, S, Tc, Cin, N, K, step, hist_ss, prec
     if rc == E_UNSUPPORTED:
         return False
     check(rc, "sconv")
+    return True
+
+
+def nsf_source(f0, uv, state_in, state_out, w, e, *, S, Tc, hop, H1, sr, alpha, sigma, state_ss=NSF_STATE_WORDS, bias=None,
+               noise=None, harm=None, rows=None):
+    """The chunked NSF sine source (csrc/nsf_source.hip, kantts_nsf_source_rows; the rule is written out in
+    include/kantts_hip.h).  f0, uv (S, Tc) fp32; state_in / state_out: int32 tensors whose first element is slot 0's state,
+    ``state_ss`` words between slots; w (H1) and bias (1) fp32; e (S, Tc * hop) fp32.  ``noise`` (S, Tc * hop, H1): used as
+    given (None: generated from the slot's key); ``harm``: optional output of the same shape, the excitation before its
+    projection; ``rows``: int32 device tensor of S per-slot frame counts (None: every slot advances by Tc).  Returns False
+    when the kernel declines the shape."""
+    g = NsfSourceArgs()
+    g.f0, g.uv, g.noise = ptr(f0, torch.float32), ptr(uv, torch.float32), ptr(noise, torch.float32)
+    g.w, g.bias = ptr(w, torch.float32), ptr(bias, torch.float32)
+    g.state_in, g.state_out = ptr(state_in, torch.int32), ptr(state_out, torch.int32)
+    g.e, g.harm, g.rows = ptr(e, torch.float32), ptr(harm, torch.float32), ptr(rows, torch.int32)
+    g.state_ss, g.S, g.Tc, g.hop, g.H1 = int(state_ss), int(S), int(Tc), int(hop), int(H1)
+    g.sr, g.alpha, g.sigma = float(sr), float(alpha), float(sigma)
+    if rows is not None and rows.numel() != int(S):
+        raise ValueError("rows must hold S = %d counts, got %d" % (int(S), rows.numel()))
+    rc = lib().kantts_nsf_source_rows(ctypes.byref(g), stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "nsf_source")
+    return True
+
+
+def nsf_downs(e, hist_in, hist_out, stages, outs, *, S, Tc, hop, hist_ss, rows=None):
+    """Every excitation down-convolution of a generator in one launch (csrc/nsf_source.hip, kantts_nsf_downs_rows).
+    e (S, Tc * hop) fp32; ``stages``: a list of (u, k, C, w (k, C) fp32, bias (C) fp32 or None); ``outs``: one fp32 tensor
+    (S, Tc * hop / u, C) per stage; hist_in / hist_out: fp32 tensors whose first element is slot 0's history
+    (max k - 1 samples), ``hist_ss`` floats between slots.  Returns False when the kernel declines the shape."""
+    g = NsfDownsArgs()
+    g.e, g.hist_in, g.hist_out = ptr(e, torch.float32), ptr(hist_in, torch.float32), ptr(hist_out, torch.float32)
+    g.rows = ptr(rows, torch.int32)
+    g.hist_ss, g.S, g.Tc, g.hop, g.nstages = int(hist_ss), int(S), int(Tc), int(hop), len(stages)
+    if len(stages) != len(outs):
+        raise ValueError("one output per stage")
+    if len(stages) > NSF_MAX_STAGES:
+        return False
+    for i, ((u, k, C, w, b), o) in enumerate(zip(stages, outs)):
+        g.u[i], g.k[i], g.C[i] = int(u), int(k), int(C)
+        g.w[i], g.bias[i], g.out[i] = ptr(w, torch.float32), ptr(b, torch.float32), ptr(o, torch.float32)
+    if rows is not None and rows.numel() != int(S):
+        raise ValueError("rows must hold S = %d counts, got %d" % (int(S), rows.numel()))
+    rc = lib().kantts_nsf_downs_rows(ctypes.byref(g), stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "nsf_downs")
     return True
 
 

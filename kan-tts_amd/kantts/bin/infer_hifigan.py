@@ -7,9 +7,11 @@ dependency here).  NSF generators take (T, C + 2) features whose last column (vo
 the reference (:52-63, :112-113); multi-band (PQMF) generators are refused.
 
 ``--chunk_frames N``: the same outputs produced chunk by chunk through kantts.models.hifigan.chunked.ChunkedVocoder
-(carried convolution state; causal single-band generators without NSF), with the time to the first chunk logged beside
+(carried convolution state; causal single-band generators), with the time to the first chunk logged beside
 the RTF.  Absent: the whole-utterance path, unchanged.  ``--slots S`` (with ``--chunk_frames``): S utterances at a time,
 each slot taking the next file as soon as its utterance ends (``ChunkedVocoder.play_many``); the same files are written.
+NSF generators play through kantts.models.hifigan.chunked_nsf.ChunkedNSFVocoder (a streamed sine excitation): utterance i
+of the sorted input list gets the noise and initial phases of ``(--seed, i)``, whatever the chunk size and the slots.
 """
 import argparse
 import glob
@@ -77,12 +79,21 @@ def _load_feats(model, path, device):
     return torch.from_numpy(np.ascontiguousarray(feats)).float().to(device)
 
 
-def _infer_many(model, mel_lst, output_dir, sr, chunk_frames, slots, device):
-    """The directory through ``slots`` vocoder slots with continuous batching; an utterance's file is written when its last
-    chunk has arrived."""
+def _chunked_vocoder(model, slots, device, seed):
+    """The chunked player of ``model``; either class refuses what it cannot play, loudly."""
+    if model.nsf_enable:
+        from kantts.models.hifigan.chunked_nsf import ChunkedNSFVocoder
+
+        return ChunkedNSFVocoder(model, slots=slots, graph=device.type == "cuda", seed=seed)
     from kantts.models.hifigan.chunked import ChunkedVocoder
 
-    vocoder = ChunkedVocoder(model, slots=slots, graph=device.type == "cuda")  # refuses what it cannot play, loudly
+    return ChunkedVocoder(model, slots=slots, graph=device.type == "cuda")
+
+
+def _infer_many(model, mel_lst, output_dir, sr, chunk_frames, slots, device, seed=0):
+    """The directory through ``slots`` vocoder slots with continuous batching; an utterance's file is written when its last
+    chunk has arrived."""
+    vocoder = _chunked_vocoder(model, slots, device, seed)
     pcm_len = 0
     with torch.no_grad():
         start = time.time()
@@ -101,7 +112,7 @@ def _infer_many(model, mel_lst, output_dir, sr, chunk_frames, slots, device):
     return rtf
 
 
-def hifigan_infer(input_mel, ckpt_path, output_dir, config=None, chunk_frames=None, slots=1):
+def hifigan_infer(input_mel, ckpt_path, output_dir, config=None, chunk_frames=None, slots=1, seed=0):
     slots = int(slots)
     if slots < 1:
         raise ValueError("slots must be >= 1")
@@ -122,16 +133,14 @@ def hifigan_infer(input_mel, ckpt_path, output_dir, config=None, chunk_frames=No
     model = model.eval().to(device)
     sr = config["audio_config"]["sampling_rate"]
     if slots > 1:
-        return _infer_many(model, mel_lst, output_dir, sr, chunk_frames, slots, device)
+        return _infer_many(model, mel_lst, output_dir, sr, chunk_frames, slots, device, seed)
     pcm_len = 0
     vocoder, first_chunk = None, []
     if chunk_frames is not None:
-        from kantts.models.hifigan.chunked import ChunkedVocoder
-
-        vocoder = ChunkedVocoder(model, slots=1, graph=device.type == "cuda")  # refuses what it cannot play, loudly
+        vocoder = _chunked_vocoder(model, 1, device, seed)
     with torch.no_grad():
         start = time.time()
-        for mel in mel_lst:
+        for index, mel in enumerate(mel_lst):
             utt_id = os.path.splitext(os.path.basename(mel))[0]
             feats = np.load(mel)
             if model.nsf_enable:
@@ -139,7 +148,8 @@ def hifigan_infer(input_mel, ckpt_path, output_dir, config=None, chunk_frames=No
             mel_data = torch.from_numpy(np.ascontiguousarray(feats)).float().to(device)
             if vocoder is not None:
                 t0, parts = time.time(), []
-                for wav in vocoder.synthesize(mel_data.transpose(1, 0), chunk_frames=chunk_frames):
+                key = {"key": index} if model.nsf_enable else {}  # the utterance's excitation, as play_many names it
+                for wav in vocoder.synthesize(mel_data.transpose(1, 0), chunk_frames=chunk_frames, **key):
                     parts.append(wav.reshape(-1).cpu())  # the copy to the host is when a chunk can be played
                     if len(parts) == 1:
                         first_chunk.append(time.time() - t0)
@@ -173,11 +183,13 @@ def main(argv=None):
                         help="Generate chunk by chunk, this many mel frames at a time (carried convolution state)")
     parser.add_argument("--slots", type=int, default=1,
                         help="With --chunk_frames: play this many utterances at a time (continuous batching)")
+    parser.add_argument("--seed", type=int, default=0,
+                        help="With --chunk_frames on an NSF generator: seed of the excitation's noise and initial phases")
     args = parser.parse_args(argv)
     if args.slots < 1 or (args.slots > 1 and args.chunk_frames is None):
         parser.error("--slots needs --chunk_frames and a value >= 1")
     return hifigan_infer(args.input_mel, args.ckpt, args.output_dir, args.config, chunk_frames=args.chunk_frames,
-                         slots=args.slots)
+                         slots=args.slots, seed=args.seed)
 
 
 if __name__ == "__main__":

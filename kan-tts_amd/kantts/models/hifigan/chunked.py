@@ -68,14 +68,17 @@ class ChunkedVocoder:
     new capture (``captures`` counts the captures of the object).
 
     Refused at construction: non-causal generators, NSF generators (the excitation's running phase and random draws need
-    a carried state of their own), ``out_channels > 1`` (PQMF synthesis), and channel counts / kernel sizes the kernel
-    declines (Cin a multiple of 8 in 16..512, k <= 11, dilation <= 7, upsampling N = scale * Cout <= 4096)."""
+    a carried state of their own: kantts.models.hifigan.chunked_nsf.ChunkedNSFVocoder plays them), ``out_channels > 1``
+    (PQMF synthesis), and channel counts / kernel sizes the kernel declines (Cin a multiple of 8 in 16..512, k <= 11,
+    dilation <= 7, upsampling N = scale * Cout <= 4096)."""
+
+    _plays_nsf = False  # kantts.models.hifigan.chunked_nsf.ChunkedNSFVocoder carries the excitation's state
 
     def __init__(self, generator, slots=1, graph=True, max_graphs=8):
         g = generator
         if not getattr(g, "causal", False):
             raise ValueError("ChunkedVocoder needs a causal generator (causal=True): a symmetric convolution looks ahead")
-        if g.nsf_enable:
+        if g.nsf_enable and not self._plays_nsf:
             raise NotImplementedError("ChunkedVocoder: NSF generators are not supported (the source module's running phase "
                                       "and random draws need a carried state of their own)")
         if g.out_channels != 1:
@@ -150,6 +153,8 @@ class ChunkedVocoder:
             L.off = off
             off += L.H * L.Cin  # Cin % 8 == 0: every layer's state starts on a 16-byte boundary
         self.state_floats = off
+        self._step_channels = self.in_channels  # channels of what ``step`` takes
+        self._plan_extra(g)
 
         # ---- snapshot of the weights
         self.device = next(g.parameters()).device
@@ -191,6 +196,19 @@ class ChunkedVocoder:
         self.captures = 0
 
     # ------------------------------------------------------------------------------------------------------------
+    # hooks of ChunkedNSFVocoder; here they do nothing and the launches of a step are the ones of _run alone
+    def _plan_extra(self, g):
+        """Further refusals, decided from shapes before anything is packed."""
+
+    def _assign(self, slot, index):
+        """``play_many``: ``slot`` (just reset) takes utterance ``index``."""
+
+    def _save_state(self):
+        return self.arena.clone()
+
+    def _restore_state(self, saved):
+        self.arena.copy_(saved)
+
     def reset(self, slot=None):
         """Zero state for one slot (others untouched) or for all: one fill launch."""
         if slot is None:
@@ -214,16 +232,18 @@ class ChunkedVocoder:
             raise RuntimeError("kantts_sconv_launch declined layer %s it was planned for" % L.name)
         return out
 
-    def _run(self, mel, parity, rows=None):
+    def _run(self, mel, parity, rows=None, stage_res=None):
         """The launches of one step: mel (S, C, Tc) fp32 -> wav (S, 1, Tc * hop).  Reads arena[parity], writes
         arena[1 - parity].  ``rows``: the int32 device buffer of per-slot frame counts (every layer passes its own rows
-        per frame; the element-wise launches run over the whole buffers -- what they do to dead rows is never read)."""
+        per frame; the element-wise launches run over the whole buffers -- what they do to dead rows is never read).
+        ``stage_res``: one (S, rows, Cout) tensor per stage, added by the stage's up-layer launch (the NSF excitation)."""
         with torch.no_grad():
             mul = 1  # rows of the current layer per mel frame
             h = self._conv(self.pre, mel.transpose(1, 2).contiguous(), parity, rows=rows, row_mul=mul)
-            for s, Cout, upl, stacks in self.stages:
+            for i, (s, Cout, upl, stacks) in enumerate(self.stages):
                 h = ops.sin_add(h)
-                h = self._conv(upl, h, parity, rows=rows, row_mul=mul).view(h.shape[0], h.shape[1] * s, Cout)
+                res = None if stage_res is None else stage_res[i]
+                h = self._conv(upl, h, parity, res=res, rows=rows, row_mul=mul).view(h.shape[0], h.shape[1] * s, Cout)
                 mul *= s
                 ys = []
                 for pairs in stacks:  # sequential, as Generator._residual_stacks runs them under no_grad
@@ -243,10 +263,10 @@ class ChunkedVocoder:
         if ent is None:
             if len(self._graphs) >= self._max_graphs:
                 self._graphs.pop(next(iter(self._graphs)))  # least recently used
-            mel = torch.zeros(self.slots, self.in_channels, Tc, device=self.device, dtype=torch.float32)
+            mel = torch.zeros(self.slots, self._step_channels, Tc, device=self.device, dtype=torch.float32)
             # eager warm-up of both parities on a side stream (kernels loaded, allocator primed); the state it advances
             # is put back afterwards
-            saved = self.arena.clone()
+            saved = self._save_state()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -260,7 +280,7 @@ class ChunkedVocoder:
                 with torch.cuda.graph(gr, capture_error_mode="thread_local"):
                     outs.append(self._run(mel, p, rows))
                 graphs.append(gr)
-            self.arena.copy_(saved)
+            self._restore_state(saved)
             self.captures += 1
             ent = (mel, graphs, outs)
         self._graphs[key] = ent
@@ -295,8 +315,8 @@ class ChunkedVocoder:
         device; device values are clamped by the kernel, not read back).  Slot ``s`` advances by ``rows[s]`` frames: frames
         of ``mel`` at and after ``rows[s]`` are not read (they may hold anything), samples of ``wav`` at and after
         ``rows[s] * hop`` are 0.0, and a slot with ``rows[s] == 0`` keeps its state bit for bit."""
-        if mel.dim() != 3 or mel.shape[0] != self.slots or mel.shape[1] != self.in_channels or mel.shape[2] < 1:
-            raise ValueError("mel must be (slots=%d, %d, Tc >= 1), got %s" % (self.slots, self.in_channels, tuple(mel.shape)))
+        if mel.dim() != 3 or mel.shape[0] != self.slots or mel.shape[1] != self._step_channels or mel.shape[2] < 1:
+            raise ValueError("mel must be (slots=%d, %d, Tc >= 1), got %s" % (self.slots, self._step_channels, tuple(mel.shape)))
         Tc = int(mel.shape[2])
         if rows is not None:
             self._set_rows(rows, Tc)
@@ -322,9 +342,12 @@ class ChunkedVocoder:
         if n < 1:
             raise ValueError("chunk_frames must be >= 1")
         self.reset(slot)
+        yield from self._play_one(mel_full, T, n, slot)
+
+    def _play_one(self, mel_full, T, n, slot):
         for t0 in range(0, T, n):
             t1 = min(T, t0 + n)
-            mel = torch.zeros(self.slots, self.in_channels, n, device=self.device, dtype=torch.float32)
+            mel = torch.zeros(self.slots, self._step_channels, n, device=self.device, dtype=torch.float32)
             mel[slot, :, :t1 - t0] = mel_full[:, t0:t1]
             yield self.step(mel)[slot, :, :(t1 - t0) * self.hop]
 
@@ -341,15 +364,16 @@ class ChunkedVocoder:
             raise ValueError("chunk_frames must be >= 1")
         mels = list(mels)
         for i, m in enumerate(mels):
-            if m.dim() != 2 or m.shape[0] != self.in_channels or m.shape[1] < 1:
-                raise ValueError("mels[%d] must be (%d, T >= 1), got %s" % (i, self.in_channels, tuple(m.shape)))
+            if m.dim() != 2 or m.shape[0] != self._step_channels or m.shape[1] < 1:
+                raise ValueError("mels[%d] must be (%d, T >= 1), got %s" % (i, self._step_channels, tuple(m.shape)))
         self.reset()
         cur, pos, nxt = [None] * self.slots, [0] * self.slots, 0
-        buf = torch.zeros(self.slots, self.in_channels, n, device=self.device, dtype=torch.float32)
+        buf = torch.zeros(self.slots, self._step_channels, n, device=self.device, dtype=torch.float32)
         while True:
             for s in range(self.slots):
                 if cur[s] is None and nxt < len(mels):
                     cur[s], pos[s], nxt = nxt, 0, nxt + 1
+                    self._assign(s, cur[s])
             if all(c is None for c in cur):
                 return
             counts = [0] * self.slots

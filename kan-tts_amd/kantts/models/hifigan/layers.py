@@ -225,10 +225,26 @@ class SourceModule(torch.nn.Module):
 
     @torch.no_grad()
     def excitation(self, pitch, uv):
-        """pitch (Hz), uv: (B, 1, frames) -> e (B, H+1, frames * upsample_ratio)."""
+        """pitch (Hz), uv: (B, 1, frames) -> e (B, H+1, frames * upsample_ratio).  Draws the initial phases and the noise
+        (one Uniform and one Normal call per utterance batch) and hands them to ``excitation_from``."""
         import numpy as np
         from torch.distributions.normal import Normal
         from torch.distributions.uniform import Uniform
+
+        dev = pitch.device
+        samples = int(pitch.size(-1) * int(self.upsample_ratio))
+        one = torch.ones((), device=dev)
+        phase_vec = Uniform(low=-np.pi * one, high=np.pi * one).sample(sample_shape=(pitch.size(0), self.nb_harmonics + 1, 1))
+        phase_vec[:, 0, :] = 0
+        noise = Normal(loc=0.0 * one, scale=self.sigma * one).sample(
+            sample_shape=(pitch.size(0), self.nb_harmonics + 1, samples))
+        return self.excitation_from(pitch, uv, phase_vec, noise)
+
+    @torch.no_grad()
+    def excitation_from(self, pitch, uv, phase_vec, noise):
+        """The arithmetic of the excitation for GIVEN draws, in the dtype of its inputs: pitch (Hz), uv (B, 1, frames),
+        phase_vec (B, H+1, 1) initial phases, noise (B, H+1, frames * upsample_ratio) -> e of the shape of ``noise``."""
+        import numpy as np
 
         up = int(self.upsample_ratio)
         dev = pitch.device
@@ -238,11 +254,6 @@ class SourceModule(torch.nn.Module):
         harm = torch.arange(1, self.nb_harmonics + 2, device=dev, dtype=pitch.dtype).view(1, -1, 1)
         F_mat = pitch_samples * harm / self.sampling_rate
         theta_mat = 2 * np.pi * (torch.cumsum(F_mat, dim=-1) % 1)
-        one = torch.ones((), device=dev)
-        phase_vec = Uniform(low=-np.pi * one, high=np.pi * one).sample(sample_shape=(pitch.size(0), self.nb_harmonics + 1, 1))
-        phase_vec[:, 0, :] = 0
-        noise = Normal(loc=0.0 * one, scale=self.sigma * one).sample(
-            sample_shape=(pitch_samples.size(0), self.nb_harmonics + 1, pitch_samples.size(-1)))
         e_voice = self.alpha * torch.sin(theta_mat + phase_vec) + noise
         e_unvoice = self.alpha / 3 / self.sigma * noise
         return e_voice * uv_samples + e_unvoice * (1 - uv_samples)
