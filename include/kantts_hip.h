@@ -1106,6 +1106,22 @@ int kantts_ragged_rows_i64(const int64_t* src, const int64_t* row_off, const int
 int kantts_scatter_rows_f32(const float* in, const int64_t* row_off, const int32_t* start, const int32_t* len, float* dst,
                             int B, int Tmax, int C, void* stream);
 
+/* The hand-over from the acoustic slot pool to the chunked vocoder (csrc/handover.hip): final post-net rows of every slot,
+ * channels-last, become the vocoder's step input, channels-first, in one launch.
+ *   src (S, T, C) fp32 (row stride C, slot stride T * C); start, rows (S) int32 on the device; out (S, C, Tc) fp32
+ *   start_s = clamp(start[s], 0, T);  n_s = clamp(rows[s], 0, min(Tc, T - start_s))
+ *   out[s][c][t] = t < n_s ? f_c(src[s][start_s + t][c]) : 0.0f
+ * Nothing outside a slot's clamped window is read, every element of out is written, start / rows are not read back.
+ * f_c is the identity; with nsf != 0 the last two channels (normalised f0 and a voicing score behind the mel bins) become
+ * what the vocoder's source module takes, as denorm_f0 of kantts/bin/infer_sambert.py computes them:
+ *   c == C - 2:  fmaxf(v * scale + offset, f0_floor)      product and sum rounded separately (no fused multiply-add)
+ *   c == C - 1:  v < uv_threshold ? 0.0f : 1.0f
+ * 16-byte loads when C % 4 == 0 and src is 16-byte aligned.
+ * KANTTS_E_BADARG: src, start, rows or out NULL, S < 0, Tc < 0, T < 1, C < 1, nsf with C < 3.  S == 0 or Tc == 0: no-op.
+ * KANTTS_E_UNSUPPORTED: S > 65535. */
+int kantts_mel_handover_rows(const float* src, const int32_t* start, const int32_t* rows, float* out, int S, int T, int C,
+                             int Tc, int nsf, float scale, float offset, float f0_floor, float uv_threshold, void* stream);
+
 /* Launch-shape knobs for sweeps and tests -- they never change a result.  tn_tile: output tile of kantts_bgemm_tn* as
  * BN * 1000 + BK (64128 / 128128 / 64256 / 128256; anything else = the library's rule; the code + 1, e.g. 64129, selects
  * that tile WITHOUT the XCD-aware workgroup mapping of round 6 -- the 3-D grid of rounds 2-5, for A/B runs); tn_slices: token slices of the

@@ -486,6 +486,7 @@ def lib():
         L.kantts_scatter_rows_f32.argtypes = [p, p, p, p, p, i, i, i, p]
         L.kantts_nsf_source_rows.argtypes = [POINTER(NsfSourceArgs), c_void_p]
         L.kantts_nsf_downs_rows.argtypes = [POINTER(NsfDownsArgs), c_void_p]
+        L.kantts_mel_handover_rows.argtypes = [p, p, p, p, i, i, i, i, i, f, f, f, f, p]
         _lib = L
     return _lib
 
@@ -512,7 +513,7 @@ EXPORTED_SYMBOLS = [
     "kantts_launch_tuning", "kantts_sconv_launch", "kantts_sconv_rows_launch",
     "kantts_pnca_decode_range", "kantts_lstm_fwd_range", "kantts_fsmn_dwconv_fwd_rows",
     "kantts_pnca_decode_slots", "kantts_lstm_fwd_slots", "kantts_fsmn_dwconv_fwd_slots", "kantts_scatter_rows_f32",
-    "kantts_nsf_source_rows", "kantts_nsf_downs_rows",
+    "kantts_nsf_source_rows", "kantts_nsf_downs_rows", "kantts_mel_handover_rows",
 ]
 
 
@@ -1003,6 +1004,27 @@ def slot_entry_points():
     L = lib()
     return all(hasattr(L, n) for n in ("kantts_pnca_decode_slots", "kantts_lstm_fwd_slots", "kantts_fsmn_dwconv_fwd_slots",
                                        "kantts_scatter_rows_f32"))
+
+
+def handover_entry_points():
+    """True when the loaded library exports the hand-over entry point of StreamingTTS."""
+    return hasattr(lib(), "kantts_mel_handover_rows")
+
+
+def mel_handover(src, start, rows, out, *, nsf=None, f0_floor=30.0, uv_threshold=0.6):
+    """Acoustic slots -> vocoder step input in one launch (csrc/handover.hip): src (S, T, C) fp32 channels-last, start and
+    rows (S) int32 device tensors (clamped by the kernel, not read back), out (S, C, Tc) fp32:
+    out[s, :, t] = src[s, start[s] + t] for t < rows[s], else 0.  ``nsf=(scale, offset)``: the last two channels become f0 in
+    Hz (floored at ``f0_floor``) and a 0 / 1 voicing flag (at ``uv_threshold``), as ``infer_sambert.denorm_f0`` computes
+    them.  Returns the status code."""
+    S, T, C = src.shape
+    assert src.is_contiguous() and out.is_contiguous() and int(out.shape[0]) == int(S) and int(out.shape[1]) == int(C)
+    assert int(start.numel()) == int(S) and int(rows.numel()) == int(S)
+    scale, offset = (0.0, 0.0) if nsf is None else nsf
+    return lib().kantts_mel_handover_rows(ptr(src, torch.float32), ptr(start, torch.int32), ptr(rows, torch.int32),
+                                          ptr(out, torch.float32), int(S), int(T), int(C), int(out.shape[2]),
+                                          int(nsf is not None), float(scale), float(offset), float(f0_floor),
+                                          float(uv_threshold), stream())
 
 
 def lstm_fwd_slots(gx, whh, bhh, lens32, out, gates, cst, t0, t1, precision):

@@ -78,11 +78,10 @@ def denorm_f0(mel, scale, offset, f0_threshold=30.0, uv_threshold=0.6):
     return mel
 
 
-def am_infer(sentence, ckpt, output_dir, se_file=None, config=None, ling_unit=None, chunk_frames=None, slots=None,
-             slot_steps=1024):
-    """``slots`` (with ``chunk_frames``): the sentences play through a pool of that many independently advancing streaming
-    slots (AcousticSlots.play_many, buffers of ``slot_steps`` decoder steps per slot) instead of one session each; the
-    files written are the same."""
+def load_am(ckpt, se_file=None, config=None, ling_unit=None):
+    """What ``am_infer`` runs with: (device, ling_unit, se, nsf, fsnet) -- the model of ``ckpt`` in eval mode on the
+    device, the symbol tables, the speaker embedding of ``se_file`` (SE models) and, for NSF models, the (scale, offset)
+    of the f0 de-normalisation (from ``mvn.npy`` beside the config, or the global minimum and maximum)."""
     device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
     if not isinstance(config, dict):
         path = config if config is not None else os.path.join(os.path.dirname(os.path.dirname(ckpt)), "config.yaml")
@@ -114,13 +113,22 @@ def am_infer(sentence, ckpt, output_dir, se_file=None, config=None, ling_unit=No
     fsnet = model["KanTtsSAMBERT"]
     logging.info("Loading checkpoint: %s", ckpt)
     fsnet.load_state_dict(torch.load(ckpt, map_location="cpu")["model"], strict=False)
-    results_dir = os.path.join(output_dir, "feat")
-    os.makedirs(results_dir, exist_ok=True)
     fsnet.eval()
     if device.type == "cuda":
         # bf16 mode: each autoregressive loop is one launch (kantts/models/sambert/ar_kernels.py); otherwise one decoder
         # step = one hipGraph replay (kantts/models/sambert/decode_graph.py)
         fsnet.mel_decoder.decode_mode = "kernel"
+    return device, ling_unit, se, nsf, fsnet
+
+
+def am_infer(sentence, ckpt, output_dir, se_file=None, config=None, ling_unit=None, chunk_frames=None, slots=None,
+             slot_steps=1024):
+    """``slots`` (with ``chunk_frames``): the sentences play through a pool of that many independently advancing streaming
+    slots (AcousticSlots.play_many, buffers of ``slot_steps`` decoder steps per slot) instead of one session each; the
+    files written are the same."""
+    device, ling_unit, se, nsf, fsnet = load_am(ckpt, se_file=se_file, config=config, ling_unit=ling_unit)
+    results_dir = os.path.join(output_dir, "feat")
+    os.makedirs(results_dir, exist_ok=True)
     chunked, chunk_steps, first_chunk, chunk_ms, totals = None, None, [], [], []
     if chunk_frames is not None:
         r = fsnet.mel_decoder.r
