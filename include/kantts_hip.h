@@ -1429,6 +1429,67 @@ typedef struct {
 } kantts_nsf_downs_args;
 int kantts_nsf_downs_rows(const kantts_nsf_downs_args* args, void* stream);
 
+/* ---- The tail of a MULTI-BAND generator in chunked inference (csrc/mb_tail.hip), one launch: conv_post (causal, K taps,
+ * step 1, Cin -> B sub-bands), tanh, and a PQMF synthesis that can be cut at any chunk boundary.  Per slot, driven by the
+ * same device `rows` buffer and row_mul as kantts_sconv_rows_launch:
+ *   n_s = clamp(rows[s], 0, Tq / row_mul) * row_mul live rows of slot s (rows == NULL: n_s = Tq for every slot);
+ *   last (S) int32, DEVICE memory, read the same way: last[s] != 0 ends the slot's utterance with this call (NULL: all 0).
+ * Sub-band rows (conv_post follows the rule of kantts_sconv_launch with step 1 and N = B; tap j reads j rows back):
+ *   z[s, t, k] = tanh( bias[k] + sum_j sum_c pre( X[s, t - j, c] ) * w[j][k][c] ),   t in [0, n_s)
+ *   X[s, t, c] = in[s, t, c] for t >= 0, hist_in[s, K - 1 + t, c] for -(K - 1) <= t < 0;   pre(v) = in_act ? LeakyReLU(v, in_slope) : v
+ *   w == NULL is the PASS-THROUGH form: in is (S, Tq, B) and z[s, t, k] = in[s, t, k] -- streaming PQMF.synthesis alone.
+ * Synthesis: with z the sub-band rows of the whole utterance, zero before its first row and after its last,
+ *   full[q * B + r] = sum_{d = -D .. D} sum_k poly[r, k, d + D] * z[q + d, k]
+ * (poly: the polyphase weights (B, B, 2 D + 1), D = ceil((taps / 2) / B)).  Row q looks AHEAD by D rows, so a slot holds back
+ * the rows whose future it has not seen.  State: KANTTS_MB_STATE_WORDS(D, B) 32-bit words per slot, slot s at
+ * base + s * state_ss words, two DIFFERENT buffers (ping-pong; state_out, hist_out and emitted are written by S extra
+ * workgroups of the same launch):
+ *   words 0 .. 2 D B - 1   float  the last 2 D rows of z seen so far, (2 D, B) dense, zero at the start
+ *   word  2 D B            int32  pending = min(rows of z seen so far, D): the rows held back
+ * A call with n = n_s new rows:              last == 0                       last != 0
+ *   low-rate rows emitted E                  max(0, n + pending - D)         n + pending (the future is zeros)
+ *   pending afterwards                       min(n + pending, D)             0
+ *   z state afterwards                       last 2 D rows of [state ; z]    zeros (the slot is as after a reset)
+ *   hist_out[s]                              last K - 1 rows of              zeros
+ *                                            [hist_in[s] ; in[s, 0:n]]
+ * The emitted rows are the next rows of the utterance in order: row i of the call is out[s, i * B .. i * B + B), centred on
+ * row 2 D - pending + i of [state ; z ; zeros]; out[s, E * B .. (Tq + D) * B) is written as 0.0f; emitted[s] = E * B.
+ * n == 0 with last == 0 emits nothing and copies state and history bit for bit; n == 0 with last != 0 is a flush of
+ * pending * B samples; a second flush emits nothing.  pending saturates at D: no cursor grows with the utterance.
+ * The bits of an utterance's samples do not depend on the chunking, the slot, its batch-mates or the tile: a z row is one
+ * fmaf chain, tap-major and channel-inner, wherever it is computed; a sample is one fmaf chain, d ascending and k inner;
+ * rows taken from the state are used as stored.  fp32 arithmetic in both precision modes.
+ * No row >= n_s of in is loaded: such rows may hold NaN.
+ *   in (S, Tq, Cin), w (K, B, Cin), bias (B) or NULL, poly (B, B, 2 D + 1), out (S, (Tq + D) * B), emitted (S) int32 or NULL:
+ *   dense; hist_in / hist_out: K - 1 raw rows, slot s at base + s * hist_ss floats (NULL allowed when K == 1 or w == NULL).
+ * KANTTS_E_BADARG: NULL in, poly, out, state_in or state_out, state_in == state_out, row_mul < 1, Tq % row_mul != 0, missing or
+ * equal history buffers with w != NULL and K > 1, state_ss / hist_ss smaller than a slot's state with S > 1.
+ * KANTTS_E_UNSUPPORTED unless 2 <= B <= 8, 1 <= D <= 16, 1 <= K <= 11, Cin % 4 == 0, 4 <= Cin <= 512 (Cin == B when w == NULL),
+ * in, w, hist_in, hist_out, poly, state_in, state_out and out 16-byte aligned, hist_ss % 4 == 0.
+ * S <= 0 or Tq <= 0: nothing is launched, KANTTS_OK (a flush needs Tq >= 1 and rows[s] = 0). */
+#define KANTTS_MB_STATE_WORDS(D, B) (2 * (D) * (B) + 1)
+typedef struct {
+  const float* in;
+  const float* hist_in;
+  float* hist_out;
+  const float* w;
+  const float* bias;
+  const float* poly;
+  const float* state_in;
+  float* state_out;
+  float* out;
+  int32_t* emitted;
+  const int32_t* rows;
+  const int32_t* last;
+  long long hist_ss;
+  long long state_ss;
+  int S, Tq, Cin, B, K, D;
+  int row_mul;
+  float in_slope;
+  int in_act;
+} kantts_mb_tail_args;
+int kantts_mb_tail_rows(const kantts_mb_tail_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

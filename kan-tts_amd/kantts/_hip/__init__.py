@@ -139,6 +139,25 @@ class NsfDownsArgs(Structure):
     ]
 
 
+class MbTailArgs(Structure):
+    """kantts_mb_tail_args (include/kantts_hip.h); ``in_`` is the C field ``in``."""
+    _fields_ = [
+        ("in_", c_void_p), ("hist_in", c_void_p), ("hist_out", c_void_p), ("w", c_void_p), ("bias", c_void_p),
+        ("poly", c_void_p), ("state_in", c_void_p), ("state_out", c_void_p), ("out", c_void_p), ("emitted", c_void_p),
+        ("rows", c_void_p), ("last", c_void_p), ("hist_ss", c_longlong), ("state_ss", c_longlong),
+        ("S", c_int32), ("Tq", c_int32), ("Cin", c_int32), ("B", c_int32), ("K", c_int32), ("D", c_int32),
+        ("row_mul", c_int32), ("in_slope", c_float), ("in_act", c_int32),
+    ]
+
+
+MB_MAX_B, MB_MAX_D, MB_MAX_K = 8, 16, 11  # what kantts_mb_tail_rows accepts (include/kantts_hip.h)
+
+
+def mb_state_words(D, B):
+    """KANTTS_MB_STATE_WORDS: the last 2 D sub-band rows (float) and the pending count (int32) of a slot."""
+    return 2 * int(D) * int(B) + 1
+
+
 class CConvArgs(Structure):
     """kantts_cconv_args (include/kantts_hip.h); ``in_`` is the C field ``in``."""
     _fields_ = [
@@ -487,6 +506,7 @@ def lib():
         L.kantts_nsf_source_rows.argtypes = [POINTER(NsfSourceArgs), c_void_p]
         L.kantts_nsf_downs_rows.argtypes = [POINTER(NsfDownsArgs), c_void_p]
         L.kantts_mel_handover_rows.argtypes = [p, p, p, p, i, i, i, i, i, f, f, f, f, p]
+        L.kantts_mb_tail_rows.argtypes = [POINTER(MbTailArgs), c_void_p]
         _lib = L
     return _lib
 
@@ -514,6 +534,7 @@ EXPORTED_SYMBOLS = [
     "kantts_pnca_decode_range", "kantts_lstm_fwd_range", "kantts_fsmn_dwconv_fwd_rows",
     "kantts_pnca_decode_slots", "kantts_lstm_fwd_slots", "kantts_fsmn_dwconv_fwd_slots", "kantts_scatter_rows_f32",
     "kantts_nsf_source_rows", "kantts_nsf_downs_rows", "kantts_mel_handover_rows",
+    "kantts_mb_tail_rows",
 ]
 
 
@@ -1465,6 +1486,50 @@ def nsf_downs(e, hist_in, hist_out, stages, outs, *, S, Tc, hop, hist_ss, rows=N
     if rc == E_UNSUPPORTED:
         return False
     check(rc, "nsf_downs")
+    return True
+
+
+def mb_tail_entry_points():
+    """True when the loaded library exports the multi-band tail of ChunkedMBVocoder."""
+    return hasattr(lib(), "kantts_mb_tail_rows")
+
+
+def mb_emit(pending, n, last, D):
+    """The streaming rule of kantts_mb_tail_rows on the host (the one definition: include/kantts_hip.h has the table): a
+    slot that holds back ``pending`` low-rate rows takes ``n`` new ones, ``last`` ending its utterance.
+    Returns (low-rate rows emitted, pending afterwards)."""
+    pending, n, D = int(pending), int(n), int(D)
+    if last:
+        return n + pending, 0
+    return max(0, n + pending - D), min(n + pending, D)
+
+
+def mb_tail(x, hist_in, hist_out, w, poly, state_in, state_out, out, *, S, Tq, Cin, B, K, D, hist_ss, state_ss, bias=None,
+            emitted=None, rows=None, row_mul=1, last=None, in_leaky=None):
+    """The tail of a multi-band generator in one launch (csrc/mb_tail.hip, kantts_mb_tail_rows; the rule is written out in
+    include/kantts_hip.h): conv_post, tanh and the streamed PQMF synthesis.  x (S, Tq, Cin) fp32; w (K, B, Cin) fp32 with
+    hist_in / hist_out fp32 tensors whose first element is slot 0's K - 1 history rows (``hist_ss`` floats between slots) --
+    or ``w=None``, the pass-through form: x (S, Tq, B) is the sub-band signal itself; poly (B, B, 2 D + 1) fp32;
+    state_in / state_out: fp32 tensors whose first element is slot 0's ``mb_state_words(D, B)`` words (``state_ss`` words
+    between slots; the last word is an int32); out (S, (Tq + D) * B) fp32; ``emitted`` (S) int32: samples written per slot;
+    ``rows`` / ``last``: int32 device tensors of S per-slot counts (in units of ``row_mul`` rows) and end-of-utterance flags
+    (None: every slot takes Tq rows / no slot ends).  Returns False when the kernel declines the shape."""
+    g = MbTailArgs()
+    g.in_, g.hist_in, g.hist_out = ptr(x, torch.float32), ptr(hist_in, torch.float32), ptr(hist_out, torch.float32)
+    g.w, g.bias, g.poly = ptr(w, torch.float32), ptr(bias, torch.float32), ptr(poly, torch.float32)
+    g.state_in, g.state_out = ptr(state_in, torch.float32), ptr(state_out, torch.float32)
+    g.out, g.emitted = ptr(out, torch.float32), ptr(emitted, torch.int32)
+    g.rows, g.last = ptr(rows, torch.int32), ptr(last, torch.int32)
+    g.hist_ss, g.state_ss = int(hist_ss), int(state_ss)
+    g.S, g.Tq, g.Cin, g.B, g.K, g.D = int(S), int(Tq), int(Cin), int(B), int(K), int(D)
+    g.row_mul, g.in_slope, g.in_act = int(row_mul), float(in_leaky or 0.0), int(in_leaky is not None)
+    for name, t in (("rows", rows), ("last", last), ("emitted", emitted)):
+        if t is not None and t.numel() != int(S):
+            raise ValueError("%s must hold S = %d entries, got %d" % (name, int(S), t.numel()))
+    rc = lib().kantts_mb_tail_rows(ctypes.byref(g), stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "mb_tail")
     return True
 
 

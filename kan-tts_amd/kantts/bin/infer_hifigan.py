@@ -4,14 +4,16 @@ Mirrors kantts/bin/infer_hifigan.py:34-163 of the reference (same function names
 ``states["model"]["generator"]``, ``<ckpt>/../../config.yaml`` discovery, ``<utt>_gen.wav`` outputs).  The generator
 runs on the MI355X kernels (kantts/models/hifigan); wav files are written with scipy (soundfile is not a
 dependency here).  NSF generators take (T, C + 2) features whose last column (voiced flag) is re-binarised first, as in
-the reference (:52-63, :112-113); multi-band (PQMF) generators are refused.
+the reference (:52-63, :112-113); multi-band generators are followed by their PQMF synthesis (:47-52, :120-121).
 
 ``--chunk_frames N``: the same outputs produced chunk by chunk through kantts.models.hifigan.chunked.ChunkedVocoder
-(carried convolution state; causal single-band generators), with the time to the first chunk logged beside
+(carried convolution state; causal generators), with the time to the first chunk logged beside
 the RTF.  Absent: the whole-utterance path, unchanged.  ``--slots S`` (with ``--chunk_frames``): S utterances at a time,
 each slot taking the next file as soon as its utterance ends (``ChunkedVocoder.play_many``); the same files are written.
 NSF generators play through kantts.models.hifigan.chunked_nsf.ChunkedNSFVocoder (a streamed sine excitation): utterance i
 of the sorted input list gets the noise and initial phases of ``(--seed, i)``, whatever the chunk size and the slots.
+Multi-band generators play through kantts.models.hifigan.chunked_mb.ChunkedMBVocoder (a PQMF synthesis that holds back the
+samples whose future it has not seen): the chunks have variable lengths and add up to the one-shot path's sample count.
 """
 import argparse
 import glob
@@ -85,6 +87,10 @@ def _chunked_vocoder(model, slots, device, seed):
         from kantts.models.hifigan.chunked_nsf import ChunkedNSFVocoder
 
         return ChunkedNSFVocoder(model, slots=slots, graph=device.type == "cuda", seed=seed)
+    if model.out_channels > 1:
+        from kantts.models.hifigan.chunked_mb import ChunkedMBVocoder
+
+        return ChunkedMBVocoder(model, slots=slots, graph=device.type == "cuda")
     from kantts.models.hifigan.chunked import ChunkedVocoder
 
     return ChunkedVocoder(model, slots=slots, graph=device.type == "cuda")
@@ -101,8 +107,8 @@ def _infer_many(model, mel_lst, output_dir, sr, chunk_frames, slots, device, see
         parts, got = {}, {}
         for i, wav in vocoder.play_many(mels, chunk_frames=chunk_frames):
             parts.setdefault(i, []).append(wav.reshape(-1).cpu())
-            got[i] = got.get(i, 0) + wav.shape[-1] // vocoder.hop
-            if got[i] >= mels[i].shape[1]:
+            got[i] = got.get(i, 0) + wav.shape[-1]  # in samples: the chunks of a multi-band voice are no multiples of hop
+            if got[i] >= mels[i].shape[1] * vocoder.hop:
                 y = torch.cat(parts.pop(i)).numpy()
                 pcm_len += len(y)
                 _write_wav(output_dir, os.path.splitext(os.path.basename(mel_lst[i]))[0], sr, y)

@@ -69,10 +69,11 @@ class ChunkedVocoder:
 
     Refused at construction: non-causal generators, NSF generators (the excitation's running phase and random draws need
     a carried state of their own: kantts.models.hifigan.chunked_nsf.ChunkedNSFVocoder plays them), ``out_channels > 1``
-    (PQMF synthesis), and channel counts / kernel sizes the kernel declines (Cin a multiple of 8 in 16..512, k <= 11,
+    (the PQMF synthesis looks ahead: kantts.models.hifigan.chunked_mb.ChunkedMBVocoder plays them), and channel counts / kernel sizes the kernel declines (Cin a multiple of 8 in 16..512, k <= 11,
     dilation <= 7, upsampling N = scale * Cout <= 4096)."""
 
     _plays_nsf = False  # kantts.models.hifigan.chunked_nsf.ChunkedNSFVocoder carries the excitation's state
+    _plays_multiband = False  # kantts.models.hifigan.chunked_mb.ChunkedMBVocoder runs conv_post inside the multi-band tail
 
     def __init__(self, generator, slots=1, graph=True, max_graphs=8):
         g = generator
@@ -81,7 +82,7 @@ class ChunkedVocoder:
         if g.nsf_enable and not self._plays_nsf:
             raise NotImplementedError("ChunkedVocoder: NSF generators are not supported (the source module's running phase "
                                       "and random draws need a carried state of their own)")
-        if g.out_channels != 1:
+        if g.out_channels != 1 and not self._plays_multiband:
             raise NotImplementedError("ChunkedVocoder: out_channels > 1 (multi-band / PQMF) generators are not supported")
         if g.training:
             raise ValueError("ChunkedVocoder needs generator.eval()")
@@ -143,6 +144,8 @@ class ChunkedVocoder:
                     self.layers += [c1, c2]
         self.layers.append(self.post)
         for L in self.layers:
+            if L is self.post and self._plays_multiband:
+                continue  # checked by the subclass against the contract of its own kernel (_plan_extra)
             if not sconv_supported(L.Cin, L.N, L.K, L.step):
                 raise NotImplementedError(
                     "ChunkedVocoder: layer %s (Cin %d, N %d, k %d, dilation %d) is outside what kantts_sconv_launch accepts "
@@ -165,7 +168,8 @@ class ChunkedVocoder:
 
         def pack(L, w_knc, bias):
             assert tuple(w_knc.shape) == (L.K, L.N, L.Cin), (L.name, tuple(w_knc.shape), (L.K, L.N, L.Cin))
-            L.w = w_knc.detach().to(torch.float32 if L.N == 1 else wdt).contiguous().clone()
+            fp32 = L.N == 1 or (L is self.post and self._plays_multiband)  # the last layer is fp32 in both modes
+            L.w = w_knc.detach().to(torch.float32 if fp32 else wdt).contiguous().clone()
             L.bias = None if bias is None else bias.detach().float().contiguous().clone()
 
         def pack_conv(L, m):
@@ -253,8 +257,12 @@ class ChunkedVocoder:
                                        row_mul=mul)
                     ys.append(x)
                 h = ops.mean_many(ys) if len(ys) > 1 else ys[0]
-            h = self._conv(self.post, h, parity, rows=rows, row_mul=mul, zero_tail=True)  # tanh(0) == 0: a silent tail
-            return torch.tanh(h).transpose(1, 2)
+            return self._tail(h, parity, rows, mul)
+
+    def _tail(self, h, parity, rows, mul):
+        """The last launches of a step: h (S, Tc * prod(scales), C) -> wav (S, 1, samples)."""
+        h = self._conv(self.post, h, parity, rows=rows, row_mul=mul, zero_tail=True)  # tanh(0) == 0: a silent tail
+        return torch.tanh(h).transpose(1, 2)
 
     def _captured(self, Tc, with_rows=False):
         key = ("rows", Tc) if with_rows else Tc

@@ -1,7 +1,8 @@
 """Symbols to waveform, chunk by chunk: the acoustic slot pool feeding the chunked vocoder on the device.
 
 ``AcousticSlots`` (kantts/models/sambert/slots.py) hands out FINAL post-net rows per slot; ``ChunkedVocoder.step(mel,
-rows=...)`` / ``ChunkedNSFVocoder.step(feats, rows=...)`` (kantts/models/hifigan) consume frames per slot.  ``StreamingTTS``
+rows=...)`` / ``ChunkedNSFVocoder.step(feats, rows=...)`` / ``ChunkedMBVocoder.step(mel, rows=..., last=...)``
+(kantts/models/hifigan) consume frames per slot.  ``StreamingTTS``
 pairs acoustic slot ``s`` with vocoder slot ``s`` and joins them with one launch per step (csrc/handover.hip,
 kantts_mel_handover_rows): the frames of every slot that are final but not yet vocoded go from the pool's channels-last
 ``y`` buffer into one channels-first (S, C, Tc) buffer -- for NSF voices with the f0 channel de-normalised and the voicing
@@ -16,19 +17,24 @@ A step is one acoustic step (``chunk_frames / outputs_per_step`` decoder steps f
 zero for the others) and then at most one vocoder step: slot ``s`` hands over ``min(chunk_frames, final_s - vocoded_s)``
 frames, where ``final_s`` counts live frames only (the padding up to a multiple of ``outputs_per_step`` is never vocoded).
 Its per-slot (start, count) pairs travel in ONE host-to-device copy, and a step in which no slot has a frame to hand over
-launches no vocoder step.  The post-net's look-ahead delays the first frames of an utterance, so a slot is released only
+launches no vocoder step.  A multi-band voice (``generator.out_channels > 1``) plays through ``ChunkedMBVocoder``, whose
+synthesis bank holds back up to ``D * B`` samples per slot: the same copy then also carries a flag per slot, set in the step
+that hands over the utterance's last frame, and that step emits everything held back -- so the audio of a step is what the
+slot EMITTED (``hip.mb_emit`` on a host count of pending rows), not ``n * hop`` samples, and ``first_sample`` is the running
+sample count of the utterance.  The post-net's look-ahead delays the first frames of an utterance, so a slot is released only
 after its last frame has been VOCODED: until then it takes zero-count acoustic steps while the vocoder drains what is left.
 
 The emulated C ABI (oracle/cabi_numpy.py) has no hand-over entry point, as it has none of the per-slot ones: the class says
 so at construction.
 
 Not here: overlapping the acoustic step of chunk k + 1 with the vocoder step of chunk k on two streams, a captured acoustic
-step, multi-band generators.
+step.
 """
 import torch
 
 import kantts._hip as hip
 from kantts.models.hifigan.chunked import ChunkedVocoder
+from kantts.models.hifigan.chunked_mb import ChunkedMBVocoder
 from kantts.models.hifigan.chunked_nsf import ChunkedNSFVocoder
 from kantts.models.sambert.slots import AcousticSlots
 
@@ -38,8 +44,9 @@ _NO_HANDOVER = ("the loaded C ABI has no hand-over entry point (kantts_mel_hando
 
 class StreamingTTS:
     """``slots`` utterances at a time from linguistic inputs to audio through one ``KanTtsSAMBERT`` (eval, bf16 mode: the
-    rules of ``AcousticSlots``) and one causal single-band ``Generator`` (eval, on the same device: the rules of
-    ``ChunkedVocoder`` / ``ChunkedNSFVocoder``, whichever the generator needs).  ``max_steps``: decoder steps the buffers of a
+    rules of ``AcousticSlots``) and one causal ``Generator`` (eval, on the same device: the rules of
+    ``ChunkedVocoder`` / ``ChunkedNSFVocoder`` / ``ChunkedMBVocoder``, whichever the generator needs; a multi-band generator
+    carries its ``pqmf``, as ``infer_hifigan.load_model`` attaches it).  ``max_steps``: decoder steps the buffers of a
     slot hold; ``chunk_frames``: frames per vocoder step, a positive multiple of ``outputs_per_step``; ``nsf=(scale,
     offset)``: the f0 de-normalisation of an NSF voice (mean_std: std and mean; global: max - min and min), with
     ``f0_threshold`` the floor in Hz and ``uv_threshold`` the voicing threshold; ``seed`` and ``graph`` go to the vocoder.
@@ -68,7 +75,10 @@ class StreamingTTS:
         self.nsf = None if nsf is None else (float(nsf[0]), float(nsf[1]))
         self.f0_threshold, self.uv_threshold = float(f0_threshold), float(uv_threshold)
         self.pool = AcousticSlots(fsnet, slots=slots, max_steps=max_steps)
-        if nsf_enable:
+        self.mb = int(generator.out_channels) > 1
+        if self.mb:
+            self.vocoder = ChunkedMBVocoder(generator, slots=slots, graph=graph)
+        elif nsf_enable:
             self.vocoder = ChunkedNSFVocoder(generator, slots=slots, graph=graph, seed=seed)
         else:
             self.vocoder = ChunkedVocoder(generator, slots=slots, graph=graph)
@@ -76,9 +86,11 @@ class StreamingTTS:
             raise ValueError("the acoustic model is on %s, the generator on %s" % (self.pool.dev, self.vocoder.device))
         self.S, self.Tc, self.chunk_steps, self.hop = self.pool.S, int(chunk_frames), int(chunk_frames) // r, self.vocoder.hop
         self.buf = torch.zeros(self.S, want, self.Tc, device=self.pool.dev, dtype=torch.float32)  # the vocoder's step input
-        # host cursors per slot: the request it plays (None: free), its live frames, how many are final, how many vocoded
+        # host cursors per slot: the request it plays (None: free), its live frames, how many are final, how many vocoded,
+        # the samples emitted so far and (multi-band) the low-rate rows the synthesis holds back
         self.index = [None] * self.S
         self.frames, self.final, self.vocoded = [0] * self.S, [0] * self.S, [0] * self.S
+        self.samples, self.pending = [0] * self.S, [0] * self.S
 
     # ------------------------------------------------------------------------------------------------ slots
     def admit(self, s, index, request):
@@ -91,7 +103,7 @@ class StreamingTTS:
         self.vocoder._assign(s, index)
         self.index[s] = index
         self.frames[s] = self.pool.live_rows(s, 0, self.pool.T)
-        self.final[s] = self.vocoded[s] = 0
+        self.final[s] = self.vocoded[s] = self.samples[s] = self.pending[s] = 0
         return self.frames[s]
 
     def done(self, s):
@@ -112,14 +124,16 @@ class StreamingTTS:
         self.pool.release(s)
         self.vocoder.reset(s)
         self.index[s] = None
-        self.frames[s] = self.final[s] = self.vocoded[s] = 0
+        self.frames[s] = self.final[s] = self.vocoded[s] = self.samples[s] = self.pending[s] = 0
 
     # ------------------------------------------------------------------------------------------------ step
     @torch.no_grad()
     def step(self):
         """One acoustic step, then at most one vocoder step.  Returns one entry per slot: None for a free slot, else
         ``(index, lo, n, wav)``: the slot's utterance, its frame position before this step, the frames handed over and
-        their audio, (1, n * hop) (n may be 0: nothing of the slot was final yet, or everything has been vocoded)."""
+        their audio, (1, n * hop) (n may be 0: nothing of the slot was final yet, or everything has been vocoded).  A
+        multi-band voice holds samples back: the audio is what the slot emitted, up to D * B samples fewer than n * hop, and
+        that many more in the step that hands over the utterance's last frame."""
         pool, S, Tc = self.pool, self.S, self.Tc
         counts = [0] * S
         for s in range(S):
@@ -133,15 +147,23 @@ class StreamingTTS:
                 rows[s] = min(Tc, self.final[s] - self.vocoded[s])
         wav = None
         if any(rows):
-            A = torch.tensor([self.vocoded, rows], dtype=torch.int32).to(pool.dev, non_blocking=True)  # the ONE upload
+            # multi-band: the utterance ends for the vocoder in the step that hands over its last frame
+            last = [int(rows[s] > 0 and self.vocoded[s] + rows[s] == self.frames[s]) for s in range(S)]
+            A = torch.tensor([self.vocoded, rows, last] if self.mb else [self.vocoded, rows],
+                             dtype=torch.int32).to(pool.dev, non_blocking=True)  # the ONE upload
             hip.check(hip.mel_handover(pool.y, A[0], A[1], self.buf, nsf=self.nsf, f0_floor=self.f0_threshold,
                                        uv_threshold=self.uv_threshold), "mel_handover_rows")
-            wav = self.vocoder.step(self.buf, rows=A[1])
+            wav = self.vocoder.step(self.buf, rows=A[1], last=A[2]) if self.mb else self.vocoder.step(self.buf, rows=A[1])
         ret = [None] * S
         for s in range(S):
             if self.index[s] is not None:
                 lo, n = self.vocoded[s], rows[s]
-                audio = wav[s, :, :n * self.hop] if n else torch.zeros(1, 0, device=pool.dev, dtype=torch.float32)
+                m = n * self.hop
+                if self.mb and n:
+                    v = self.vocoder
+                    e, self.pending[s] = hip.mb_emit(self.pending[s], n * v.low_hop, last[s], v.D)
+                    m = e * v.B
+                audio = wav[s, :, :m] if m else torch.zeros(1, 0, device=pool.dev, dtype=torch.float32)
                 ret[s] = (self.index[s], lo, n, audio)
                 self.vocoded[s] = lo + n
         return ret
@@ -149,7 +171,8 @@ class StreamingTTS:
     def play_many(self, requests, results=None):
         """Continuous batching from symbols to audio: a generator that plays ``requests`` -- each the arguments of
         ``AcousticSlots.admit`` without the slot -- through all slots, yielding ``(index, first_sample, wav)`` with wav
-        (1, n * hop) the next ``n`` frames of request ``index``, in slot order after every step.  The schedule is that of
+        (1, n * hop) the next ``n`` frames of request ``index`` (a multi-band voice: the samples the step emitted, see
+        ``step``; ``first_sample`` is the utterance's running sample count), in slot order after every step.  The schedule is that of
         the two halves' own ``play_many``: every slot must be free; the slots take requests in input order; a slot is
         released once its last frame has been vocoded -- after ``results[index] = pool.result(slot)`` when a dictionary is
         given -- and takes the next request before the next step.  The chunks of an utterance add up to frames * hop
@@ -166,9 +189,10 @@ class StreamingTTS:
                     nxt += 1
             if all(i is None for i in self.index):
                 return
-            for out in self.step():
-                if out is not None and out[2] > 0:
-                    yield out[0], out[1] * self.hop, out[3]
+            for s, out in enumerate(self.step()):
+                if out is not None and out[3].shape[-1] > 0:
+                    yield out[0], self.samples[s], out[3]
+                    self.samples[s] += int(out[3].shape[-1])
             for s in range(self.S):
                 if self.index[s] is not None and self.done(s):
                     self.release(s, results)
