@@ -1346,6 +1346,64 @@ typedef struct {
 } kantts_sconv_rows_args;
 int kantts_sconv_rows_launch(const kantts_sconv_rows_args* args, void* stream);
 
+/* ---- The per-slot layer for SYMMETRIC (non-causal) networks (csrc/sconv_sym.hip): a symmetric convolution of padding p
+ * is the causal one with the same taps whose output stream is p rows late, zero outside the utterance.  Every tensor of
+ * such a network has an integer delay: row n of its stream, counted from the slot's reset, is true row n - delay.
+ * The rule of kantts_sconv_rows_launch (same tiles, arithmetic and summation order) with
+ *   n_s      = clamp(rows[s], 0, Tc / row_mul) * row_mul           live rows of slot s, as there
+ *   pos_s    = pos_in[s * pos_ss]                                  frames slot s consumed before this call
+ *   end_s    = end[s]                                              frames of the slot's utterance; < 0: open
+ *   Hs       = (K - 1) * step + lag                                state rows of the layer
+ *   X[s, t]  = in[s, t] (0 <= t < n_s),  hist_in[s, Hs + t] (-Hs <= t < 0); with in_end != 0 and end_s >= 0 a row whose
+ *              stream position pos_s * row_mul + t is >= end_s * row_mul is 0.0f and is NOT loaded (flush rows)
+ *   R[s, t]  = res[s, t] (t >= 0),  res_hist[s, res_hist_rows + t] (-res_hist_rows <= t < 0)
+ *   y[s,q,n] = post( bias[n] + sum_j sum_c pre( X[s, q - lag - j*step, c] ) * w[j][n][c] ) + R[s, q - res_lag, n]
+ *   g(q, n)  = (pos_s * row_mul + q) * sub + (sub > 1 ? n / (N / sub) : 0) - delay        true sample index, 64-bit
+ *   out[s, q, n] = y[s, q, n]  when 0 <= g(q, n) and (end_s < 0 or g(q, n) < end_s * row_mul * sub),  else 0.0f,  q < n_s
+ *   out[s, q, n] for q >= n_s: not written; written as 0.0f when zero_tail != 0 (N == 1 only)
+ *   hist_out[s, h, c] = X[s, n_s - Hs + h, c]   for h in [0, Hs)
+ *   pos_out[s * pos_ss] = pos_s + n_s / row_mul   when pos_out != NULL (written by the state workgroup of slot s; the
+ *              first layer of a step passes it, every launch of the step reads the same pos_in: ping-pong with the state)
+ * res_hist is another layer's carried state (read only), (res_hist_rows, N) dense inside a slot, res_hist_ss floats between
+ * slots.  A polyphase layer of stride u passes sub = u: row q, column n of out is sample q * u + n / (N / u).
+ * No row >= n_s of in / res, and no flush row of in, is loaded: such rows may hold NaN.  w, precision, alignment and the
+ * shape contract are those of kantts_sconv_launch (hist_ss >= Hs * Cin when S > 1).
+ * KANTTS_E_BADARG: rows / end / pos_in == NULL, row_mul < 1, Tc % row_mul != 0, lag < 0, res_lag < 0, delay < 0, sub < 1,
+ * N % sub != 0, res_lag > 0 without res and res_hist or beyond res_hist_rows, res_hist without res, missing hist_in /
+ * hist_out when Hs > 0.  KANTTS_E_UNSUPPORTED: zero_tail with N != 1, and what kantts_sconv_launch declines. */
+typedef struct {
+  const float* in;
+  const float* hist_in;
+  float* hist_out;
+  const void* w;
+  const float* bias;
+  const float* res;
+  const float* res_hist;
+  float* out;
+  const int32_t* rows;
+  const int32_t* end;
+  const int32_t* pos_in;
+  int32_t* pos_out;
+  long long hist_ss;
+  long long res_hist_ss;
+  long long pos_ss;
+  long long delay;
+  int S, Tc, Cin, N, K, step;
+  float in_slope;
+  int in_act;
+  float out_slope;
+  int out_act;
+  int precision;
+  int row_mul;
+  int zero_tail;
+  int lag;
+  int res_lag;
+  int res_hist_rows;
+  int sub;
+  int in_end;
+} kantts_sconv_sym_args;
+int kantts_sconv_sym_rows_launch(const kantts_sconv_sym_args* args, void* stream);
+
 /* ---- The NSF excitation of chunked inference (csrc/nsf_source.hip): a sine source that can be cut at any frame boundary
  * and the strided one-channel convolutions that bring it to every upsampling stage's rate.  Both entry points are per slot
  * and read the same device `rows` buffer as kantts_sconv_rows_launch:

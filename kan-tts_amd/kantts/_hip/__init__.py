@@ -115,6 +115,20 @@ class SConvRowsArgs(Structure):
     _fields_ = SConvArgs._fields_ + [("rows", c_void_p), ("row_mul", c_int32), ("zero_tail", c_int32)]
 
 
+class SConvSymArgs(Structure):
+    """kantts_sconv_sym_args (include/kantts_hip.h); ``in_`` is the C field ``in``."""
+    _fields_ = [
+        ("in_", c_void_p), ("hist_in", c_void_p), ("hist_out", c_void_p), ("w", c_void_p), ("bias", c_void_p),
+        ("res", c_void_p), ("res_hist", c_void_p), ("out", c_void_p), ("rows", c_void_p), ("end", c_void_p),
+        ("pos_in", c_void_p), ("pos_out", c_void_p),
+        ("hist_ss", c_longlong), ("res_hist_ss", c_longlong), ("pos_ss", c_longlong), ("delay", c_longlong),
+        ("S", c_int32), ("Tc", c_int32), ("Cin", c_int32), ("N", c_int32), ("K", c_int32), ("step", c_int32),
+        ("in_slope", c_float), ("in_act", c_int32), ("out_slope", c_float), ("out_act", c_int32),
+        ("precision", c_int32), ("row_mul", c_int32), ("zero_tail", c_int32), ("lag", c_int32), ("res_lag", c_int32),
+        ("res_hist_rows", c_int32), ("sub", c_int32), ("in_end", c_int32),
+    ]
+
+
 NSF_STATE_WORDS = 36  # KANTTS_NSF_STATE_WORDS: phase[16] u32, phase0[16] f32, cursor u64, key u64
 NSF_MAX_H1, NSF_MAX_STAGES, NSF_MAX_K = 16, 8, 8192
 
@@ -507,6 +521,7 @@ def lib():
         L.kantts_nsf_downs_rows.argtypes = [POINTER(NsfDownsArgs), c_void_p]
         L.kantts_mel_handover_rows.argtypes = [p, p, p, p, i, i, i, i, i, f, f, f, f, p]
         L.kantts_mb_tail_rows.argtypes = [POINTER(MbTailArgs), c_void_p]
+        L.kantts_sconv_sym_rows_launch.argtypes = [POINTER(SConvSymArgs), c_void_p]
         _lib = L
     return _lib
 
@@ -534,7 +549,7 @@ EXPORTED_SYMBOLS = [
     "kantts_pnca_decode_range", "kantts_lstm_fwd_range", "kantts_fsmn_dwconv_fwd_rows",
     "kantts_pnca_decode_slots", "kantts_lstm_fwd_slots", "kantts_fsmn_dwconv_fwd_slots", "kantts_scatter_rows_f32",
     "kantts_nsf_source_rows", "kantts_nsf_downs_rows", "kantts_mel_handover_rows",
-    "kantts_mb_tail_rows",
+    "kantts_mb_tail_rows", "kantts_sconv_sym_rows_launch",
 ]
 
 
@@ -1437,6 +1452,59 @@ def sconv(x, hist_in, hist_out, w, out, *, S, Tc, Cin, N, K, step, hist_ss, prec
     if rc == E_UNSUPPORTED:
         return False
     check(rc, "sconv")
+    return True
+
+
+def sconv_sym_entry_points():
+    """True when the loaded library exports the symmetric-network layer of ChunkedNCVocoder."""
+    return hasattr(lib(), "kantts_sconv_sym_rows_launch")
+
+
+def nc_emit(pos, n, end, delay, hop):
+    """The emission rule of a chunked non-causal vocoder on the host (the one definition): a slot that has consumed ``pos``
+    frames takes ``n`` more (flush frames included); its utterance has ``end`` frames (< 0: not known yet) and the waveform
+    is ``delay`` samples late.  The step's output holds true samples [max(0, pos*hop - delay), min((pos+n)*hop - delay,
+    end*hop)) and 0.0 elsewhere.  Returns (offset of the first of them in the step's output, their count); (0, 0) when there are none."""
+    pos, n, end, delay, hop = int(pos), int(n), int(end), int(delay), int(hop)
+    lo = max(0, pos * hop - delay)
+    hi = (pos + n) * hop - delay
+    if end >= 0:
+        hi = min(hi, end * hop)
+    if hi <= lo:
+        return 0, 0
+    return lo + delay - pos * hop, hi - lo
+
+
+def sconv_sym(x, hist_in, hist_out, w, out, *, S, Tc, Cin, N, K, step, hist_ss, precision, rows, end, pos_in, pos_out=None,
+              pos_ss=1, row_mul=1, delay=0, sub=1, lag=0, in_end=False, bias=None, res=None, res_hist=None, res_hist_ss=0,
+              res_hist_rows=0, res_lag=0, in_leaky=None, out_leaky=None, zero_tail=False):
+    """The layer of chunked inference for symmetric networks (csrc/sconv_sym.hip, kantts_sconv_sym_rows_launch; the token
+    rule is written out in include/kantts_hip.h): ``sconv`` with per-slot counts, plus an input ``lag`` (state: the last
+    (K - 1) * step + lag rows), a residual read ``res_lag`` rows back through ``res_hist`` (another layer's state, read
+    only), and the output window: with ``pos_in`` / ``end`` int32 device tensors (frames consumed per slot, ``pos_ss`` words
+    between slots; frames of the utterance, < 0 open), an output sample whose true index (stream index - ``delay``) lies
+    outside [0, end * row_mul * sub) is stored as 0.0.  ``in_end``: rows of x at or beyond end * row_mul are not loaded.
+    ``pos_out``: where the launch writes pos_in + rows.  Returns False when the kernel declines the shape."""
+    g = SConvSymArgs()
+    g.in_, g.hist_in, g.hist_out = ptr(x, torch.float32), ptr(hist_in, torch.float32), ptr(hist_out, torch.float32)
+    g.w = ptr(w, torch.bfloat16 if (precision == PREC_BF16 and N > 1) else torch.float32)
+    g.bias, g.res, g.out = ptr(bias, torch.float32), ptr(res, torch.float32), ptr(out, torch.float32)
+    g.res_hist = ptr(res_hist, torch.float32)
+    g.rows, g.end = ptr(rows, torch.int32), ptr(end, torch.int32)
+    g.pos_in, g.pos_out = ptr(pos_in, torch.int32), ptr(pos_out, torch.int32)
+    for name, t in (("rows", rows), ("end", end)):
+        if t is not None and t.numel() != int(S):
+            raise ValueError("%s must hold S = %d counts, got %d" % (name, int(S), t.numel()))
+    g.hist_ss, g.res_hist_ss, g.pos_ss, g.delay = int(hist_ss), int(res_hist_ss), int(pos_ss), int(delay)
+    g.S, g.Tc, g.Cin, g.N, g.K, g.step = int(S), int(Tc), int(Cin), int(N), int(K), int(step)
+    g.in_slope, g.in_act = float(in_leaky or 0.0), int(in_leaky is not None)
+    g.out_slope, g.out_act = float(out_leaky or 0.0), int(out_leaky is not None)
+    g.precision, g.row_mul, g.zero_tail = int(precision), int(row_mul), int(bool(zero_tail))
+    g.lag, g.res_lag, g.res_hist_rows, g.sub, g.in_end = int(lag), int(res_lag), int(res_hist_rows), int(sub), int(bool(in_end))
+    rc = lib().kantts_sconv_sym_rows_launch(ctypes.byref(g), stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "sconv_sym")
     return True
 
 

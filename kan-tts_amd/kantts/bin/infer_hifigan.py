@@ -12,6 +12,8 @@ the RTF.  Absent: the whole-utterance path, unchanged.  ``--slots S`` (with ``--
 each slot taking the next file as soon as its utterance ends (``ChunkedVocoder.play_many``); the same files are written.
 NSF generators play through kantts.models.hifigan.chunked_nsf.ChunkedNSFVocoder (a streamed sine excitation): utterance i
 of the sorted input list gets the noise and initial phases of ``(--seed, i)``, whatever the chunk size and the slots.
+Non-causal generators (single band, no source module) play through kantts.models.hifigan.chunked_nc.ChunkedNCVocoder: the
+network's look-ahead becomes a delay (logged; 3424 samples for the shipped non-causal geometry) that is flushed at the end.
 Multi-band generators play through kantts.models.hifigan.chunked_mb.ChunkedMBVocoder (a PQMF synthesis that holds back the
 samples whose future it has not seen): the chunks have variable lengths and add up to the one-shot path's sample count.
 """
@@ -91,6 +93,13 @@ def _chunked_vocoder(model, slots, device, seed):
         from kantts.models.hifigan.chunked_mb import ChunkedMBVocoder
 
         return ChunkedMBVocoder(model, slots=slots, graph=device.type == "cuda")
+    if not model.causal:
+        from kantts.models.hifigan.chunked_nc import ChunkedNCVocoder
+
+        vocoder = ChunkedNCVocoder(model, slots=slots, graph=device.type == "cuda")
+        logging.info("Non-causal generator: the waveform comes %d samples (%d frames) after the frames it is made of.",
+                     vocoder.delay_samples, vocoder.flush_frames)
+        return vocoder
     from kantts.models.hifigan.chunked import ChunkedVocoder
 
     return ChunkedVocoder(model, slots=slots, graph=device.type == "cuda")

@@ -67,8 +67,12 @@ def _stream(symbols_file, output_dir, am_ckpt, voc_ckpt, se_file, chunk_frames, 
     generator.remove_weight_norm()
     generator = generator.eval().to(device)
     sr = voc_config["audio_config"]["sampling_rate"]
+    # lookahead: a non-causal voice streams too, its audio ``flush_frames`` frames late
     tts = StreamingTTS(fsnet, generator, slots=slots, max_steps=slot_steps, chunk_frames=chunk_frames, nsf=nsf, seed=seed,
-                       graph=device.type == "cuda")  # refuses what it cannot stream, loudly
+                       graph=device.type == "cuda", lookahead=True)  # refuses what it cannot stream, loudly
+    if tts.flush_frames:
+        logging.info("Non-causal generator: the audio of an utterance starts %d frames (%d samples) after its first frame.",
+                     tts.flush_frames, tts.vocoder.delay_samples)
     feat_dir = os.path.join(output_dir, "feat")
     os.makedirs(feat_dir, exist_ok=True)
     with open(symbols_file, encoding="utf-8") as f:

@@ -67,17 +67,20 @@ class ChunkedVocoder:
     counts live in one int32 device buffer that the captured launches read, so they change between replays without a
     new capture (``captures`` counts the captures of the object).
 
-    Refused at construction: non-causal generators, NSF generators (the excitation's running phase and random draws need
+    Refused at construction: non-causal generators (kantts.models.hifigan.chunked_nc.ChunkedNCVocoder plays them, late by
+    the network's look-ahead), NSF generators (the excitation's running phase and random draws need
     a carried state of their own: kantts.models.hifigan.chunked_nsf.ChunkedNSFVocoder plays them), ``out_channels > 1``
     (the PQMF synthesis looks ahead: kantts.models.hifigan.chunked_mb.ChunkedMBVocoder plays them), and channel counts / kernel sizes the kernel declines (Cin a multiple of 8 in 16..512, k <= 11,
     dilation <= 7, upsampling N = scale * Cout <= 4096)."""
 
     _plays_nsf = False  # kantts.models.hifigan.chunked_nsf.ChunkedNSFVocoder carries the excitation's state
     _plays_multiband = False  # kantts.models.hifigan.chunked_mb.ChunkedMBVocoder runs conv_post inside the multi-band tail
+    _plays_noncausal = False  # kantts.models.hifigan.chunked_nc.ChunkedNCVocoder delays, windows and flushes
+    _conv_cls, _up_cls = CausalConv1d, CausalConvTranspose1d  # what the layers of the generator must be
 
     def __init__(self, generator, slots=1, graph=True, max_graphs=8):
         g = generator
-        if not getattr(g, "causal", False):
+        if not getattr(g, "causal", False) and not self._plays_noncausal:
             raise ValueError("ChunkedVocoder needs a causal generator (causal=True): a symmetric convolution looks ahead")
         if g.nsf_enable and not self._plays_nsf:
             raise NotImplementedError("ChunkedVocoder: NSF generators are not supported (the source module's running phase "
@@ -102,8 +105,8 @@ class ChunkedVocoder:
 
         # ---- geometry of every stateful layer, from the modules' shapes alone (nothing is computed or launched yet)
         def conv_layer(name, m, in_leaky):
-            if not isinstance(m, CausalConv1d):
-                raise ValueError("ChunkedVocoder: %s is not a CausalConv1d" % name)
+            if not isinstance(m, self._conv_cls) or m.causal == self._plays_noncausal:
+                raise ValueError("ChunkedVocoder: %s is not a %s" % (name, self._conv_cls.__name__))
             c = m.conv1d
             if c.stride[0] != 1 or c.groups != 1:
                 raise NotImplementedError("ChunkedVocoder: %s has stride / groups != 1" % name)
@@ -114,16 +117,11 @@ class ChunkedVocoder:
         self.stages = []
         for i, s in enumerate(self.scales):
             up = g.transpose_upsamples[i][1]
-            if not isinstance(up, CausalConvTranspose1d):
-                raise ValueError("ChunkedVocoder: transpose_upsamples[%d] is not causal" % i)
+            if not isinstance(up, self._up_cls):
+                raise ValueError("ChunkedVocoder: transpose_upsamples[%d] is not %s" % (
+                    i, "causal" if self._up_cls is CausalConvTranspose1d else "a " + self._up_cls.__name__))
             d = up.deconv
-            if d.kernel_size[0] % s:
-                raise NotImplementedError("ChunkedVocoder: upsampling kernel %d is not a multiple of its stride %d"
-                                          % (d.kernel_size[0], s))
-            J = d.kernel_size[0] // s
-            if g.repeat_upsample:
-                k7 = g.repeat_upsamples[i][2].conv1d.kernel_size[0]
-                J = max(J, 1 + -(-(k7 - 1) // s))
+            J = self._stage_taps(g, i, s)
             upl = _Layer("stage%d.up" % i, d.in_channels, s * d.out_channels, J, 1, self.slope)
             stacks = []
             for j, blk in enumerate(g.conv_blocks[i * g.num_kernels:(i + 1) * g.num_kernels]):
@@ -179,11 +177,7 @@ class ChunkedVocoder:
         with torch.no_grad():
             pack_conv(self.pre, g.conv_pre)
             for i, (s, Cout, upl, stacks) in enumerate(self.stages):
-                if g.repeat_upsample:
-                    w, b = g._dual_path_weight(i, s)  # (Cin, Cout, J*s)
-                else:
-                    d = g.transpose_upsamples[i][1].deconv
-                    w, b = effective_weight(d), d.bias
+                w, b = self._stage_weight(g, i, s)  # (Cin, Cout, J*s)
                 w2 = w.reshape(upl.Cin, Cout, upl.K, s).permute(2, 3, 1, 0).reshape(upl.K, s * Cout, upl.Cin)
                 pack(upl, w2, None if b is None else b.repeat(s))
                 blocks = g.conv_blocks[i * g.num_kernels:(i + 1) * g.num_kernels]
@@ -200,7 +194,28 @@ class ChunkedVocoder:
         self.captures = 0
 
     # ------------------------------------------------------------------------------------------------------------
-    # hooks of ChunkedNSFVocoder; here they do nothing and the launches of a step are the ones of _run alone
+    # the polyphase form of an upsampling stage (ChunkedNCVocoder has the symmetric stage's)
+    def _stage_taps(self, g, i, s):
+        """J: input tokens per output row of stage ``i`` (stride ``s``), from shapes alone."""
+        d = g.transpose_upsamples[i][1].deconv
+        if d.kernel_size[0] % s:
+            raise NotImplementedError("ChunkedVocoder: upsampling kernel %d is not a multiple of its stride %d"
+                                      % (d.kernel_size[0], s))
+        J = d.kernel_size[0] // s
+        if g.repeat_upsample:
+            k7 = g.repeat_upsamples[i][2].conv1d.kernel_size[0]
+            J = max(J, 1 + -(-(k7 - 1) // s))
+        return J
+
+    def _stage_weight(self, g, i, s):
+        """(Cin, Cout, J * s) weight and (Cout) bias of stage ``i`` as one causal transposed convolution."""
+        if g.repeat_upsample:
+            return g._dual_path_weight(i, s)
+        d = g.transpose_upsamples[i][1].deconv
+        return effective_weight(d), d.bias
+
+    # ------------------------------------------------------------------------------------------------------------
+    # hooks of the subclasses; here they do nothing and the launches of a step are the ones of _run alone
     def _plan_extra(self, g):
         """Further refusals, decided from shapes before anything is packed."""
 

@@ -97,19 +97,26 @@ class ConvTranspose1d(torch.nn.Module):
                                                      output_padding=0))
         self.deconv.apply(init_weights)
 
-        if kernel_size % stride != 0 or (kernel_size - stride) % 2 != 0 or padding != (kernel_size - stride) // 2:
-            raise NotImplementedError("only kernel = m*stride with padding (kernel - stride) / 2 (every shipped yaml)")
+        if output_padding != 0 or padding < 0:
+            raise NotImplementedError("ConvTranspose1d: output_padding != 0 and negative padding are not supported (any "
+                                      "kernel, stride and padding >= 0 are: the polyphase form zero-extends the kernel to a "
+                                      "multiple of the stride)")
         self.stride, self.padding = stride, padding
 
     def forward_cl(self, x, in_leaky=None, res=None):
-        """Full transposed convolution = the polyphase form over one extra (zero) input token; the symmetric
-        padding of the reference (:94-121) drops ``padding`` samples at both ends of it."""
+        """Full transposed convolution = the polyphase form over extra (zero) input tokens, with the kernel zero-extended
+        to ceil(K / s) * s taps when K is no multiple of the stride (the added taps contribute nothing and the pad's
+        backward drops their gradient); the symmetric padding of the reference (:94-121) keeps samples
+        [padding, padding + (T - 1) s - 2 padding + K) of it -- T s + (K - s) % 2 of them for padding (K - s) // 2."""
         B, T, _ = x.shape
-        s, pad = self.stride, self.padding
-        taps = self.deconv.kernel_size[0] // s
+        s, pad, K = self.stride, self.padding, self.deconv.kernel_size[0]
+        taps = -(-K // s)
+        w = effective_weight(self.deconv)
+        if taps * s != K:
+            w = torch.nn.functional.pad(w, (0, taps * s - K))
         xz = torch.nn.functional.pad(x, (0, 0, 0, taps - 1))
-        full = ops.conv_transpose_cl(xz, effective_weight(self.deconv), self.deconv.bias, s, in_leaky=in_leaky)
-        y = full[:, pad:pad + T * s, :]
+        full = ops.conv_transpose_cl(xz, w, self.deconv.bias, s, in_leaky=in_leaky)
+        y = full[:, pad:pad + (T - 1) * s - 2 * pad + K, :]
         return y if res is None else y + res
 
     def forward(self, x):

@@ -24,6 +24,12 @@ slot EMITTED (``hip.mb_emit`` on a host count of pending rows), not ``n * hop`` 
 sample count of the utterance.  The post-net's look-ahead delays the first frames of an utterance, so a slot is released only
 after its last frame has been VOCODED: until then it takes zero-count acoustic steps while the vocoder drains what is left.
 
+``lookahead=True`` lets a non-causal generator (single band, no source module) play, through ``ChunkedNCVocoder``: its audio
+comes ``vocoder.delay_samples`` late, so the upload also carries every slot's frame count (``end``) and the vocoder's own
+per-slot counts, which exceed the handed-over frames by flush frames once the acoustic frames have run out; the audio of a step
+is what the slot emitted (``hip.nc_emit``), and a slot is released only after the flush.  Without it such a generator is
+refused as before: the added latency (``vocoder.flush_frames`` frames before the first sample) is a decision.
+
 The emulated C ABI (oracle/cabi_numpy.py) has no hand-over entry point, as it has none of the per-slot ones: the class says
 so at construction.
 
@@ -57,7 +63,7 @@ class StreamingTTS:
     point, and whatever either underlying class refuses."""
 
     def __init__(self, fsnet, generator, slots=1, max_steps=1024, chunk_frames=None, nsf=None, f0_threshold=30.0,
-                 uv_threshold=0.6, seed=0, graph=True):
+                 uv_threshold=0.6, seed=0, graph=True, lookahead=False):
         r = int(fsnet.mel_decoder.r)
         if chunk_frames is None or int(chunk_frames) < 1 or int(chunk_frames) % r:
             raise ValueError("chunk_frames must be a positive multiple of outputs_per_step (%d), got %r" % (r, chunk_frames))
@@ -76,7 +82,12 @@ class StreamingTTS:
         self.f0_threshold, self.uv_threshold = float(f0_threshold), float(uv_threshold)
         self.pool = AcousticSlots(fsnet, slots=slots, max_steps=max_steps)
         self.mb = int(generator.out_channels) > 1
-        if self.mb:
+        self.nc = bool(lookahead) and not getattr(generator, "causal", False) and not self.mb and not nsf_enable
+        if self.nc:
+            from kantts.models.hifigan.chunked_nc import ChunkedNCVocoder
+
+            self.vocoder = ChunkedNCVocoder(generator, slots=slots, graph=graph)
+        elif self.mb:
             self.vocoder = ChunkedMBVocoder(generator, slots=slots, graph=graph)
         elif nsf_enable:
             self.vocoder = ChunkedNSFVocoder(generator, slots=slots, graph=graph, seed=seed)
@@ -87,10 +98,12 @@ class StreamingTTS:
         self.S, self.Tc, self.chunk_steps, self.hop = self.pool.S, int(chunk_frames), int(chunk_frames) // r, self.vocoder.hop
         self.buf = torch.zeros(self.S, want, self.Tc, device=self.pool.dev, dtype=torch.float32)  # the vocoder's step input
         # host cursors per slot: the request it plays (None: free), its live frames, how many are final, how many vocoded,
-        # the samples emitted so far and (multi-band) the low-rate rows the synthesis holds back
+        # the samples emitted so far, (multi-band) the low-rate rows the synthesis holds back and (lookahead) the flush
+        # frames the vocoder has taken behind the utterance's last one
         self.index = [None] * self.S
         self.frames, self.final, self.vocoded = [0] * self.S, [0] * self.S, [0] * self.S
-        self.samples, self.pending = [0] * self.S, [0] * self.S
+        self.samples, self.pending, self.flushed = [0] * self.S, [0] * self.S, [0] * self.S
+        self.flush_frames = self.vocoder.flush_frames if self.nc else 0
 
     # ------------------------------------------------------------------------------------------------ slots
     def admit(self, s, index, request):
@@ -103,15 +116,15 @@ class StreamingTTS:
         self.vocoder._assign(s, index)
         self.index[s] = index
         self.frames[s] = self.pool.live_rows(s, 0, self.pool.T)
-        self.final[s] = self.vocoded[s] = self.samples[s] = self.pending[s] = 0
+        self.final[s] = self.vocoded[s] = self.samples[s] = self.pending[s] = self.flushed[s] = 0
         return self.frames[s]
 
     def done(self, s):
-        """True once the last live frame of the slot's utterance has been vocoded."""
+        """True once the last live frame of the slot's utterance has been vocoded (lookahead: and flushed out)."""
         s = int(s)
         if self.index[s] is None:
             raise ValueError("slot %d is free" % s)
-        return self.pool.finished(s) and self.vocoded[s] >= self.frames[s]
+        return self.pool.finished(s) and self.vocoded[s] >= self.frames[s] and self.flushed[s] >= self.flush_frames
 
     def release(self, s, results=None):
         """Free slot ``s`` of both halves after ``results[index] = pool.result(s)`` when a dictionary is given; the
@@ -124,7 +137,7 @@ class StreamingTTS:
         self.pool.release(s)
         self.vocoder.reset(s)
         self.index[s] = None
-        self.frames[s] = self.final[s] = self.vocoded[s] = self.samples[s] = self.pending[s] = 0
+        self.frames[s] = self.final[s] = self.vocoded[s] = self.samples[s] = self.pending[s] = self.flushed[s] = 0
 
     # ------------------------------------------------------------------------------------------------ step
     @torch.no_grad()
@@ -133,7 +146,9 @@ class StreamingTTS:
         ``(index, lo, n, wav)``: the slot's utterance, its frame position before this step, the frames handed over and
         their audio, (1, n * hop) (n may be 0: nothing of the slot was final yet, or everything has been vocoded).  A
         multi-band voice holds samples back: the audio is what the slot emitted, up to D * B samples fewer than n * hop, and
-        that many more in the step that hands over the utterance's last frame."""
+        that many more in the step that hands over the utterance's last frame.  With ``lookahead`` the audio is what the
+        slot emitted too: nothing for the first ``flush_frames`` frames or so, and the rest in steps with n == 0 in which
+        the vocoder takes flush frames."""
         pool, S, Tc = self.pool, self.S, self.Tc
         counts = [0] * S
         for s in range(S):
@@ -145,8 +160,20 @@ class StreamingTTS:
             if self.index[s] is not None:
                 self.final[s] = max(self.final[s], min(outs[s][1], self.frames[s]))
                 rows[s] = min(Tc, self.final[s] - self.vocoded[s])
+        flush = [0] * S  # lookahead: frames the vocoder takes behind the last one, once every live frame is final
+        if self.nc:
+            for s in range(S):
+                if self.index[s] is not None and self.final[s] == self.frames[s]:
+                    flush[s] = min(Tc - rows[s], self.flush_frames - self.flushed[s])
         wav = None
-        if any(rows):
+        if self.nc and (any(rows) or any(flush)):
+            end = [self.frames[s] if self.index[s] is not None else -1 for s in range(S)]
+            A = torch.tensor([self.vocoded, rows, [r + f for r, f in zip(rows, flush)], end],
+                             dtype=torch.int32).to(pool.dev, non_blocking=True)  # the ONE upload
+            if any(rows):
+                hip.check(hip.mel_handover(pool.y, A[0], A[1], self.buf), "mel_handover_rows")
+            wav = self.vocoder.step(self.buf, rows=A[2], end=A[3])
+        elif any(rows):
             # multi-band: the utterance ends for the vocoder in the step that hands over its last frame
             last = [int(rows[s] > 0 and self.vocoded[s] + rows[s] == self.frames[s]) for s in range(S)]
             A = torch.tensor([self.vocoded, rows, last] if self.mb else [self.vocoded, rows],
@@ -159,11 +186,15 @@ class StreamingTTS:
             if self.index[s] is not None:
                 lo, n = self.vocoded[s], rows[s]
                 m = n * self.hop
+                off = 0
                 if self.mb and n:
                     v = self.vocoder
                     e, self.pending[s] = hip.mb_emit(self.pending[s], n * v.low_hop, last[s], v.D)
                     m = e * v.B
-                audio = wav[s, :, :m] if m else torch.zeros(1, 0, device=pool.dev, dtype=torch.float32)
+                if self.nc:
+                    off, m = hip.nc_emit(lo + self.flushed[s], n + flush[s], self.frames[s], self.vocoder.delay_samples, self.hop)
+                    self.flushed[s] += flush[s]
+                audio = wav[s, :, off:off + m] if m else torch.zeros(1, 0, device=pool.dev, dtype=torch.float32)
                 ret[s] = (self.index[s], lo, n, audio)
                 self.vocoded[s] = lo + n
         return ret
