@@ -268,6 +268,26 @@ int kantts_lr_gather_fwd(const float* x, const int32_t* idx, const int64_t* vali
 int kantts_lr_gather_bwd(const float* dout, const int32_t* cs, const int64_t* valid_lens, float* dx, int B, int N,
                          int Tp, int C, int ldo, int out_col_offset, int accumulate, void* stream);
 
+/* The regulated hand-over to the decoder (kantts_sambert.py: three regulators, + pos_enc, LFR reshape, cat) as one launch
+ * each way.  aug (B,N,d_t), spk (B,N,d_s), emo (B,N,d_e), pos_enc (B,Tp,d_t), idx / cs / valid_lens of kantts_lr_index and
+ * kantts_lr_gather_* (valid_lens may be NULL), Tp % r == 0, L = Tp / r:
+ *   memory (B, L, r*d_t + d_s + d_e), contiguous:
+ *     memory[b, l, j*d_t + c]       = G(aug)[b, l*r + j, c] + pos_enc[b, l*r + j, c]
+ *     memory[b, l, r*d_t + c]       = G(spk)[b, l*r, c]       memory[b, l, r*d_t + d_s + c] = G(emo)[b, l*r, c]
+ *   with G = kantts_lr_gather_fwd's rule (0 when idx < 0 or t >= valid_lens[b]); the sum is one fp32 add of the gathered
+ *   value (or 0) and pos_enc: bit-identical to the composition.  lr_text (B,Tp,d_t), lr_spk (B,Tp,d_s), lr_emo (B,Tp,d_e):
+ *   optional (NULL = not written) frame-level results of the composition, G(aug) + pos_enc, G(spk), G(emo).
+ * kantts_lr_memory_bwd: d_memory (B, L, .) with row pitch ldm floats (>= r*d_t + d_s + d_e; batch pitch L * ldm) ->
+ *   d_aug (B,N,d_t), d_spk (B,N,d_s), d_emo (B,N,d_e): per token the sum over its frames
+ *   [cs[n], min(cs[n+1], Tp, valid_lens[b])) in frame order, as kantts_lr_gather_bwd sums them (d_spk / d_emo: the frames
+ *   with t % r == 0) -- bit-identical to the composition's backward.  Every element of the three outputs is written.
+ * KANTTS_E_UNSUPPORTED: a width that is no multiple of 4, ldm % 4 != 0, or a tensor that is not 16-byte aligned. */
+int kantts_lr_memory_fwd(const float* aug, const float* spk, const float* emo, const int32_t* idx,
+                         const int64_t* valid_lens, const float* pos_enc, float* memory, float* lr_text, float* lr_spk,
+                         float* lr_emo, int B, int N, int Tp, int r, int d_t, int d_s, int d_e, void* stream);
+int kantts_lr_memory_bwd(const float* d_memory, long long ldm, const int32_t* cs, const int64_t* valid_lens, float* d_aug,
+                         float* d_spk, float* d_emo, int B, int N, int Tp, int r, int d_t, int d_s, int d_e, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * FSMN memory block (kantts/models/sambert/fsmn.py:43-72), channels-last (B,T,C), w (C,K):
  *   xm = x*keep; y = keep*(sum_k w[c,k]*xm[t+k-left_pad] + xm[t]) (+ res); keep[b,t] = t < lens[b].

@@ -260,6 +260,130 @@ extern "C" int kantts_lr_gather_bwd(const float* dout, const int32_t* cs, const 
 }
 
 // ------------------------------------------------------------------------------------------------
+// The regulated hand-over to the decoder as one launch each way: three gathers, the position add and the LFR grouping
+// write the decoder's memory directly.  L = Tp / r decoder steps, row of memory = [r * dt text | ds spk | de emo]:
+//   mem[b, l, j*dt + c]      = gather(aug)[b, l*r + j, c] + pos[b, l*r + j, c]
+//   mem[b, l, r*dt + c]      = gather(spk)[b, l*r, c]          mem[b, l, r*dt + ds + c] = gather(emo)[b, l*r, c]
+// gather = lr_gather_kernel's rule (0 when idx < 0 or t >= valid[b]); the add is one fp32 add of (gathered or 0) and pos,
+// as the composition lr_gather -> (+ pos) -> reshape -> cat computes it.  lr_text / lr_spk / lr_emo (may be NULL): the
+// frame-level tensors of that composition, (B, Tp, dt / ds / de).  Thread = (b, t, 4 columns of [text | spk | emo]).
+__global__ __launch_bounds__(256) void lr_memory_fwd_kernel(
+    const float* __restrict__ aug, const float* __restrict__ spk, const float* __restrict__ emo,
+    const int32_t* __restrict__ idx, const int64_t* __restrict__ valid, const float* __restrict__ pos,
+    float* __restrict__ mem, float* __restrict__ lr_text, float* __restrict__ lr_spk, float* __restrict__ lr_emo, int B,
+    int N, int Tp, int r, int dt, int ds, int de) {
+  const int W4 = (dt + ds + de) >> 2;
+  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (long long)B * Tp * W4) return;
+  const int col = (int)(g % W4) << 2;
+  const long long bt = g / W4;
+  const int t = (int)(bt % Tp), b = (int)(bt / Tp);
+  const int id = idx[bt];
+  const bool live = id >= 0 && (!valid || t < (int)valid[b]);
+  const int l = t / r, j = t - l * r;
+  float* mrow = mem + (bt / r) * (long long)(r * dt + ds + de);  // (b * L + l): Tp = L * r
+  const long long tok = (long long)b * N + (live ? id : 0);
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (col < dt) {
+    if (live) v = *reinterpret_cast<const float4*>(aug + tok * dt + col);
+    const float4 p = *reinterpret_cast<const float4*>(pos + bt * dt + col);
+    v.x = v.x + p.x; v.y = v.y + p.y; v.z = v.z + p.z; v.w = v.w + p.w;
+    *reinterpret_cast<float4*>(mrow + j * dt + col) = v;
+    if (lr_text) *reinterpret_cast<float4*>(lr_text + bt * dt + col) = v;
+  } else if (col < dt + ds) {
+    const int c = col - dt;
+    if (!lr_spk && j) return;
+    if (live) v = *reinterpret_cast<const float4*>(spk + tok * ds + c);
+    if (lr_spk) *reinterpret_cast<float4*>(lr_spk + bt * ds + c) = v;
+    if (!j) *reinterpret_cast<float4*>(mrow + r * dt + c) = v;
+  } else {
+    const int c = col - dt - ds;
+    if (!lr_emo && j) return;
+    if (live) v = *reinterpret_cast<const float4*>(emo + tok * de + c);
+    if (lr_emo) *reinterpret_cast<float4*>(lr_emo + bt * de + c) = v;
+    if (!j) *reinterpret_cast<float4*>(mrow + r * dt + ds + c) = v;
+  }
+}
+
+// d_aug[b,n,:] = sum over the token's frames t in [cs[n], min(cs[n+1], Tp, valid[b])), in frame order, of
+// dmem[b, t/r, (t%r)*dt + :]; d_spk / d_emo: the same sum over the frames with t % r == 0 (the others carried exact zeros
+// in the composition's zero-padded slice gradient, and acc + 0 == acc: acc is never -0).  dmem rows have pitch ldm.
+// Thread = (b, n, 4 columns of [text | spk | emo]).
+__global__ __launch_bounds__(256) void lr_memory_bwd_kernel(
+    const float* __restrict__ dmem, const int32_t* __restrict__ cs, const int64_t* __restrict__ valid,
+    float* __restrict__ d_aug, float* __restrict__ d_spk, float* __restrict__ d_emo, int B, int N, int Tp, int r, int dt,
+    int ds, int de, long long ldm) {
+  const int W4 = (dt + ds + de) >> 2;
+  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (long long)B * N * W4) return;
+  const int col = (int)(g % W4) << 2;
+  const long long bn = g / W4;
+  const int n = (int)(bn % N), b = (int)(bn / N);
+  int s = cs[(long long)b * (N + 1) + n], e = cs[(long long)b * (N + 1) + n + 1];
+  if (e > Tp) e = Tp;
+  if (valid && e > (int)valid[b]) e = (int)valid[b];
+  if (s < 0) s = 0;
+  const float* base = dmem + (long long)b * (Tp / r) * ldm;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  float* out;
+  if (col < dt) {
+    for (int t = s; t < e; ++t) {
+      const int l = t / r, j = t - l * r;
+      const float4 d = *reinterpret_cast<const float4*>(base + l * ldm + j * dt + col);
+      acc.x += d.x; acc.y += d.y; acc.z += d.z; acc.w += d.w;
+    }
+    out = d_aug + bn * dt + col;
+  } else {
+    const bool is_spk = col < dt + ds;
+    const int off = is_spk ? r * dt + (col - dt) : r * dt + ds + (col - dt - ds);
+    for (int l = (s + r - 1) / r; l * r < e; ++l) {
+      const float4 d = *reinterpret_cast<const float4*>(base + l * ldm + off);
+      acc.x += d.x; acc.y += d.y; acc.z += d.z; acc.w += d.w;
+    }
+    out = is_spk ? d_spk + bn * ds + (col - dt) : d_emo + bn * de + (col - dt - ds);
+  }
+  *reinterpret_cast<float4*>(out) = acc;
+}
+
+static inline bool lrm_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int kantts_lr_memory_fwd(const float* aug, const float* spk, const float* emo, const int32_t* idx,
+                                    const int64_t* valid_lens, const float* pos_enc, float* memory, float* lr_text,
+                                    float* lr_spk, float* lr_emo, int B, int N, int Tp, int r, int d_t, int d_s, int d_e,
+                                    void* stream) {
+  if (!aug || !spk || !emo || !idx || !pos_enc || !memory || B < 0 || N < 1 || Tp < 0 || r < 1 || d_t < 1 || d_s < 1 ||
+      d_e < 1 || Tp % r)
+    return KANTTS_E_BADARG;
+  if ((d_t | d_s | d_e) & 3) return KANTTS_E_UNSUPPORTED;  // 16-byte accesses
+  for (const void* p : {(const void*)aug, (const void*)spk, (const void*)emo, (const void*)pos_enc, (const void*)memory,
+                        (const void*)lr_text, (const void*)lr_spk, (const void*)lr_emo})
+    if (!lrm_aligned16(p)) return KANTTS_E_UNSUPPORTED;
+  const long long total = (long long)B * Tp * ((d_t + d_s + d_e) >> 2);
+  if ((total + 255) / 256 > 0x7fffffffLL) return KANTTS_E_UNSUPPORTED;
+  if (total == 0) return KANTTS_OK;
+  hipLaunchKernelGGL(lr_memory_fwd_kernel, dim3((unsigned)kantts_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, aug,
+                     spk, emo, idx, valid_lens, pos_enc, memory, lr_text, lr_spk, lr_emo, B, N, Tp, r, d_t, d_s, d_e);
+  KANTTS_CHECK_LAUNCH();
+}
+
+extern "C" int kantts_lr_memory_bwd(const float* d_memory, long long ldm, const int32_t* cs, const int64_t* valid_lens,
+                                    float* d_aug, float* d_spk, float* d_emo, int B, int N, int Tp, int r, int d_t, int d_s,
+                                    int d_e, void* stream) {
+  if (!d_memory || !cs || !d_aug || !d_spk || !d_emo || B < 0 || N < 1 || Tp < 0 || r < 1 || d_t < 1 || d_s < 1 ||
+      d_e < 1 || Tp % r || ldm < (long long)r * d_t + d_s + d_e)
+    return KANTTS_E_BADARG;
+  if (((d_t | d_s | d_e) & 3) || (ldm & 3)) return KANTTS_E_UNSUPPORTED;
+  for (const void* p : {(const void*)d_memory, (const void*)d_aug, (const void*)d_spk, (const void*)d_emo})
+    if (!lrm_aligned16(p)) return KANTTS_E_UNSUPPORTED;
+  const long long total = (long long)B * N * ((d_t + d_s + d_e) >> 2);
+  if ((total + 255) / 256 > 0x7fffffffLL) return KANTTS_E_UNSUPPORTED;
+  if (total == 0) return KANTTS_OK;
+  hipLaunchKernelGGL(lr_memory_bwd_kernel, dim3((unsigned)kantts_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                     d_memory, cs, valid_lens, d_aug, d_spk, d_emo, B, N, Tp, r, d_t, d_s, d_e, ldm);
+  KANTTS_CHECK_LAUNCH();
+}
+
+// ------------------------------------------------------------------------------------------------
 // FSMN memory block (channels-last):  xm = x * keep;  y = keep * (sum_k w[c,k] xm[t+k-lp] + xm[t]) (+ res)
 // keep[b,t] = t < lens[b] (all ones when lens == NULL).  Block = one (b, 32-frame tile), thread = channel.
 // ROWS = true (kantts_fsmn_dwconv_fwd_rows): the tiles start at row r0 and only rows [r0, r1) are computed; a row sums its

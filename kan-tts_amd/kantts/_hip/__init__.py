@@ -432,6 +432,8 @@ def lib():
         L.kantts_lr_index.argtypes = [p, p, p, p, p, p, i, i, i, p]
         L.kantts_lr_gather_fwd.argtypes = [p, p, p, p, i, i, i, i, i, i, p]
         L.kantts_lr_gather_bwd.argtypes = [p, p, p, p, i, i, i, i, i, i, i, p]
+        L.kantts_lr_memory_fwd.argtypes = [p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, p]
+        L.kantts_lr_memory_bwd.argtypes = [p, ll, p, p, p, p, p, i, i, i, i, i, i, i, p]
         L.kantts_fsmn_dwconv_fwd.argtypes = [p, p, p, p, p, i, i, i, i, i, p]
         L.kantts_fsmn_dwconv_bwd.argtypes = [p, p, p, p, p, p, p, ll, i, i, i, i, i, p]
         L.kantts_fsmn_dwconv_bwd_ws.argtypes = [i, i, i, i]
@@ -549,7 +551,7 @@ EXPORTED_SYMBOLS = [
     "kantts_pnca_decode_range", "kantts_lstm_fwd_range", "kantts_fsmn_dwconv_fwd_rows",
     "kantts_pnca_decode_slots", "kantts_lstm_fwd_slots", "kantts_fsmn_dwconv_fwd_slots", "kantts_scatter_rows_f32",
     "kantts_nsf_source_rows", "kantts_nsf_downs_rows", "kantts_mel_handover_rows",
-    "kantts_mb_tail_rows", "kantts_sconv_sym_rows_launch",
+    "kantts_mb_tail_rows", "kantts_sconv_sym_rows_launch", "kantts_lr_memory_fwd", "kantts_lr_memory_bwd",
 ]
 
 

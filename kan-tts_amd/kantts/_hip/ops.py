@@ -576,11 +576,13 @@ class _FusedLinear(torch.autograd.Function):
 
 
 def linear(xs, weights, bias=None, *, mode=None, bias2=None, res=None, rowmask=None, relu=False, alpha=1.0,
-           drop_p=0.0, pad=0, dilation=1, T=0, out_bf16=False, ln_next=None):
+           drop_p=0.0, pad=0, dilation=1, T=0, out_bf16=False, ln_next=None, res_grad=None):
     """Functional entry: xs / weights are tensors or lists (see _FusedLinear).  In bf16 mode the contraction runs on
     the bf16-operand kernels (ops_bf16) whenever its extents allow; ``out_bf16`` then stores the result as bf16 (for
     outputs whose only consumers are contractions).  fp32 mode ignores it.  ``ln_next``: the nn.LayerNorm(128) of the
-    pre-LN sub-layer that consumes the output -- bf16 mode computes it in this launch's epilogue (ops_bf16.PreNorm)."""
+    pre-LN sub-layer that consumes the output -- bf16 mode computes it in this launch's epilogue (ops_bf16.PreNorm).
+    ``res_grad`` (ops_bf16.ResGradToken): the input is also the residual of the add that closes the layer; bf16 mode
+    takes that add's gradient into the input-gradient launch (fp32 mode leaves the token unarmed: autograd sums)."""
     xs = [xs] if torch.is_tensor(xs) else list(xs)
     weights = [weights] if torch.is_tensor(weights) else list(weights)
     if mode is None:
@@ -598,7 +600,7 @@ def linear(xs, weights, bias=None, *, mode=None, bias2=None, res=None, rowmask=N
             wbs = [ops_bf16.bf16_weight(w) for w in params]
         return ops_bf16.linear(xs, weights, wbs, bias, mode=mode, bias2=bias2, res=res, rowmask=rowmask, relu=relu,
                                alpha=alpha, drop_p=drop_p, pad=pad, dilation=dilation, T=T, out_bf16=out_bf16,
-                               ln_next=ln_next)
+                               ln_next=ln_next, res_grad=res_grad)
     xs = [x.float() if x.dtype != torch.float32 else x for x in xs]  # the segmented GEMM reads fp32 operands
     token = ops_bf16.RowMaskToken(rowmask) if (rowmask is not None and not relu and torch.is_grad_enabled()) else None
     opts = dict(nx=len(xs), mode=mode, relu=bool(relu), alpha=float(alpha), drop_p=float(drop_p), pad=int(pad),
@@ -1202,6 +1204,95 @@ class _LRGather(torch.autograd.Function):
 
 def lr_gather(x, idx, cs, valid_lens):
     return _LRGather.apply(x, idx, cs, valid_lens)
+
+
+class _LRMemoryDeclined(Exception):
+    """kantts_lr_memory_fwd returned KANTTS_E_UNSUPPORTED: the caller runs the composition."""
+
+
+class _LRMemory(torch.autograd.Function):
+    """(aug, spk, emo) -> (memory, LR_text, LR_spk, LR_emo) in one launch, and back in one (csrc/seq.hip:
+    kantts_lr_memory_fwd / _bwd).  The frame-level outputs are what the result dictionary hands out; gradients that arrive
+    through them (none in a training step) are added by the regulator's own backward launch."""
+
+    @staticmethod
+    def forward(ctx, aug, spk, emo, idx, cs, valid, pos_enc, r, want_frames):
+        B, N, dt = aug.shape
+        ds, de = spk.shape[-1], emo.shape[-1]
+        Tp = idx.shape[1]
+        dev = aug.device
+        mem = torch.empty((B, Tp // r, r * dt + ds + de), device=dev, dtype=torch.float32)
+        text = torch.empty((B, Tp, dt), device=dev, dtype=torch.float32)
+        fs = torch.empty((B, Tp, ds), device=dev, dtype=torch.float32) if want_frames else None
+        fe = torch.empty((B, Tp, de), device=dev, dtype=torch.float32) if want_frames else None
+        rc = lib().kantts_lr_memory_fwd(ptr(aug, torch.float32), ptr(spk, torch.float32), ptr(emo, torch.float32), ptr(idx),
+                                        ptr(valid), ptr(pos_enc, torch.float32), ptr(mem), ptr(text), ptr(fs), ptr(fe), B, N,
+                                        Tp, r, dt, ds, de, stream())
+        if rc == E_UNSUPPORTED:
+            raise _LRMemoryDeclined()
+        check(rc, "lr_memory_fwd")
+        ctx.save_for_backward(cs, valid)
+        ctx.cfg = (B, N, Tp, r, dt, ds, de)
+        ctx.set_materialize_grads(False)
+        return mem, text, fs, fe
+
+    @staticmethod
+    def backward(ctx, dmem, dtext, dfs, dfe):
+        cs, valid = ctx.saved_tensors
+        B, N, Tp, r, dt, ds, de = ctx.cfg
+        dev = cs.device
+        d_aug = torch.empty((B, N, dt), device=dev, dtype=torch.float32)
+        d_spk = torch.empty((B, N, ds), device=dev, dtype=torch.float32)
+        d_emo = torch.empty((B, N, de), device=dev, dtype=torch.float32)
+        if dmem is None:
+            for t in (d_aug, d_spk, d_emo):
+                t.zero_()
+        else:
+            L = Tp // r
+            # the gradient is read where it lies: any row pitch, e.g. the leading columns of a wider buffer
+            if not (dmem.stride(2) == 1 and (B == 1 or dmem.stride(0) == L * dmem.stride(1)) and dmem.stride(1) % 4 == 0
+                    and dmem.data_ptr() % 16 == 0):
+                dmem = dmem.contiguous()
+            check(lib().kantts_lr_memory_bwd(ptr(dmem, torch.float32), int(dmem.stride(1)), ptr(cs), ptr(valid), ptr(d_aug),
+                                             ptr(d_spk), ptr(d_emo), B, N, Tp, r, dt, ds, de, stream()), "lr_memory_bwd")
+        for g, dx, C in ((dtext, d_aug, dt), (dfs, d_spk, ds), (dfe, d_emo, de)):
+            if g is not None:
+                check(lib().kantts_lr_gather_bwd(ptr(_c(g), torch.float32), ptr(cs), ptr(valid), ptr(dx), B, N, Tp, C, C, 0,
+                                                 1, stream()), "lr_gather_bwd")
+        return d_aug, d_spk, d_emo, None, None, None, None, None, None
+
+
+LR_MEMORY = {"on": not os.environ.get("KANTTS_NO_LR_MEMORY")}  # A/B switch: the hand-over as one launch each way
+
+
+def lr_memory_entry_points():
+    """True when the loaded library exports the one-launch hand-over (the numpy model of the C ABI does not)."""
+    return hasattr(lib(), "kantts_lr_memory_fwd")
+
+
+def lr_memory(aug, spk, emo, idx, cs, valid_lens, pos_enc, r, frames=None):
+    """The decoder's memory (B, Tp / r, r * d_t + d_s + d_e) = [LFR-grouped (regulated aug + pos_enc) | regulated spk of a
+    group's first frame | regulated emo of it], with the frame-level tensors it is made of: returns (memory, LR_text, LR_spk,
+    LR_emo).  One launch forward and one backward; the composition (three lr_gather, the add, the reshapes, torch.cat) runs
+    instead when the launch declines the shape (widths that are no multiples of 4) -- both give the same bits.
+    ``frames`` = (LR_spk, LR_emo) when the caller already has them (formed beside the encoder): they are handed back as they
+    are and the launch does not write them."""
+    B, Tp = idx.shape
+    if (LR_MEMORY["on"] and Tp % r == 0 and not pos_enc.requires_grad and lr_memory_entry_points()
+            and tuple(pos_enc.shape) == (B, Tp, aug.shape[-1])
+            and all(t.dtype == torch.float32 for t in (aug, spk, emo, pos_enc))):
+        try:
+            mem, text, fs, fe = _LRMemory.apply(_c(aug), _c(spk), _c(emo), idx, cs, valid_lens, _c(pos_enc), int(r),
+                                                frames is None)
+            return (mem, text) + ((fs, fe) if frames is None else tuple(frames))
+        except _LRMemoryDeclined:
+            pass
+    text = lr_gather(aug, idx, cs, valid_lens) + pos_enc
+    fs, fe = frames if frames is not None else (lr_gather(spk, idx, cs, valid_lens), lr_gather(emo, idx, cs, valid_lens))
+    ds, de = spk.shape[-1], emo.shape[-1]
+    mem = torch.cat([text.reshape(B, -1, r * text.shape[-1]), fs.reshape(B, -1, r * ds)[:, :, :ds],
+                     fe.reshape(B, -1, r * de)[:, :, :de]], dim=-1)
+    return mem, text, fs, fe
 
 
 # ================================================================================================
@@ -2420,10 +2511,11 @@ class _SinAddAct(torch.autograd.Function):
 
 
 class _Dropout2Add(torch.autograd.Function):
-    """x * keep1 * keep2 (+ res) with regenerated masks (kantts_dropout2_add); backward = the same kernel on dy."""
+    """x * keep1 * keep2 (+ res) with regenerated masks (kantts_dropout2_add); backward = the same kernel on dy.
+    ``res_grad``: an armed ops_bf16.ResGradToken receives the residual's gradient instead of autograd."""
 
     @staticmethod
-    def forward(ctx, x, res, p1, p2):
+    def forward(ctx, x, res, p1, p2, res_grad=None):
         from . import rng_ptr
 
         x = _c(x)
@@ -2434,6 +2526,7 @@ class _Dropout2Add(torch.autograd.Function):
         check(lib().kantts_dropout2_add(ptr(x, torch.float32), ptr(r, torch.float32), ptr(y), x.numel(), float(p1), s1,
                                         float(p2), s2, rng_ptr(x.device), stream()), "dropout2_add")
         ctx.cfg = (float(p1), s1, float(p2), s2, res is not None)
+        ctx.res_grad = res_grad if (res is not None and res_grad is not None and res_grad.armed) else None
         return y
 
     @staticmethod
@@ -2447,10 +2540,14 @@ class _Dropout2Add(torch.autograd.Function):
             dx = torch.empty_like(dy)
             check(lib().kantts_dropout2_add(ptr(dy, torch.float32), None, ptr(dx), dy.numel(), p1, s1, p2, s2,
                                             rng_ptr(dy.device), stream()), "dropout2_add")
-        return dx, (dy if has_res and ctx.needs_input_grad[1] else None), None, None
+        d_res = dy if has_res and ctx.needs_input_grad[1] else None
+        if d_res is not None and ctx.res_grad is not None:
+            # the contraction that reads the same tensor adds it in its input-gradient launch (ResGradToken)
+            ctx.res_grad.dres, d_res = d_res, None
+        return dx, d_res, None, None, None
 
 
-def dropout2_add(x, p1=0.0, p2=0.0, res=None):
+def dropout2_add(x, p1=0.0, p2=0.0, res=None, res_grad=None):
     """dropout_{p2}(dropout_{p1}(x)) (+ res) in one pass (fp32, numel % 4 == 0); plain add / identity when both p are 0."""
     if p1 <= 0.0 and p2 <= 0.0:
         return x if res is None else x + res
@@ -2459,7 +2556,7 @@ def dropout2_add(x, p1=0.0, p2=0.0, res=None):
 
         y = F.dropout(F.dropout(x, p1, True), p2, True)
         return y if res is None else y + res
-    return _Dropout2Add.apply(x, res, float(p1), float(p2))
+    return _Dropout2Add.apply(x, res, float(p1), float(p2), res_grad)
 
 
 def sin_add(x, act_slope=None):

@@ -227,6 +227,19 @@ class ReluGateToken:
         self.scale = 1.0
 
 
+class ResGradToken:
+    """x feeds a contraction AND, as the residual, the add that closes the same layer (kantts/models/sambert/fsmn.py:
+    x -> FFN -> memory block -> dropout (+ x)).  Autograd would sum the two gradients of x with one elementwise launch per
+    layer, on the backward chain.  Instead the add's backward (ops._Dropout2Add) deposits the residual's gradient here and
+    reports none; the contraction's input-gradient launch, which autograd can only reach after it, takes it in through its
+    ``res`` port: dx = dz W + dres, the same fp32 add.  ``armed`` is set by the contraction that will do so (a single fp32
+    operand on the bf16 kernels); unarmed, both sides behave as if the token were not there."""
+    __slots__ = ("armed", "dres")
+
+    def __init__(self):
+        self.armed, self.dres = False, None
+
+
 def _same_tensor(a, b):
     return a is not None and b is not None and a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.dtype == b.dtype
 
@@ -704,9 +717,17 @@ class _FusedLinearB(torch.autograd.Function):
                                 ldg=kk, **gkw):
                         rtok.dz = dx
                         dxs[k] = dx
+                rg = opts.get("res_grad")
+                if rg is not None and rg.dres is not None and not (needs[5 + k] and dxs[k] is None):
+                    raise RuntimeError("a residual gradient was handed to this contraction's input-gradient launch "
+                                       "(ResGradToken), which does not run")
                 if needs[5 + k] and dxs[k] is None:
                     dx = torch.empty(x.shape, device=x.device, dtype=ctx.x_dtypes[k])
-                    if not bgemm_nt([(dz, N, (wb, woff), wld, N, 0)], M, kk, dx, kk, b_kn=True, a_drop_ld=N, **kw):
+                    rkw = {}
+                    if rg is not None and rg.dres is not None:  # the residual branch's gradient of x rides in (ResGradToken)
+                        rkw = dict(res=_c(rg.dres).view(M, kk), ldr=kk)
+                        rg.dres = None
+                    if not bgemm_nt([(dz, N, (wb, woff), wld, N, 0)], M, kk, dx, kk, b_kn=True, a_drop_ld=N, **rkw, **kw):
                         raise RuntimeError("bgemm_nt declined an input gradient")
                     dxs[k] = dx
                 need_w = needs[5 + nx] if mode == "concat" else needs[5 + nx + k]
@@ -730,7 +751,7 @@ class _FusedLinearB(torch.autograd.Function):
 
 
 def linear(xs, weights, wbs, bias, *, mode, bias2, res, rowmask, relu, alpha, drop_p, pad, dilation, T, out_bf16,
-           ln_next=None):
+           ln_next=None, res_grad=None):
     token = RowMaskToken(rowmask) if (rowmask is not None and not relu and torch.is_grad_enabled()) else None
     pre = PreNorm(ln_next) if (ln_next is not None and PRENORM["on"] and not relu and not out_bf16
                                and weights[0].shape[0] == 128) else None
@@ -741,6 +762,10 @@ def linear(xs, weights, wbs, bias, *, mode, bias2, res, rowmask, relu, alpha, dr
             opts["relugate_self"] = ReluGateToken()
         if len(xs) == 1 and mode != "conv" and xs[0].dtype == BF16:
             opts["relugate"] = getattr(xs[0], "_kantts_relugate", None)
+    if (res_grad is not None and torch.is_grad_enabled() and len(xs) == 1 and mode != "conv"
+            and xs[0].dtype == torch.float32 and xs[0].requires_grad and xs[0].shape[-1] % 4 == 0):
+        res_grad.armed = True  # the input gradient takes the generic launch below: no LayerNorm / ReLU-gate epilogue on it
+        opts["res_grad"] = res_grad
     if LNBWD["on"] and torch.is_grad_enabled():
         if res is not None:  # this launch's backward sees the residual branch's gradient first
             opts["lnbwd_res"] = getattr(res, "_kantts_lnbwd_res", None)

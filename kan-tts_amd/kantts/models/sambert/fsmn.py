@@ -1,8 +1,15 @@
 """FSMN encoder on HIP kernels (reference kantts/models/sambert/fsmn.py:8-124), channels-last."""
+import os
+
+import torch
 import torch.nn as nn
 
 from kantts._hip import ops
+from kantts._hip.ops_bf16 import ResGradToken
 from kantts.models.utils import SeqInfo
+
+
+_RES_GRAD_PORT = not os.environ.get("KANTTS_NO_RES_GRAD_PORT")  # A/B switch: the residual's gradient through the res port
 
 
 class FeedForwardNet(nn.Module):
@@ -16,10 +23,11 @@ class FeedForwardNet(nn.Module):
         self.w_2 = nn.Conv1d(d_hid, d_out, k_out, padding=(k_out - 1) // 2, bias=False)
         self.dropout = nn.Dropout(dropout)
 
-    def forward(self, x):
+    def forward(self, x, res_grad=None):
+        """``res_grad``: x is also the residual of the layer this FFN opens (FsmnEncoderV2.forward)."""
         p = float(self.dropout.p) if self.training else 0.0
         # the hidden activation only feeds the second contraction: bf16 in bf16 mode (fp32 mode ignores the flag)
-        h = ops.linear(x, self.w_1.weight, self.w_1.bias, relu=True, drop_p=p, out_bf16=True)
+        h = ops.linear(x, self.w_1.weight, self.w_1.bias, relu=True, drop_p=p, out_bf16=True, res_grad=res_grad)
         return ops.linear(h, self.w_2.weight, None)
 
 
@@ -38,7 +46,7 @@ class MemoryBlockV2(nn.Module):
         self.conv_dw = nn.Conv1d(d, d, filter_size, stride=1, padding=0, groups=d, bias=False)
         self.dropout = nn.Dropout(dropout)
 
-    def forward(self, input, mask=None, res=None, outer_p=0.0):
+    def forward(self, input, mask=None, res=None, outer_p=0.0, res_grad=None):
         """``outer_p``: the encoder's own dropout on this block's output (reference :118), applied in the same pass as
         the block's dropout and the residual add (kantts_dropout2_add)."""
         info = SeqInfo.of(mask)
@@ -46,7 +54,7 @@ class MemoryBlockV2(nn.Module):
         p = float(self.dropout.p) if self.training else 0.0
         if p > 0.0 or outer_p > 0.0:
             out = ops.fsmn_memory(input, self.conv_dw.weight, lens, self.lp)
-            return ops.dropout2_add(out, p, outer_p, res)
+            return ops.dropout2_add(out, p, outer_p, res, res_grad=res_grad)
         return ops.fsmn_memory(input, self.conv_dw.weight, lens, self.lp, res=res)
 
 
@@ -71,7 +79,11 @@ class FsmnEncoderV2(nn.Module):
         p = float(self.dropout) if self.training else 0.0
         x = ops.dropout2_add(input, p) if p > 0 else input
         for ffn, memory_block in zip(self.ffn_lst, self.memory_block_lst):
-            context = ffn(x)
             same = self.num_memory_units == x.size(-1)
-            x = memory_block(context, info, res=x if same else None, outer_p=p)
+            # x has two readers, the FFN and the residual add: backward, the add's gradient rides into the input-gradient
+            # launch of the FFN's first contraction instead of one elementwise add per layer (ops_bf16.ResGradToken)
+            fold = _RES_GRAD_PORT and same and p > 0 and torch.is_grad_enabled()
+            tok = ResGradToken() if fold else None
+            context = ffn(x, res_grad=tok)
+            x = memory_block(context, info, res=x if same else None, outer_p=p, res_grad=tok)
         return x

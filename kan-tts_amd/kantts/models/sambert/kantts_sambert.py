@@ -343,15 +343,22 @@ class VarianceAdaptor(nn.Module):
             plan = self.length_regulator.index(durations, max_len=max_out_len)
             pos_enc = self.position_term(plan, out_info)
         LR_length_rounded = plan[3]
-        LR_text_outputs, _ = self.length_regulator(aug, durations, masks=out_info, plan=plan)
-        if teacher_plan is not None and "LR_emo" in teacher_plan:
-            LR_emo_outputs, LR_spk_outputs = teacher_plan["LR_emo"], teacher_plan["LR_spk"]
+        # the three regulators, the position add, the LFR grouping and the concatenation into the decoder's memory
+        # [text (r*d) | spk of a group's first frame | emo of it]: one launch forward, one backward (ops.lr_memory)
+        idx, cs, max_len = plan[0], plan[2], plan[5]
+        if len(plan) > 6:
+            valid = plan[6]
+        elif out_info is not None:
+            valid = torch.clamp(out_info.lens64, max=max_len)
         else:
-            LR_emo_outputs, _ = self.length_regulator(inputs_emo_embedding, durations, masks=out_info, plan=plan)
-            LR_spk_outputs, _ = self.length_regulator(inputs_spk_embedding, durations, masks=out_info, plan=plan)
-        LR_text_outputs = LR_text_outputs + pos_enc
+            valid = torch.full_like(LR_length_rounded, max_len) if plan[4] != max_len else None
+        frames = None
+        if teacher_plan is not None and "LR_emo" in teacher_plan:  # formed beside the encoder: they stay off the main chain
+            frames = (teacher_plan["LR_spk"], teacher_plan["LR_emo"])
+        memory, LR_text_outputs, LR_spk_outputs, LR_emo_outputs = ops.lr_memory(
+            aug, inputs_spk_embedding, inputs_emo_embedding, idx, cs, valid, pos_enc, self.length_regulator.r, frames=frames)
         return (LR_text_outputs, LR_emo_outputs, LR_spk_outputs, LR_length_rounded, log_duration_predictions,
-                pitch_predictions, energy_predictions)
+                pitch_predictions, energy_predictions, memory)
 
 
 class MelPNCADecoder(nn.Module):
@@ -691,7 +698,7 @@ class KanTtsSAMBERT(nn.Module):
                 max_out_len = mel_targets.size(1)
                 out_info = tplan["out_info"] if tplan is not None else SeqInfo(output_lengths, max_out_len)
             (LR_text_outputs, LR_emo_outputs, LR_spk_outputs, LR_length_rounded, log_duration_predictions,
-             pitch_predictions, energy_predictions) = self.variance_adaptor(
+             pitch_predictions, energy_predictions, memory) = self.variance_adaptor(
                 text_hid, emo_hid, spk_hid, masks=in_info, output_masks=out_info, duration_targets=duration_targets,
                 pitch_targets=pitch_targets, energy_targets=energy_targets, max_out_len=max_out_len, teacher_plan=tplan)
         Tp = LR_text_outputs.size(1)
@@ -704,13 +711,6 @@ class KanTtsSAMBERT(nn.Module):
             # the reference infers one utterance at a time (mask None); in a batch every sequence keeps its own
             # decoder length and band width so that batched inference equals per-utterance inference
             lfr_info = SeqInfo((LR_length_rounded + r - 1) // r, Tp // r)
-        # LFR: group r frames; memory = [text (r*d) | spk of the first frame | emo of the first frame]
-        d_t, d_s, d_e = text_hid.shape[-1], spk_hid.shape[-1], emo_hid.shape[-1]
-        memory = torch.cat([
-            LR_text_outputs.reshape(batch_size, -1, r * d_t),
-            LR_spk_outputs.reshape(batch_size, -1, r * d_s)[:, :, :d_s],
-            LR_emo_outputs.reshape(batch_size, -1, r * d_e)[:, :, :d_e],
-        ], dim=-1)
         if tplan is not None:
             bw_val = tplan["bw_val"]
         elif duration_targets is not None:
