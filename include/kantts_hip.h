@@ -84,7 +84,9 @@ typedef struct kantts_gemm_seg {
   int32_t a_mode, b_mode; /* staging layout hints, see csrc/gemm.hip: 0 scalar/lanes along k, 1 scalar/lanes
                           along rows, 2 float4 along k (needs unit k stride, klen % 4 == 0, 16-byte aligned
                           rows, no token map on kk), 3 float4 along rows (unit row stride, extent % 4 == 0,
-                          no token map on the row index).  0 is always valid. */
+                          no token map on the row index; every float4 16-byte aligned as well: base, gate, k stride,
+                          group stride, and b_tap when there are several taps).  0 is always valid.  With kmask set the launcher stages
+                          every a_mode == 2 segment as a_mode 0 (the mask is per element of k, the float4 is not). */
 } kantts_gemm_seg;
 
 typedef struct kantts_gemm_args {
@@ -124,6 +126,15 @@ typedef struct kantts_gemm_args {
 } kantts_gemm_args;
 
 int kantts_gemm_seg_launch(const kantts_gemm_args* args_host, void* stream);
+
+/* What kantts_gemm_seg_launch would do with this descriptor, without launching (the launcher takes its choice from the same
+   function, KANTTS_GEMM_* switches included).  Returns KANTTS_OK unless a pointer is NULL.
+   out[0]: <0 the refusal code, 0 nothing to launch (M == 0 or N == 0), 1 generic MFMA kernel, 2 fast kernel,
+           3 scalar reference kernel
+   out[1]: BM (32/64)   out[2]: BIGK   out[3]: A_ROW   out[4]: B_ROW   out[5]: GATE   out[6]: coalesced epilogue (vec_out)
+   out[7]: segments whose a_mode 2 was demoted to 0 because kmask is set
+   (out points to eight words) */
+int kantts_gemm_plan(const kantts_gemm_args* args_host, int32_t* out);
 
 /* ------------------------------------------------------------------------------------------
  * LayerNorm (eps inside sqrt, biased variance).  Replaces nn.LayerNorm(eps=1e-6) at

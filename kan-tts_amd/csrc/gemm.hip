@@ -437,53 +437,86 @@ __global__ void gemm_seg_ref_kernel(const kantts_gemm_args g) {
     *dst = v;
 }
 
-int kantts_gemm_try_fast(const kantts_gemm_args& g, hipStream_t st);  // gemm_fast.hip
+// gemm_fast.hip: whether (and with which instantiation) the fast kernels take a validated descriptor, and their launch
+int kantts_gemm_fast_plan(const kantts_gemm_args& g, int32_t out[8]);
+void kantts_gemm_fast_launch(const kantts_gemm_args& g, const int32_t plan[8], hipStream_t st);
 
-extern "C" int kantts_gemm_seg_launch(const kantts_gemm_args* a, void* stream) {
-  if (!a || a->nseg < 1 || a->nseg > KANTTS_GEMM_MAX_SEG || a->M < 0 || a->N < 0 || !a->c) return KANTTS_E_BADARG;
-  if (a->M == 0 || a->N == 0) return KANTTS_OK;
-  int splitk = a->splitk < 1 ? 1 : a->splitk;
-  int groups = a->groups < 1 ? 1 : a->groups;
-  if (splitk > 1 && (!a->accumulate || a->relu || a->out_act || a->gate || a->drop_p > 0.f)) return KANTTS_E_BADARG;
+// The one place where a descriptor is validated and its kernel chosen: kantts_gemm_seg_launch launches what this
+// returns, kantts_gemm_plan reports it.  `g` becomes the launcher's private copy (splitk / groups normalised, a_mode
+// demoted under kmask); `out` as documented for kantts_gemm_plan.  Returns out[0].
+static int gemm_make_plan(const kantts_gemm_args* a, kantts_gemm_args& g, int32_t out[8]) {
+  for (int k = 0; k < 8; ++k) out[k] = 0;
+  auto refuse = [&](int code) { return out[0] = code; };
+  if (!a || a->nseg < 1 || a->nseg > KANTTS_GEMM_MAX_SEG || a->M < 0 || a->N < 0 || !a->c) return refuse(KANTTS_E_BADARG);
+  if (a->M == 0 || a->N == 0) return 0;
+  const int splitk = a->splitk < 1 ? 1 : a->splitk;
+  const int groups = a->groups < 1 ? 1 : a->groups;
+  if (splitk > 1 && (!a->accumulate || a->relu || a->out_act || a->gate || a->drop_p > 0.f)) return refuse(KANTTS_E_BADARG);
   for (int s = 0; s < a->nseg; ++s) {
     const kantts_gemm_seg& sg = a->seg[s];
-    if (!sg.a || !sg.b || sg.klen < 0 || sg.ntaps < 1) return KANTTS_E_BADARG;
+    if (!sg.a || !sg.b || sg.klen < 0 || sg.ntaps < 1) return refuse(KANTTS_E_BADARG);
     if ((sg.a_tok_axis && sg.a_Tq <= 0 && a->T <= 0) || (sg.b_tok_axis && sg.b_Tq <= 0 && a->T <= 0))
-      return KANTTS_E_BADARG;
+      return refuse(KANTTS_E_BADARG);
   }
-  int ztaps = a->z_taps > 0 ? a->z_taps : 1;
-  if (a->z_taps > 0 && (a->nseg != 1 || a->z_taps != a->seg[0].ntaps)) return KANTTS_E_BADARG;
-  if ((long long)groups * splitk * ztaps > 65535) return KANTTS_E_BADARG;
-  kantts_gemm_args g = *a;
+  const int ztaps = a->z_taps > 0 ? a->z_taps : 1;
+  if (a->z_taps > 0 && (a->nseg != 1 || a->z_taps != a->seg[0].ntaps)) return refuse(KANTTS_E_BADARG);
+  if ((long long)groups * splitk * ztaps > 65535) return refuse(KANTTS_E_BADARG);
+  if (a->precision < 0 || a->precision > 2) return refuse(KANTTS_E_BADARG);
+  g = *a;
   g.splitk = splitk;
   g.groups = groups;
-  hipStream_t st = (hipStream_t)stream;
-  static const bool no_fast = getenv("KANTTS_GEMM_NOFAST") != nullptr;
-  if (!no_fast && g.precision != 2 && kantts_gemm_try_fast(g, st)) {
-    KANTTS_CHECK_LAUNCH();
-  }
+  // kmask is per element of k: the float4-along-k staging of A tests (generic kernel) or knows (fast kernels) only whole
+  // vectors, so such segments are staged with the scalar layout, which masks every element
+  if (g.kmask)
+    for (int s = 0; s < g.nseg; ++s)
+      if (g.seg[s].a_mode == 2) {
+        g.seg[s].a_mode = 0;
+        out[7]++;
+      }
   if (g.precision == 2) {
     g.splitk = 1;
+    return out[0] = 3;
+  }
+  static const bool no_fast = getenv("KANTTS_GEMM_NOFAST") != nullptr;
+  if (!no_fast && kantts_gemm_fast_plan(g, out)) return out[0] = 2;
+  // 32-row tiles when 64-row tiles would leave most of the 256 CUs idle
+  const long long blocks64 = (long long)kantts_cdiv(g.N, G_BN) * kantts_cdiv(g.M, 64) * groups * splitk * ztaps;
+  out[1] = blocks64 < 512 ? 32 : 64;
+  return out[0] = 1;
+}
+
+extern "C" int kantts_gemm_plan(const kantts_gemm_args* a, int32_t out[8]) {
+  if (!a || !out) return KANTTS_E_BADARG;
+  kantts_gemm_args g;
+  gemm_make_plan(a, g, out);
+  return KANTTS_OK;
+}
+
+extern "C" int kantts_gemm_seg_launch(const kantts_gemm_args* a, void* stream) {
+  kantts_gemm_args g;
+  int32_t plan[8];
+  const int kind = gemm_make_plan(a, g, plan);
+  if (kind <= 0) return kind;  // a refusal, or nothing to launch (M == 0 / N == 0)
+  hipStream_t st = (hipStream_t)stream;
+  const int ztaps = g.z_taps > 0 ? g.z_taps : 1;
+  if (kind == 2) {
+    kantts_gemm_fast_launch(g, plan, st);
+  } else if (kind == 3) {
     long long total = (long long)g.M * g.N;
-    hipLaunchKernelGGL(gemm_seg_ref_kernel, dim3(kantts_cdiv(total, 256), groups * ztaps), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(gemm_seg_ref_kernel, dim3(kantts_cdiv(total, 256), g.groups * ztaps), dim3(256), 0, st, g);
   } else {
-    // 32-row tiles when 64-row tiles would leave most of the 256 CUs idle
-    const long long blocks64 = (long long)kantts_cdiv(g.N, G_BN) * kantts_cdiv(g.M, 64) * groups * splitk * ztaps;
-    const bool small = blocks64 < 512;
-    const int bm = small ? 32 : 64;
-    dim3 grid(kantts_cdiv(g.N, G_BN), kantts_cdiv(g.M, bm), groups * splitk * ztaps);
+    const bool small = plan[1] == 32;
+    dim3 grid(kantts_cdiv(g.N, G_BN), kantts_cdiv(g.M, plan[1]), g.groups * g.splitk * ztaps);
     if (g.precision == 1) {
       if (small)
         hipLaunchKernelGGL((gemm_seg_mfma_kernel<true, 32>), grid, dim3(G_THREADS), 0, st, g);
       else
         hipLaunchKernelGGL((gemm_seg_mfma_kernel<true, 64>), grid, dim3(G_THREADS), 0, st, g);
-    } else if (g.precision == 0) {
+    } else {
       if (small)
         hipLaunchKernelGGL((gemm_seg_mfma_kernel<false, 32>), grid, dim3(G_THREADS), 0, st, g);
       else
         hipLaunchKernelGGL((gemm_seg_mfma_kernel<false, 64>), grid, dim3(G_THREADS), 0, st, g);
-    } else {
-      return KANTTS_E_BADARG;
     }
   }
   KANTTS_CHECK_LAUNCH();

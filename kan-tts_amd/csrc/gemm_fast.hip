@@ -514,45 +514,31 @@ static void launch_fast3(const kantts_gemm_args& g, bool a_row, bool b_row, dim3
 }
 
 template <bool BF16, int BM, bool BIGK>
-static void launch_fast2(const kantts_gemm_args& g, bool a_row, bool b_row, dim3 grid, hipStream_t st) {
-  bool gate = false;
-  for (int s = 0; s < g.nseg; ++s) gate = gate || (g.seg[s].a_gate != nullptr);
-  if (gate)
-    launch_fast3<BF16, BM, BIGK, true>(g, a_row, b_row, grid, st);
+static void launch_fast2(const kantts_gemm_args& g, const int32_t plan[8], dim3 grid, hipStream_t st) {
+  if (plan[5])
+    launch_fast3<BF16, BM, BIGK, true>(g, plan[3] != 0, plan[4] != 0, grid, st);
   else
-    launch_fast3<BF16, BM, BIGK, false>(g, a_row, b_row, grid, st);
+    launch_fast3<BF16, BM, BIGK, false>(g, plan[3] != 0, plan[4] != 0, grid, st);
 }
 
 template <bool BF16, int BM>
-static void launch_fast(const kantts_gemm_args& g, bool a_row, bool b_row, dim3 grid, hipStream_t st) {
-  long long ktot = 0;
-  int kmin = 1 << 30;
-  for (int s = 0; s < g.nseg; ++s) {
-    ktot += (long long)g.seg[s].klen * g.seg[s].ntaps;
-    kmin = g.seg[s].klen < kmin ? g.seg[s].klen : kmin;
-  }
-  static const char* force_bk = getenv("KANTTS_GEMM_BIGK");
-  // a reduction tile never spans two taps / segments: deep tiles only pay when every run is at least one tile
-  bool big = (ktot >= 512) && (kmin >= (BF16 ? 128 : 64));
-  if (force_bk) big = (force_bk[0] == '1');
-  if (big)
-    launch_fast2<BF16, BM, true>(g, a_row, b_row, grid, st);
+static void launch_fast(const kantts_gemm_args& g, const int32_t plan[8], dim3 grid, hipStream_t st) {
+  if (plan[2])
+    launch_fast2<BF16, BM, true>(g, plan, grid, st);
   else
-    launch_fast2<BF16, BM, false>(g, a_row, b_row, grid, st);
+    launch_fast2<BF16, BM, false>(g, plan, grid, st);
 }
 
-// Returns 1 when the launch was taken by a fast kernel, 0 when the descriptor does not qualify.
-int kantts_gemm_try_fast(const kantts_gemm_args& g_in, hipStream_t st) {
-  if (g_in.precision > 1) return 0;
-#ifdef F_DEBUG
-  kantts_gemm_args g = g_in;
-  static const char* dbg_env = getenv("KANTTS_GEMM_DBG");
-  const int dbg_mask = dbg_env ? atoi(dbg_env) : 0;
-#else
-  const kantts_gemm_args& g = g_in;
-#endif
+// Whether the fast kernels take the (validated, normalised) descriptor, and which instantiation: returns 1 and fills
+// out[1] BM, out[2] BIGK, out[3] A_ROW, out[4] B_ROW, out[5] GATE, out[6] coalesced epilogue; 0 when it does not qualify.
+// gemm.hip's gemm_make_plan is the only caller: the launcher and kantts_gemm_plan both go through it.
+int kantts_gemm_fast_plan(const kantts_gemm_args& g, int32_t out[8]) {
+  if (g.precision > 1) return 0;
   const int am = g.seg[0].a_mode, bm = g.seg[0].b_mode;
   if (am < 2 || bm < 2) return 0;
+  bool gate = false;
+  long long ktot = 0;
+  int kmin = 1 << 30;
   for (int s = 0; s < g.nseg; ++s) {
     const kantts_gemm_seg& sg = g.seg[s];
     if (sg.a_mode != am || sg.b_mode != bm) return 0;
@@ -575,6 +561,9 @@ int kantts_gemm_try_fast(const kantts_gemm_args& g_in, hipStream_t st) {
     const long long ext_b = ((long long)g.N + 8) * llabs(sg.b_js) + b_ks_n * llabs(sg.b_ks);
     if (ext_a >= (1ll << 30) || ext_b >= (1ll << 30)) return 0;
     if (sg.a_is < 0 || sg.a_ks < 0 || sg.b_js < 0 || sg.b_ks < 0) return 0;
+    gate = gate || (sg.a_gate != nullptr);
+    ktot += (long long)sg.klen * sg.ntaps;
+    kmin = sg.klen < kmin ? sg.klen : kmin;
   }
   const int splitk = g.splitk < 1 ? 1 : g.splitk;
   const int groups = g.groups < 1 ? 1 : g.groups;
@@ -583,23 +572,51 @@ int kantts_gemm_try_fast(const kantts_gemm_args& g_in, hipStream_t st) {
   static const char* force_bm = getenv("KANTTS_GEMM_BM");
   bool small = blocks64 < 512;
   if (force_bm) small = (force_bm[0] == '3');
-  const int bmr = small ? 32 : 64;
-  dim3 grid(kantts_cdiv(g.N, F_BN), kantts_cdiv(g.M, bmr), splitk * groups * ztaps);
-  const bool a_row = (am == 3), b_row = (bm == 3);
+  static const char* force_bk = getenv("KANTTS_GEMM_BIGK");
+  // a reduction tile never spans two taps / segments: deep tiles only pay when every run is at least one tile
+  bool big = (ktot >= 512) && (kmin >= (g.precision == 1 ? 128 : 64));
+  if (force_bk) big = (force_bk[0] == '1');
+  out[1] = small ? 32 : 64;
+  out[2] = big;
+  out[3] = (am == 3);
+  out[4] = (bm == 3);
+  out[5] = gate;
+  // the condition under which gemm_fast_kernel takes its coalesced epilogue (vec_out there; ztap < 0 <=> no z_taps)
+#ifdef F_VARIANT_DIRECT_EPI
+  out[6] = 0;
+#else
+  out[6] = !g.accumulate && g.c_js == 1 && (g.c_is & 3) == 0 && ((uintptr_t)g.c & 15) == 0 &&
+           (!g.res || (g.r_js == 1 && (g.r_is & 3) == 0 && ((uintptr_t)g.res & 15) == 0)) && (g.N & 3) == 0 &&
+           groups <= 1 && !g.gate && g.z_taps <= 0;
+#endif
+  return 1;
+}
+
+// Launch the instantiation kantts_gemm_fast_plan chose.
+void kantts_gemm_fast_launch(const kantts_gemm_args& g_in, const int32_t plan[8], hipStream_t st) {
+#ifdef F_DEBUG
+  kantts_gemm_args g = g_in;
+  static const char* dbg_env = getenv("KANTTS_GEMM_DBG");
+  const int dbg_mask = dbg_env ? atoi(dbg_env) : 0;
+#else
+  const kantts_gemm_args& g = g_in;
+#endif
+  const int ztaps = g.z_taps > 0 ? g.z_taps : 1;
+  const bool small = plan[1] == 32;
+  dim3 grid(kantts_cdiv(g.N, F_BN), kantts_cdiv(g.M, plan[1]), g.splitk * g.groups * ztaps);
   const int prec = g.precision;
 #ifdef F_DEBUG
   g.precision |= dbg_mask << 8;
 #endif
   if (prec == 1) {
     if (small)
-      launch_fast<true, 32>(g, a_row, b_row, grid, st);
+      launch_fast<true, 32>(g, plan, grid, st);
     else
-      launch_fast<true, 64>(g, a_row, b_row, grid, st);
+      launch_fast<true, 64>(g, plan, grid, st);
   } else {
     if (small)
-      launch_fast<false, 32>(g, a_row, b_row, grid, st);
+      launch_fast<false, 32>(g, plan, grid, st);
     else
-      launch_fast<false, 64>(g, a_row, b_row, grid, st);
+      launch_fast<false, 64>(g, plan, grid, st);
   }
-  return 1;
 }

@@ -412,6 +412,7 @@ def lib():
         L.kantts_abi_version.restype = c_int
         L.kantts_target_arch.restype = c_char_p
         L.kantts_gemm_seg_launch.argtypes = [POINTER(GemmArgs), c_void_p]
+        L.kantts_gemm_plan.argtypes = [POINTER(GemmArgs), POINTER(c_int32 * 8)]
         i, f, p, ll, u64 = c_int, c_float, c_void_p, c_longlong, c_uint64
         L.kantts_layernorm_fwd.argtypes = [p, p, p, p, p, p, i, i, f, p]
         L.kantts_layernorm_bwd.argtypes = [p, p, p, p, p, p, p, p, i, i, p]
@@ -529,7 +530,7 @@ def lib():
 
 
 EXPORTED_SYMBOLS = [
-    "kantts_abi_version", "kantts_target_arch", "kantts_gemm_seg_launch", "kantts_layernorm_fwd",
+    "kantts_abi_version", "kantts_target_arch", "kantts_gemm_seg_launch", "kantts_gemm_plan", "kantts_layernorm_fwd",
     "kantts_layernorm_bwd", "kantts_attn_fwd", "kantts_attn_bwd", "kantts_pnca_attn_fwd", "kantts_pnca_attn_bwd", "kantts_lstm_fwd", "kantts_lstm_bwd",
     "kantts_embed_sum_fwd", "kantts_embed_sum_bwd", "kantts_lr_index", "kantts_lr_gather_fwd",
     "kantts_lr_gather_bwd", "kantts_fsmn_dwconv_fwd", "kantts_fsmn_dwconv_bwd", "kantts_fsmn_dwconv_bwd_ws", "kantts_masked_l1",
@@ -676,18 +677,19 @@ def _staging_mode(base, row_stride, k_stride, klen, rows, tok_axis, group_stride
 _gemm_log = {} if os.environ.get("KANTTS_GEMM_LOG") else None
 
 
-def gemm(segs, M, N, c, c_is, c_js, bias=None, bias2=None, res=None, r_is=0, r_js=0, rowmask=None, kmask=None,
-         a_rowsum=None, alpha=1.0, relu=False, accumulate=False, splitk=1, T=0, drop_p=0.0, drop_seed=0,
-         precision=None, c_off=0, groups=1, a_gs=0, b_gs=0, c_gs=0, bias_gs=0, r_gs=0, out_leaky=None, gate=None,
-         gate_slope=0.0, res_off=0, z_taps=0, c_tap=0):
+def gemm_args(segs, M, N, c, c_is, c_js, bias=None, bias2=None, res=None, r_is=0, r_js=0, rowmask=None, kmask=None,
+              a_rowsum=None, alpha=1.0, relu=False, accumulate=False, splitk=1, T=0, drop_p=0.0, drop_seed=0,
+              precision=None, c_off=0, groups=1, a_gs=0, b_gs=0, c_gs=0, bias_gs=0, r_gs=0, out_leaky=None, gate=None,
+              gate_slope=0.0, res_off=0, z_taps=0, c_tap=0):
+    """The kantts_gemm_args descriptor of a gemm(...) call (staging modes chosen here)."""
     g = GemmArgs()
     assert 1 <= len(segs) <= GEMM_MAX_SEG
     for k, s in enumerate(segs):
         s.a_mode = _staging_mode(s.a or 0, s.a_is, s.a_ks, s.klen, M, s.a_tok_axis, a_gs, s.a_gate)
         s.b_mode = _staging_mode((s.b or 0) + 0, s.b_js, s.b_ks, s.klen, N, 1 if False else (2 if s.b_tok_axis == 2 else 0),
                                  b_gs)
-        if s.b_mode == 2 and (s.b_tap % 4 != 0 and s.ntaps > 1):
-            s.b_mode = 0
+        if s.b_mode >= 2 and (s.b_tap % 4 != 0 and s.ntaps > 1):  # the float4 of a later tap would not be 16-byte aligned
+            s.b_mode = 0 if s.b_mode == 2 else 1
         g.seg[k] = s
     g.nseg, g.M, g.N, g.T = len(segs), int(M), int(N), int(T)
     if _gemm_log is not None:
@@ -717,6 +719,13 @@ def gemm(segs, M, N, c, c_is, c_js, bias=None, bias2=None, res=None, r_is=0, r_j
     g.precision = _precision["gemm"] if precision is None else precision
     g.drop_p, g.drop_seed = float(drop_p), int(drop_seed)
     g.seed_dev = rng_ptr(c.device) if (drop_p > 0 or any(s.a_drop_p > 0 for s in segs)) else None
+    return g
+
+
+def gemm(segs, M, N, c, c_is, c_js, **kw):
+    """kantts_gemm_seg_launch; the keywords are those of gemm_args."""
+    g = gemm_args(segs, M, N, c, c_is, c_js, **kw)
+    groups = kw.get("groups", 1)
     if _profile is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -725,6 +734,14 @@ def gemm(segs, M, N, c, c_is, c_js, bias=None, bias2=None, res=None, r_is=0, r_j
         _profile.append((e0, e1, 2.0 * M * N * max(1, groups) * sum(s.klen * s.ntaps for s in segs)))
         return
     check(lib().kantts_gemm_seg_launch(ctypes.byref(g), stream()), "gemm_seg")
+
+
+def gemm_plan(g):
+    """kantts_gemm_plan of a descriptor (gemm_args(...)): the eight words documented in include/kantts_hip.h --
+    [kind (< 0 refusal, 1 generic, 2 fast, 3 scalar reference), BM, BIGK, A_ROW, B_ROW, GATE, vec_out, demoted]."""
+    out = (c_int32 * 8)()
+    check(lib().kantts_gemm_plan(ctypes.byref(g), ctypes.byref(out)), "gemm_plan")
+    return list(out)
 
 
 E_UNSUPPORTED = -2

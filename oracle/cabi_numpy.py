@@ -188,6 +188,8 @@ class EmulatedLib:
                     Bm = _gather(s.b, boffs, bvalid)
                     if s.b_act:
                         Bm = np.where(Bm > 0, Bm, Bm * np.float32(s.b_slope))
+                    if g.precision == 1:  # bf16 MFMA inputs: the prepared operands are rounded, accumulation stays fp32
+                        A, Bm = _bf16_round(A), _bf16_round(Bm)
                     acc += A @ Bm.T
                     if si == 0:
                         rowsum += A.sum(axis=1)
