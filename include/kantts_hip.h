@@ -1518,6 +1518,57 @@ typedef struct {
 } kantts_nsf_downs_args;
 int kantts_nsf_downs_rows(const kantts_nsf_downs_args* args, void* stream);
 
+/* ---- The NSF excitation of chunked inference for NON-CAUSAL generators (csrc/nsf_source_sym.hip): the two entry points
+ * above for a network whose tensors are delayed and whose utterance ends (the rule of kantts_sconv_sym_rows_launch).  Both
+ * are per slot, fp32 in both precision modes, and read the device buffers a step of that layer reads:
+ *   n_s   = clamp(rows[s], 0, Tc)      frames of slot s in this call, flush frames included (rows == NULL: Tc)
+ *   end_s = end[s]                     frames of the slot's utterance; < 0: open.  end == NULL: every slot is open
+ *   pos_s = pos_in[s * pos_ss]         frames slot s consumed before this call (read only when end != NULL)
+ *   l_s   = n_s when end_s < 0, else clamp(end_s - pos_s, 0, n_s)      the frames of this call inside the utterance
+ *
+ * kantts_nsf_source_end_rows: `src` is the argument of kantts_nsf_source_rows, rule, shapes and state included, and the
+ * launch does for l_s frames of slot s exactly what that entry point does for n_s: the same bits of e, harm and state_out
+ * (state_out.cursor = cursor + l_s * hop: the source's cursor stops at the end, which is why pos comes from elsewhere).
+ * Frames at or beyond l_s of f0 / uv / noise are not loaded (they may hold NaN), samples at or beyond l_s * hop of e / harm
+ * are not written, l_s == 0 copies the state bit for bit.
+ * KANTTS_E_BADARG: args == NULL, end != NULL with pos_in == NULL, pos_ss < 0, and what kantts_nsf_source_rows answers with
+ * it for `src`; KANTTS_E_UNSUPPORTED: as there.  S <= 0: nothing is launched, KANTTS_OK. */
+typedef struct {
+  kantts_nsf_source_args src;
+  const int32_t* end;
+  const int32_t* pos_in;
+  long long pos_ss;
+} kantts_nsf_source_end_args;
+int kantts_nsf_source_end_rows(const kantts_nsf_source_end_args* args, void* stream);
+
+/* kantts_nsf_downs_sym_rows: all source_downs convolutions of a non-causal generator in one launch, stage i read lag[i]
+ * samples back.  `d` is the argument of kantts_nsf_downs_rows (stages, weights tap-major (k, C), outputs, history buffers
+ * and their stride), except that the history holds Hh samples, an argument.  With A_s = pos_s * hop:
+ *   E[s, t]        = d.e[s, t]               for 0 <= t < n_s * hop and (end_s < 0 or A_s + t < end_s * hop)
+ *                  = 0.0f, NOT loaded        for t >= 0 otherwise (flush frames: they may hold NaN)
+ *                  = d.hist_in[s, Hh + t]    for -Hh <= t < 0
+ *   d_i[s, q, c]   = bias_i[c] + sum_{j < k[i]} w_i[j][c] * E[s, q * u[i] - lag[i] + j],     q in [0, n_s * hop / u[i])
+ *   hist_out[s, h] = E[s, n_s * hop - Hh + h]   for h in [0, Hh)      (n_s == 0: a copy of hist_in[s])
+ * Rows q >= n_s * hop / u[i] of out_i are not written.  out_i is byte for byte the `res` of stage i's polyphase up-layer
+ * (kantts_sconv_sym_rows_launch with res_lag = 0), whose own window stores 0.0f where the true index is outside the
+ * utterance, whatever this formula gave there.  A torch Conv1d(1, C, k, stride u, padding p) whose output the up-layer
+ * holds D rows late is lag = D * u + p with w_i[j][c] = W[c, 0, j]; a zeroed history is its zero left pad, the zeros behind
+ * end_s * hop its right pad.  lag[i] = k[i] - 1, end == NULL and Hh = max_i (k[i] - 1) is kantts_nsf_downs_rows bit for bit
+ * (same tiles, same summation order).  The tile's window does not grow with the lag: neither lag nor Hh has a cap.
+ * KANTTS_E_BADARG: args == NULL, end != NULL with pos_in == NULL, pos_ss < 0, Hh < 0, lag[i] < k[i] - u[i] (a tap in the
+ * slot's future), lag[i] > Hh, d.e == NULL, Tc < 1, hop < 1, nstages < 1, a stage with a NULL w / out or u, k, C < 1,
+ * missing or equal history buffers with Hh > 0, hist_ss < Hh with S > 1.  KANTTS_E_UNSUPPORTED: nstages > 8, a stage
+ * whose u does not divide hop, k[i] > 8192.  S <= 0: nothing is launched. */
+typedef struct {
+  kantts_nsf_downs_args d;
+  const int32_t* end;
+  const int32_t* pos_in;
+  long long pos_ss;
+  int Hh;
+  int lag[8];
+} kantts_nsf_downs_sym_args;
+int kantts_nsf_downs_sym_rows(const kantts_nsf_downs_sym_args* args, void* stream);
+
 /* ---- The tail of a MULTI-BAND generator in chunked inference (csrc/mb_tail.hip), one launch: conv_post (causal, K taps,
  * step 1, Cin -> B sub-bands), tanh, and a PQMF synthesis that can be cut at any chunk boundary.  Per slot, driven by the
  * same device `rows` buffer and row_mul as kantts_sconv_rows_launch:

@@ -153,6 +153,17 @@ class NsfDownsArgs(Structure):
     ]
 
 
+class NsfSourceEndArgs(Structure):
+    """kantts_nsf_source_end_args (include/kantts_hip.h)."""
+    _fields_ = [("src", NsfSourceArgs), ("end", c_void_p), ("pos_in", c_void_p), ("pos_ss", c_longlong)]
+
+
+class NsfDownsSymArgs(Structure):
+    """kantts_nsf_downs_sym_args (include/kantts_hip.h)."""
+    _fields_ = [("d", NsfDownsArgs), ("end", c_void_p), ("pos_in", c_void_p), ("pos_ss", c_longlong), ("Hh", c_int32),
+                ("lag", c_int32 * 8)]
+
+
 class MbTailArgs(Structure):
     """kantts_mb_tail_args (include/kantts_hip.h); ``in_`` is the C field ``in``."""
     _fields_ = [
@@ -525,6 +536,8 @@ def lib():
         L.kantts_mel_handover_rows.argtypes = [p, p, p, p, i, i, i, i, i, f, f, f, f, p]
         L.kantts_mb_tail_rows.argtypes = [POINTER(MbTailArgs), c_void_p]
         L.kantts_sconv_sym_rows_launch.argtypes = [POINTER(SConvSymArgs), c_void_p]
+        L.kantts_nsf_source_end_rows.argtypes = [POINTER(NsfSourceEndArgs), c_void_p]
+        L.kantts_nsf_downs_sym_rows.argtypes = [POINTER(NsfDownsSymArgs), c_void_p]
         _lib = L
     return _lib
 
@@ -553,6 +566,7 @@ EXPORTED_SYMBOLS = [
     "kantts_pnca_decode_slots", "kantts_lstm_fwd_slots", "kantts_fsmn_dwconv_fwd_slots", "kantts_scatter_rows_f32",
     "kantts_nsf_source_rows", "kantts_nsf_downs_rows", "kantts_mel_handover_rows",
     "kantts_mb_tail_rows", "kantts_sconv_sym_rows_launch", "kantts_lr_memory_fwd", "kantts_lr_memory_bwd",
+    "kantts_nsf_source_end_rows", "kantts_nsf_downs_sym_rows",
 ]
 
 
@@ -1527,6 +1541,17 @@ def sconv_sym(x, hist_in, hist_out, w, out, *, S, Tc, Cin, N, K, step, hist_ss, 
     return True
 
 
+def _nsf_source_fill(g, f0, uv, state_in, state_out, w, e, S, Tc, hop, H1, sr, alpha, sigma, state_ss, bias, noise, harm, rows):
+    g.f0, g.uv, g.noise = ptr(f0, torch.float32), ptr(uv, torch.float32), ptr(noise, torch.float32)
+    g.w, g.bias = ptr(w, torch.float32), ptr(bias, torch.float32)
+    g.state_in, g.state_out = ptr(state_in, torch.int32), ptr(state_out, torch.int32)
+    g.e, g.harm, g.rows = ptr(e, torch.float32), ptr(harm, torch.float32), ptr(rows, torch.int32)
+    g.state_ss, g.S, g.Tc, g.hop, g.H1 = int(state_ss), int(S), int(Tc), int(hop), int(H1)
+    g.sr, g.alpha, g.sigma = float(sr), float(alpha), float(sigma)
+    if rows is not None and rows.numel() != int(S):
+        raise ValueError("rows must hold S = %d counts, got %d" % (int(S), rows.numel()))
+
+
 def nsf_source(f0, uv, state_in, state_out, w, e, *, S, Tc, hop, H1, sr, alpha, sigma, state_ss=NSF_STATE_WORDS, bias=None,
                noise=None, harm=None, rows=None):
     """The chunked NSF sine source (csrc/nsf_source.hip, kantts_nsf_source_rows; the rule is written out in
@@ -1536,14 +1561,7 @@ def nsf_source(f0, uv, state_in, state_out, w, e, *, S, Tc, hop, H1, sr, alpha, 
     projection; ``rows``: int32 device tensor of S per-slot frame counts (None: every slot advances by Tc).  Returns False
     when the kernel declines the shape."""
     g = NsfSourceArgs()
-    g.f0, g.uv, g.noise = ptr(f0, torch.float32), ptr(uv, torch.float32), ptr(noise, torch.float32)
-    g.w, g.bias = ptr(w, torch.float32), ptr(bias, torch.float32)
-    g.state_in, g.state_out = ptr(state_in, torch.int32), ptr(state_out, torch.int32)
-    g.e, g.harm, g.rows = ptr(e, torch.float32), ptr(harm, torch.float32), ptr(rows, torch.int32)
-    g.state_ss, g.S, g.Tc, g.hop, g.H1 = int(state_ss), int(S), int(Tc), int(hop), int(H1)
-    g.sr, g.alpha, g.sigma = float(sr), float(alpha), float(sigma)
-    if rows is not None and rows.numel() != int(S):
-        raise ValueError("rows must hold S = %d counts, got %d" % (int(S), rows.numel()))
+    _nsf_source_fill(g, f0, uv, state_in, state_out, w, e, S, Tc, hop, H1, sr, alpha, sigma, state_ss, bias, noise, harm, rows)
     rc = lib().kantts_nsf_source_rows(ctypes.byref(g), stream())
     if rc == E_UNSUPPORTED:
         return False
@@ -1551,12 +1569,8 @@ def nsf_source(f0, uv, state_in, state_out, w, e, *, S, Tc, hop, H1, sr, alpha, 
     return True
 
 
-def nsf_downs(e, hist_in, hist_out, stages, outs, *, S, Tc, hop, hist_ss, rows=None):
-    """Every excitation down-convolution of a generator in one launch (csrc/nsf_source.hip, kantts_nsf_downs_rows).
-    e (S, Tc * hop) fp32; ``stages``: a list of (u, k, C, w (k, C) fp32, bias (C) fp32 or None); ``outs``: one fp32 tensor
-    (S, Tc * hop / u, C) per stage; hist_in / hist_out: fp32 tensors whose first element is slot 0's history
-    (max k - 1 samples), ``hist_ss`` floats between slots.  Returns False when the kernel declines the shape."""
-    g = NsfDownsArgs()
+def _nsf_downs_fill(g, e, hist_in, hist_out, stages, outs, S, Tc, hop, hist_ss, rows):
+    """False when there are more stages than the struct holds."""
     g.e, g.hist_in, g.hist_out = ptr(e, torch.float32), ptr(hist_in, torch.float32), ptr(hist_out, torch.float32)
     g.rows = ptr(rows, torch.int32)
     g.hist_ss, g.S, g.Tc, g.hop, g.nstages = int(hist_ss), int(S), int(Tc), int(hop), len(stages)
@@ -1569,10 +1583,70 @@ def nsf_downs(e, hist_in, hist_out, stages, outs, *, S, Tc, hop, hist_ss, rows=N
         g.w[i], g.bias[i], g.out[i] = ptr(w, torch.float32), ptr(b, torch.float32), ptr(o, torch.float32)
     if rows is not None and rows.numel() != int(S):
         raise ValueError("rows must hold S = %d counts, got %d" % (int(S), rows.numel()))
+    return True
+
+
+def nsf_downs(e, hist_in, hist_out, stages, outs, *, S, Tc, hop, hist_ss, rows=None):
+    """Every excitation down-convolution of a generator in one launch (csrc/nsf_source.hip, kantts_nsf_downs_rows).
+    e (S, Tc * hop) fp32; ``stages``: a list of (u, k, C, w (k, C) fp32, bias (C) fp32 or None); ``outs``: one fp32 tensor
+    (S, Tc * hop / u, C) per stage; hist_in / hist_out: fp32 tensors whose first element is slot 0's history
+    (max k - 1 samples), ``hist_ss`` floats between slots.  Returns False when the kernel declines the shape."""
+    g = NsfDownsArgs()
+    if not _nsf_downs_fill(g, e, hist_in, hist_out, stages, outs, S, Tc, hop, hist_ss, rows):
+        return False
     rc = lib().kantts_nsf_downs_rows(ctypes.byref(g), stream())
     if rc == E_UNSUPPORTED:
         return False
     check(rc, "nsf_downs")
+    return True
+
+
+def nsf_sym_entry_points():
+    """True when the loaded library exports the excitation launches of ChunkedNCNSFVocoder."""
+    return hasattr(lib(), "kantts_nsf_source_end_rows") and hasattr(lib(), "kantts_nsf_downs_sym_rows")
+
+
+def _end_pos(g, S, end, pos_in, pos_ss):
+    if end is not None and end.numel() != int(S):
+        raise ValueError("end must hold S = %d counts, got %d" % (int(S), end.numel()))
+    g.end, g.pos_in, g.pos_ss = ptr(end, torch.int32), ptr(pos_in, torch.int32), int(pos_ss)
+
+
+def nsf_source_end(f0, uv, state_in, state_out, w, e, *, S, Tc, hop, H1, sr, alpha, sigma, state_ss=NSF_STATE_WORDS,
+                   bias=None, noise=None, harm=None, rows=None, end=None, pos_in=None, pos_ss=1):
+    """``nsf_source`` stopped at the utterance's end (csrc/nsf_source_sym.hip, kantts_nsf_source_end_rows): with ``end`` (S
+    int32 on the device: frames of each slot's utterance, < 0 open) and ``pos_in`` (the frames each slot consumed before this
+    call, ``pos_ss`` words between slots) only the frames of the call that lie inside the utterance are read and produce
+    samples and state.  Returns False when the kernel declines the shape."""
+    g = NsfSourceEndArgs()
+    _nsf_source_fill(g.src, f0, uv, state_in, state_out, w, e, S, Tc, hop, H1, sr, alpha, sigma, state_ss, bias, noise, harm, rows)
+    _end_pos(g, S, end, pos_in, pos_ss)
+    rc = lib().kantts_nsf_source_end_rows(ctypes.byref(g), stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "nsf_source_end")
+    return True
+
+
+def nsf_downs_sym(e, hist_in, hist_out, stages, lags, outs, *, S, Tc, hop, hist_rows, hist_ss, rows=None, end=None, pos_in=None,
+                  pos_ss=1):
+    """Every excitation down-convolution of a NON-CAUSAL generator in one launch (csrc/nsf_source_sym.hip,
+    kantts_nsf_downs_sym_rows): ``nsf_downs`` with tap j of stage i's row q reading sample q * u - lags[i] + j, a history of
+    ``hist_rows`` >= max(lags) samples, and zeros (not loaded) behind the utterance's end (``end`` / ``pos_in`` / ``pos_ss`` as
+    in ``nsf_source_end``).  Returns False when the kernel declines the shape."""
+    g = NsfDownsSymArgs()
+    if len(lags) != len(stages):
+        raise ValueError("one lag per stage")
+    if not _nsf_downs_fill(g.d, e, hist_in, hist_out, stages, outs, S, Tc, hop, hist_ss, rows):
+        return False
+    _end_pos(g, S, end, pos_in, pos_ss)
+    g.Hh = int(hist_rows)
+    for i, lag in enumerate(lags):
+        g.lag[i] = int(lag)
+    rc = lib().kantts_nsf_downs_sym_rows(ctypes.byref(g), stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "nsf_downs_sym")
     return True
 
 

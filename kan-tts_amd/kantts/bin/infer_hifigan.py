@@ -14,6 +14,9 @@ NSF generators play through kantts.models.hifigan.chunked_nsf.ChunkedNSFVocoder 
 of the sorted input list gets the noise and initial phases of ``(--seed, i)``, whatever the chunk size and the slots.
 Non-causal generators (single band, no source module) play through kantts.models.hifigan.chunked_nc.ChunkedNCVocoder: the
 network's look-ahead becomes a delay (logged; 3424 samples for the shipped non-causal geometry) that is flushed at the end.
+Non-causal NSF generators (the vocoders of sambert_nsf_16k and sambert_se_nsf_global_16k) play through
+kantts.models.hifigan.chunked_nc_nsf.ChunkedNCNSFVocoder: both of the above -- the excitation of ``(--seed, i)``, stopped at
+the utterance's end, and the same delay, since the source module adds none.
 Multi-band generators play through kantts.models.hifigan.chunked_mb.ChunkedMBVocoder (a PQMF synthesis that holds back the
 samples whose future it has not seen): the chunks have variable lengths and add up to the one-shot path's sample count.
 """
@@ -85,6 +88,13 @@ def _load_feats(model, path, device):
 
 def _chunked_vocoder(model, slots, device, seed):
     """The chunked player of ``model``; either class refuses what it cannot play, loudly."""
+    if model.nsf_enable and not model.causal and model.out_channels == 1:
+        from kantts.models.hifigan.chunked_nc_nsf import ChunkedNCNSFVocoder
+
+        vocoder = ChunkedNCNSFVocoder(model, slots=slots, graph=device.type == "cuda", seed=seed)
+        logging.info("Non-causal NSF generator: the waveform comes %d samples (%d frames) after the frames it is made of.",
+                     vocoder.delay_samples, vocoder.flush_frames)
+        return vocoder
     if model.nsf_enable:
         from kantts.models.hifigan.chunked_nsf import ChunkedNSFVocoder
 

@@ -115,7 +115,8 @@ class ChunkedNCVocoder(ChunkedVocoder):
     launch, read by every launch of the step), so a zeroed state is a fresh slot and captured steps stay valid across
     resets.  ``rows`` and ``end`` live in persistent device buffers the captured launches read.
 
-    Refused at construction: causal generators (``ChunkedVocoder`` plays them), NSF generators, ``out_channels > 1``,
+    Refused at construction: causal generators (``ChunkedVocoder`` plays them), NSF generators
+    (kantts.models.hifigan.chunked_nc_nsf.ChunkedNCNSFVocoder plays them), ``out_channels > 1``,
     ``training``, upsampling kernels with (kernel - stride) odd or below 0, even convolution kernels, and whatever the
     layer contract declines."""
 
@@ -126,13 +127,11 @@ class ChunkedNCVocoder(ChunkedVocoder):
         if getattr(generator, "causal", False):
             raise ValueError("ChunkedNCVocoder plays non-causal generators (causal=False); a causal one needs no delay: "
                              "use ChunkedVocoder")
-        if generator.nsf_enable:
+        if generator.nsf_enable and not self._plays_nsf:  # chunked_nc_nsf.ChunkedNCNSFVocoder plays them
             raise NotImplementedError("ChunkedNCVocoder: non-causal NSF generators are not supported (the symmetric "
                                       "source_downs and the excitation's delay are not built)")
         if generator.out_channels != 1:
             raise NotImplementedError("ChunkedNCVocoder: out_channels > 1 (non-causal multi-band) is not supported")
-        if not hip.sconv_sym_entry_points():
-            raise RuntimeError("ChunkedNCVocoder: the loaded library has no kantts_sconv_sym_rows_launch")
         super().__init__(generator, slots=slots, graph=graph, max_graphs=max_graphs)
         self._end = torch.full((self.slots,), -1, device=self.device, dtype=torch.int32)
         self._arena_i32 = self.arena.view(torch.int32)
@@ -202,6 +201,8 @@ class ChunkedNCVocoder(ChunkedVocoder):
             off += L.Hs * L.Cin
         self._pos_off = off  # one int32 word per slot; the arena's slot stride stays a multiple of 4 floats
         self.state_floats = off + 4
+        if not hip.sconv_sym_entry_points():  # the first look at the library: behind every refusal, before anything is packed
+            raise RuntimeError("ChunkedNCVocoder: the loaded library has no kantts_sconv_sym_rows_launch")
 
     # ---- launches
     def _conv(self, L, x, parity, res=None, rows=None, row_mul=1, zero_tail=False):
@@ -215,8 +216,11 @@ class ChunkedNCVocoder(ChunkedVocoder):
         kw = {}
         if res is not None:
             R = L.res_from
-            kw = dict(res=res, res_hist=self.arena[parity, 0, R.off:R.off + R.Hs * R.Cin], res_hist_ss=ss, res_hist_rows=R.Hs,
-                      res_lag=L.res_lag)
+            if R is None:  # an up-layer's excitation: produced as late as the layer's output, read at res_lag = 0
+                kw = dict(res=res)
+            else:
+                kw = dict(res=res, res_hist=self.arena[parity, 0, R.off:R.off + R.Hs * R.Cin], res_hist_ss=ss,
+                          res_hist_rows=R.Hs, res_lag=L.res_lag)
         first = L is self.pre
         ok = hip.sconv_sym(x, hin, hout, L.w, out, S=S, Tc=T, Cin=L.Cin, N=L.N, K=L.K, step=L.step, hist_ss=ss,
                            precision=self.precision, rows=rows, end=self._end, row_mul=row_mul,
@@ -279,6 +283,10 @@ class ChunkedNCVocoder(ChunkedVocoder):
         if n < 1:
             raise ValueError("chunk_frames must be >= 1")
         self.reset(slot)
+        yield from self._play_flushed(mel_full, T, n, slot)
+
+    def _play_flushed(self, mel_full, T, n, slot):
+        """The steps of ``synthesize`` on a slot that has just been reset: the utterance's T frames, then the flush frames."""
         self._end[slot] = T
         total = T + self.flush_frames
         for t0 in range(0, total, n):

@@ -24,7 +24,9 @@ slot EMITTED (``hip.mb_emit`` on a host count of pending rows), not ``n * hop`` 
 sample count of the utterance.  The post-net's look-ahead delays the first frames of an utterance, so a slot is released only
 after its last frame has been VOCODED: until then it takes zero-count acoustic steps while the vocoder drains what is left.
 
-``lookahead=True`` lets a non-causal generator (single band, no source module) play, through ``ChunkedNCVocoder``: its audio
+``lookahead=True`` lets a non-causal generator (single band) play, through ``ChunkedNCVocoder`` or, with a source module
+(``nsf=``), through ``ChunkedNCNSFVocoder`` (kantts/models/hifigan/chunked_nc_nsf.py: the hand-over de-normalises f0 as for a
+causal NSF voice, ``admit`` keys the utterance's excitation, flush frames are read by no launch): its audio
 comes ``vocoder.delay_samples`` late, so the upload also carries every slot's frame count (``end``) and the vocoder's own
 per-slot counts, which exceed the handed-over frames by flush frames once the acoustic frames have run out; the audio of a step
 is what the slot emitted (``hip.nc_emit``), and a slot is released only after the flush.  Without it such a generator is
@@ -82,8 +84,12 @@ class StreamingTTS:
         self.f0_threshold, self.uv_threshold = float(f0_threshold), float(uv_threshold)
         self.pool = AcousticSlots(fsnet, slots=slots, max_steps=max_steps)
         self.mb = int(generator.out_channels) > 1
-        self.nc = bool(lookahead) and not getattr(generator, "causal", False) and not self.mb and not nsf_enable
-        if self.nc:
+        self.nc = bool(lookahead) and not getattr(generator, "causal", False) and not self.mb
+        if self.nc and nsf_enable:
+            from kantts.models.hifigan.chunked_nc_nsf import ChunkedNCNSFVocoder
+
+            self.vocoder = ChunkedNCNSFVocoder(generator, slots=slots, graph=graph, seed=seed)
+        elif self.nc:
             from kantts.models.hifigan.chunked_nc import ChunkedNCVocoder
 
             self.vocoder = ChunkedNCVocoder(generator, slots=slots, graph=graph)
@@ -171,7 +177,8 @@ class StreamingTTS:
             A = torch.tensor([self.vocoded, rows, [r + f for r, f in zip(rows, flush)], end],
                              dtype=torch.int32).to(pool.dev, non_blocking=True)  # the ONE upload
             if any(rows):
-                hip.check(hip.mel_handover(pool.y, A[0], A[1], self.buf), "mel_handover_rows")
+                hip.check(hip.mel_handover(pool.y, A[0], A[1], self.buf, nsf=self.nsf, f0_floor=self.f0_threshold,
+                                           uv_threshold=self.uv_threshold), "mel_handover_rows")
             wav = self.vocoder.step(self.buf, rows=A[2], end=A[3])
         elif any(rows):
             # multi-band: the utterance ends for the vocoder in the step that hands over its last frame
