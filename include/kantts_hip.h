@@ -1569,6 +1569,58 @@ typedef struct {
 } kantts_nsf_downs_sym_args;
 int kantts_nsf_downs_sym_rows(const kantts_nsf_downs_sym_args* args, void* stream);
 
+/* ---- The NSF excitation in TRAINING (csrc/nsf_train.hip).  The forward of a training step is kantts_nsf_source_rows as it
+ * stands (S = batch items, Tc = frames, rows = NULL); these two entry points give it starting words drawn on the device
+ * and the gradient of its projection, so that a whole GAN step of an NSF generator can be captured and replayed.
+ *
+ * kantts_nsf_draw_states: the device twin of kantts.models.hifigan.chunked_nsf.initial_state.  seed_counter: two 64-bit
+ * words {seed, counter} in DEVICE memory.  One workgroup reads both and writes, for item s in [0, S), the
+ * KANTTS_NSF_STATE_WORDS words at state_out + s * state_ss of utterance key (counter << 20) | s under `seed`:
+ *   key64     = mix(mix(seed, 0x4E5346), (counter << 20) | s)          mix: kantts_rng_mix of csrc/common.h
+ *   phase     = 0 (16 words),  cursor = 0,  key = key64
+ *   phase0[0] = 0,  phase0[h] = (float)(((mix(key64, 2^63 + h) >> 40) / 2^24 * 2 - 1) * pi)   for h in [1, H1): computed in
+ *               fp64 and rounded ONCE, the bits of the Python function;  phase0[h] = 0 for h in [H1, 16)
+ * then, behind a barrier, stores counter + 1: consecutive launches (and replays of one captured launch) draw different
+ * numbers, and a counter set back replays them.  Exactly words [0, KANTTS_NSF_STATE_WORDS) of every item are written, with
+ * plain 32-bit vector stores; the words between items (state_ss > KANTTS_NSF_STATE_WORDS) and `seed` are not.
+ * KANTTS_E_BADARG: a NULL pointer, a pointer that is not 8-byte aligned, an odd state_ss, state_ss < KANTTS_NSF_STATE_WORDS
+ * with S > 1, H1 < 1.  KANTTS_E_UNSUPPORTED: S outside [1, 2^20) (the key holds the item in 20 bits), H1 > 16.  Nothing is
+ * written when a call is refused. */
+int kantts_nsf_draw_states(uint64_t* seed_counter, int S, int H1, int32_t* state_out, long long state_ss, void* stream);
+
+/* kantts_nsf_source_wgrad: the backward of the projection of kantts_nsf_source_rows, for the call that produced `e`:
+ *   dpre[s, n] = de[s, n] * (1 - e[s, n]^2)
+ *   dw[h]      = sum_{s, n} dpre[s, n] * x_h[s, n]      h in [0, H1)
+ *   dbias[0]   = sum_{s, n} dpre[s, n]                  (dbias == NULL: not written)
+ * x_h is the excitation before the projection (`harm` of the forward).  It is recomputed, not read: f0, uv, state_in, noise,
+ * hop, H1, sr, alpha, sigma and state_ss are the forward's (rows == NULL there: every item has Tc live frames), and forward
+ * and backward evaluate x_h through the same function, so the bits are the forward's.  dw and dbias are WRITTEN, not
+ * accumulated into, and the same inputs give the same bits from run to run: one workgroup per (item, frame) leaves H1 + 1
+ * partial sums in ws (a fixed in-workgroup tree, no atomics), a second launch behind it on the stream adds the S * Tc
+ * partials of every sum in a fixed order.  ws: S * Tc * (H1 + 1) floats of device memory that the call may overwrite;
+ * ws_floats says how many there are.
+ *   f0, uv (S, Tc); noise (S, Tc * hop, H1) or NULL; e, de (S, Tc * hop); dw (H1); dbias (1) or NULL: fp32, dense.
+ * KANTTS_E_BADARG: args == NULL, a NULL required pointer (f0, uv, state_in, e, de, dw, ws), S < 1, Tc < 1, hop < 1, H1 < 1,
+ * sr <= 0, sigma <= 0, state_ss < KANTTS_NSF_STATE_WORDS with S > 1, ws_floats < S * Tc * (H1 + 1).  KANTTS_E_UNSUPPORTED:
+ * H1 > 16, a state that is not 8-byte aligned or an odd state_ss, S * Tc * hop >= 2^31.  Nothing is written when a call is
+ * refused. */
+typedef struct {
+  const float* f0;
+  const float* uv;
+  const float* noise;
+  const int32_t* state_in;
+  const float* e;
+  const float* de;
+  float* dw;
+  float* dbias;
+  float* ws;
+  long long state_ss;
+  long long ws_floats;
+  int S, Tc, hop, H1;
+  float sr, alpha, sigma;
+} kantts_nsf_wgrad_args;
+int kantts_nsf_source_wgrad(const kantts_nsf_wgrad_args* args, void* stream);
+
 /* ---- The tail of a MULTI-BAND generator in chunked inference (csrc/mb_tail.hip), one launch: conv_post (causal, K taps,
  * step 1, Cin -> B sub-bands), tanh, and a PQMF synthesis that can be cut at any chunk boundary.  Per slot, driven by the
  * same device `rows` buffer and row_mul as kantts_sconv_rows_launch:

@@ -54,50 +54,68 @@ __device__ __forceinline__ void nsf_source_state(const kantts_nsf_source_args& g
   }
 }
 
-// ---- the hop samples of LIVE frame k of slot s (the caller has returned for a dead frame, before any load)
-__device__ __forceinline__ void nsf_source_frame(const kantts_nsf_source_args& g, int s, int k, nsf_source_lds& lds) {
-  const int H1 = g.H1, hop = g.hop;
+// ---- what LIVE frame k of slot s starts from: the phase in front of it, its increment and the initial phases, H1 cells each
+// (threads below H1; the caller puts the barrier behind it)
+__device__ __forceinline__ void nsf_frame_phases(const kantts_nsf_source_args& g, int s, int k, nsf_source_lds& lds) {
   const int tid = threadIdx.x;
   const double inv_sr = 1.0 / (double)g.sr;
   const nsf_state* si = reinterpret_cast<const nsf_state*>(g.state_in + (long long)s * g.state_ss);
   const float* f0p = g.f0 + (long long)s * g.Tc;
-  if (tid < H1) {
+  if (tid < g.H1) {
     uint32_t p = si->phase[tid];
-    for (int kk = 0; kk < k; ++kk) p += (uint32_t)hop * nsf_inc(f0p[kk], tid, inv_sr);
+    for (int kk = 0; kk < k; ++kk) p += (uint32_t)g.hop * nsf_inc(f0p[kk], tid, inv_sr);
     lds.phase[tid] = p;
     lds.inc[tid] = nsf_inc(f0p[k], tid, inv_sr);
     lds.phase0[tid] = si->phase0[tid];
-    lds.w[tid] = g.w[tid];
   }
+}
+
+// ---- x_h of ONE sample: sample j of its frame, element o of the call, absolute sample n of the utterance.  THE definition
+// of the excitation before its projection: the forward (nsf_source_frame) and the weight gradient of csrc/nsf_train.hip both
+// call it, for h = 0, 1, ... H1 - 1 in this order, so both see the same bits.  An even h forms the Box-Muller pair of
+// harmonics h and h + 1 from one hash and leaves the second Gaussian in z1, where h + 1 finds it (an odd H1: the last
+// harmonic forms a pair and uses its first half).
+__device__ __forceinline__ float nsf_harmonic(const kantts_nsf_source_args& g, const nsf_source_lds& lds, int h, int j,
+                                              long long o, uint64_t key, uint64_t n, float uv, float unv, float& z1) {
+  const float cyc = 6.283185307179586f / 4294967296.f;
+  float z;
+  if (g.noise) {
+    z = g.noise[o * g.H1 + h];
+  } else if ((h & 1) == 0) {
+    const uint64_t r = kantts_rng_mix(key, n * 8ull + (uint64_t)(h >> 1));
+    const float u1 = (float)((uint32_t)(r >> 40) + 1u) * (1.f / 16777216.f);  // (0, 1]
+    const float u2 = (float)((uint32_t)r >> 8) * (1.f / 16777216.f);          // [0, 1)
+    const float rad = g.sigma * sqrtf(-2.f * logf(u1));
+    z = rad * cosf(6.283185307179586f * u2);
+    z1 = rad * sinf(6.283185307179586f * u2);
+  } else {
+    z = z1;
+  }
+  const uint32_t ph = lds.phase[h] + (uint32_t)(j + 1) * lds.inc[h];
+  const float theta = (float)(int32_t)ph * cyc;  // [-pi, pi)
+  const float voiced = g.alpha * sinf(theta + lds.phase0[h]) + z;
+  return voiced * uv + (unv * z) * (1.f - uv);
+}
+
+// ---- the hop samples of LIVE frame k of slot s (the caller has returned for a dead frame, before any load)
+__device__ __forceinline__ void nsf_source_frame(const kantts_nsf_source_args& g, int s, int k, nsf_source_lds& lds) {
+  const int H1 = g.H1, hop = g.hop;
+  const int tid = threadIdx.x;
+  const nsf_state* si = reinterpret_cast<const nsf_state*>(g.state_in + (long long)s * g.state_ss);
+  nsf_frame_phases(g, s, k, lds);
+  if (tid < H1) lds.w[tid] = g.w[tid];
   __syncthreads();
   const float uv = g.uv[(long long)s * g.Tc + k];
   const float b = g.bias ? g.bias[0] : 0.f;
   const float unv = g.alpha / 3.f / g.sigma;
   const uint64_t key = si->key;
   const uint64_t n0 = si->cursor + (uint64_t)k * (uint64_t)hop;  // absolute index of the frame's first sample
-  const float cyc = 6.283185307179586f / 4294967296.f;
   for (int j = tid; j < hop; j += NSF_THREADS) {
     const long long o = ((long long)s * g.Tc + k) * hop + j;  // sample of this call
     float acc = b;
     float z1 = 0.f;  // the second Gaussian of a Box-Muller pair, for the odd harmonic
     for (int h = 0; h < H1; ++h) {
-      float z;
-      if (g.noise) {
-        z = g.noise[o * H1 + h];
-      } else if ((h & 1) == 0) {
-        const uint64_t r = kantts_rng_mix(key, (n0 + (uint64_t)j) * 8ull + (uint64_t)(h >> 1));
-        const float u1 = (float)((uint32_t)(r >> 40) + 1u) * (1.f / 16777216.f);  // (0, 1]
-        const float u2 = (float)((uint32_t)r >> 8) * (1.f / 16777216.f);          // [0, 1)
-        const float rad = g.sigma * sqrtf(-2.f * logf(u1));
-        z = rad * cosf(6.283185307179586f * u2);
-        z1 = rad * sinf(6.283185307179586f * u2);
-      } else {
-        z = z1;
-      }
-      const uint32_t ph = lds.phase[h] + (uint32_t)(j + 1) * lds.inc[h];
-      const float theta = (float)(int32_t)ph * cyc;  // [-pi, pi)
-      const float voiced = g.alpha * sinf(theta + lds.phase0[h]) + z;
-      const float x = voiced * uv + (unv * z) * (1.f - uv);
+      const float x = nsf_harmonic(g, lds, h, j, o, key, n0 + (uint64_t)j, uv, unv, z1);
       if (g.harm) g.harm[o * H1 + h] = x;
       acc += lds.w[h] * x;
     }

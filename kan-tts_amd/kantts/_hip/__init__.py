@@ -164,6 +164,16 @@ class NsfDownsSymArgs(Structure):
                 ("lag", c_int32 * 8)]
 
 
+class NsfWgradArgs(Structure):
+    """kantts_nsf_wgrad_args (include/kantts_hip.h)."""
+    _fields_ = [
+        ("f0", c_void_p), ("uv", c_void_p), ("noise", c_void_p), ("state_in", c_void_p), ("e", c_void_p), ("de", c_void_p),
+        ("dw", c_void_p), ("dbias", c_void_p), ("ws", c_void_p), ("state_ss", c_longlong), ("ws_floats", c_longlong),
+        ("S", c_int32), ("Tc", c_int32), ("hop", c_int32), ("H1", c_int32),
+        ("sr", c_float), ("alpha", c_float), ("sigma", c_float),
+    ]
+
+
 class MbTailArgs(Structure):
     """kantts_mb_tail_args (include/kantts_hip.h); ``in_`` is the C field ``in``."""
     _fields_ = [
@@ -538,6 +548,9 @@ def lib():
         L.kantts_sconv_sym_rows_launch.argtypes = [POINTER(SConvSymArgs), c_void_p]
         L.kantts_nsf_source_end_rows.argtypes = [POINTER(NsfSourceEndArgs), c_void_p]
         L.kantts_nsf_downs_sym_rows.argtypes = [POINTER(NsfDownsSymArgs), c_void_p]
+        if hasattr(L, "kantts_nsf_draw_states") and hasattr(L, "kantts_nsf_source_wgrad"):  # has_nsf_train(): a library
+            L.kantts_nsf_draw_states.argtypes = [p, i, i, p, ll, p]                         # built before them still loads
+            L.kantts_nsf_source_wgrad.argtypes = [POINTER(NsfWgradArgs), c_void_p]
         _lib = L
     return _lib
 
@@ -566,7 +579,7 @@ EXPORTED_SYMBOLS = [
     "kantts_pnca_decode_slots", "kantts_lstm_fwd_slots", "kantts_fsmn_dwconv_fwd_slots", "kantts_scatter_rows_f32",
     "kantts_nsf_source_rows", "kantts_nsf_downs_rows", "kantts_mel_handover_rows",
     "kantts_mb_tail_rows", "kantts_sconv_sym_rows_launch", "kantts_lr_memory_fwd", "kantts_lr_memory_bwd",
-    "kantts_nsf_source_end_rows", "kantts_nsf_downs_sym_rows",
+    "kantts_nsf_source_end_rows", "kantts_nsf_downs_sym_rows", "kantts_nsf_draw_states", "kantts_nsf_source_wgrad",
 ]
 
 
@@ -1647,6 +1660,44 @@ def nsf_downs_sym(e, hist_in, hist_out, stages, lags, outs, *, S, Tc, hop, hist_
     if rc == E_UNSUPPORTED:
         return False
     check(rc, "nsf_downs_sym")
+    return True
+
+
+def has_nsf_train():
+    """True when the loaded library exports the training entry points of the NSF excitation (csrc/nsf_train.hip)."""
+    return hasattr(lib(), "kantts_nsf_draw_states") and hasattr(lib(), "kantts_nsf_source_wgrad")
+
+
+def nsf_draw_states(words, state_out, *, S, H1, state_ss=NSF_STATE_WORDS):
+    """Starting words of S utterances drawn on the device (csrc/nsf_train.hip, kantts_nsf_draw_states): ``words``, an int64
+    device tensor {seed, counter}; item s of the call gets what chunked_nsf.initial_state(seed, (counter << 20) | s, H1)
+    gives, in ``state_out`` (int32, ``state_ss`` words between items), and the counter is left one higher.  Returns False
+    when the kernel declines the shape (S outside [1, 2^20), H1 > 16)."""
+    rc = lib().kantts_nsf_draw_states(ptr(words, torch.int64), int(S), int(H1), ptr(state_out, torch.int32), int(state_ss),
+                                      stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "nsf_draw_states")
+    return True
+
+
+def nsf_source_wgrad(f0, uv, state_in, e, de, dw, dbias, ws, *, S, Tc, hop, H1, sr, alpha, sigma, state_ss=NSF_STATE_WORDS,
+                     noise=None):
+    """Gradient of the projection of ``nsf_source`` (csrc/nsf_train.hip, kantts_nsf_source_wgrad): f0, uv, state_in, noise
+    and the scalars as the forward that produced ``e`` (S, Tc * hop) saw them, ``de`` its cotangent; writes dw (H1) and dbias
+    (1, or None) -- bit-reproducible, not accumulated.  ``ws``: fp32 scratch of at least S * Tc * (H1 + 1) elements.  Returns
+    False when the kernel declines the shape."""
+    g = NsfWgradArgs()
+    g.f0, g.uv, g.noise = ptr(f0, torch.float32), ptr(uv, torch.float32), ptr(noise, torch.float32)
+    g.state_in, g.e, g.de = ptr(state_in, torch.int32), ptr(e, torch.float32), ptr(de, torch.float32)
+    g.dw, g.dbias, g.ws = ptr(dw, torch.float32), ptr(dbias, torch.float32), ptr(ws, torch.float32)
+    g.state_ss, g.ws_floats = int(state_ss), int(ws.numel())
+    g.S, g.Tc, g.hop, g.H1 = int(S), int(Tc), int(hop), int(H1)
+    g.sr, g.alpha, g.sigma = float(sr), float(alpha), float(sigma)
+    rc = lib().kantts_nsf_source_wgrad(ctypes.byref(g), stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "nsf_source_wgrad")
     return True
 
 

@@ -12,7 +12,7 @@ import math
 import torch
 
 from . import (E_UNSUPPORTED, act_cast_bf16, bgemm_nt, bgemm_tn, cconv, cconv_wgrad, check, get_precision, conv_c1, conv_n1, conv_wgrad,
-               conv_win, gemm, lib, make_seg, ptr, rng_state, stream)
+               conv_win, gemm, lib, make_seg, nsf_source, nsf_source_wgrad, ptr, rng_state, stream)
 from . import ops_bf16
 
 _seed_counter = itertools.count(1)
@@ -2565,6 +2565,48 @@ def sin_add(x, act_slope=None):
     if act_slope is not None:
         return _SinAddAct.apply(x, float(act_slope))
     return _SinAdd.apply(x)
+
+
+class _NsfExcite(torch.autograd.Function):
+    """tanh(bias + sum_h w[h] * x_h) of the NSF sine source in one launch (kantts_nsf_source_rows), x_h made from f0 / uv and
+    the utterances' starting words; backward recomputes x_h from the same words (kantts_nsf_source_wgrad) instead of keeping
+    the (S, T, H + 1) excitation.  Gradients for w and bias only: the excitation has none (reference layers.py:229-290)."""
+
+    @staticmethod
+    def forward(ctx, f0, uv, w, bias, states, scratch, hop, H1, sr, alpha, sigma):
+        f0, uv = _c(f0), _c(uv)
+        S, Tc = f0.shape
+        e = torch.empty((S, Tc * hop), device=f0.device, dtype=torch.float32)
+        wf = _c(w.detach()).reshape(-1)
+        if wf.numel() != H1:
+            raise ValueError("the projection weight must hold H + 1 = %d values, got %s" % (H1, tuple(w.shape)))
+        if not nsf_source(f0, uv, states, scratch, wf, e, S=S, Tc=Tc, hop=hop, H1=H1, sr=sr, alpha=alpha, sigma=sigma,
+                          bias=None if bias is None else _c(bias.detach())):
+            raise RuntimeError("kantts_nsf_source_rows declined a shape nsf_excite was planned for")
+        ctx.save_for_backward(f0, uv, states, e)
+        ctx.geom = (S, Tc, hop, H1, sr, alpha, sigma)
+        ctx.w_shape, ctx.has_bias = w.shape, bias is not None
+        return e
+
+    @staticmethod
+    def backward(ctx, de):
+        f0, uv, states, e = ctx.saved_tensors
+        S, Tc, hop, H1, sr, alpha, sigma = ctx.geom
+        de = _c(de)
+        dw = torch.empty(H1, device=e.device, dtype=torch.float32)
+        db = torch.empty(1, device=e.device, dtype=torch.float32) if ctx.has_bias else None
+        ws = torch.empty(S * Tc * (H1 + 1), device=e.device, dtype=torch.float32)
+        if not nsf_source_wgrad(f0, uv, states, e, de, dw, db, ws, S=S, Tc=Tc, hop=hop, H1=H1, sr=sr, alpha=alpha, sigma=sigma):
+            raise RuntimeError("kantts_nsf_source_wgrad declined a shape its forward ran")
+        return None, None, dw.view(ctx.w_shape), db, None, None, None, None, None, None, None
+
+
+def nsf_excite(f0, uv, w, bias, states, scratch, *, hop, H1, sr, alpha, sigma):
+    """The projected NSF excitation of a training step: f0 (Hz), uv (S, Tc) -> e (S, Tc * hop), differentiable in ``w`` (H + 1
+    values in any shape, e.g. what conv_weight gives for the 1x1 projection) and ``bias`` (1, or None).  ``states``: the
+    (S, 36) int32 starting words of the S utterances (hip.nsf_draw_states; backward reads them again, so the caller must not
+    overwrite them before it ran); ``scratch``: (S, 36) int32 the launch may overwrite (its state_out)."""
+    return _NsfExcite.apply(f0, uv, w, bias, states, scratch, int(hop), int(H1), float(sr), float(alpha), float(sigma))
 
 
 def upsample_weights(w, s, bias=None):

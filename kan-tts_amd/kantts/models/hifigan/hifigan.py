@@ -157,6 +157,18 @@ class Generator(torch.nn.Module):
         h = self.conv_post.forward_cl(h, in_leaky=0.01)
         return torch.tanh(h).transpose(1, 2)
 
+    def enable_device_excitation(self, seed):
+        """Training with the excitation drawn on the device (``SourceModule.enable_device_draws``: two launches that read
+        nothing from the host, which is what lets the GAN step of an NSF generator be captured).  Raises NotImplementedError
+        for a generator without a source module and for geometry the source kernel does not take."""
+        if not self.nsf_enable:
+            raise NotImplementedError("enable_device_excitation: the generator has no source module (nsf_params)")
+        self.source_module.enable_device_draws(seed, hop=int(np.prod(self.upsample_scales)))
+
+    def disable_device_excitation(self):
+        if self.nsf_enable:
+            self.source_module.disable_device_draws()
+
     def _residual_stacks(self, h, i, image_slope=None):
         # the num_kernels residual stacks of a stage read the same h and are summed: independent branches.  One stream
         # each when a backward pass will follow (their weight gradients are the low-occupancy launches that gain:

@@ -229,6 +229,82 @@ class SourceModule(torch.nn.Module):
         self.alpha = alpha
         self.sigma = sigma
         self.ffn = nn.Sequential(weight_norm(nn.Conv1d(self.nb_harmonics + 1, 1, kernel_size=1, stride=1)), nn.Tanh())
+        self._draw_words = None  # device draws (enable_device_draws): {seed, counter} int64 on the device -- a plain
+        # attribute, not a buffer: state_dict() is the reference's
+
+    def enable_device_draws(self, seed, hop=None):
+        """From now on ``forward_cl`` is two launches that read nothing from the host, so a captured step draws new numbers
+        at every replay: kantts_nsf_draw_states (initial phases and the noise key of every item, from ``seed`` and a draw
+        counter in device memory that the launch itself advances) and ``ops.nsf_excite`` (kantts_nsf_source_rows: the
+        whole source module; backward: kantts_nsf_source_wgrad).  Item s of draw number c is utterance
+        ``(c << 20) | s`` of ``chunked_nsf.initial_state(seed, ...)``; ``draw_counter`` reads the counter,
+        ``set_draw_counter`` puts it back.
+
+        Two known differences from the reference's draw, the ones chunked_nsf.py states for inference: frames are indexed
+        exactly (sample n belongs to frame n // hop, where ``interpolate``'s float scale can pick the neighbouring frame
+        for hops that are no power of two), and initial phases and noise come from the hash of csrc/common.h instead of
+        torch's generator -- the same distributions, not the same numbers.  The running phase is the kernel's exact
+        fixed-point sum instead of an fp32 ``cumsum``.
+
+        Geometry the kernel does not take is refused HERE with NotImplementedError: more than 16 harmonics, a projection
+        that is not the 1x1 convolution H + 1 -> 1, and -- ``hop``: the product of the generator's upsampling scales, when
+        the caller knows it -- an ``upsample_ratio`` that differs from it.  Without the training entry points in the loaded
+        library (``hip.has_nsf_train()``) it raises NotImplementedError as well.  The module's device is fixed from here
+        on (``disable_device_draws`` before moving it)."""
+        import kantts._hip as hip
+
+        H1 = int(self.nb_harmonics) + 1
+        if H1 > hip.NSF_MAX_H1:
+            raise NotImplementedError("SourceModule: nb_harmonics + 1 = %d harmonics, kantts_nsf_source_rows takes %d"
+                                      % (H1, hip.NSF_MAX_H1))
+        if hop is not None and int(self.upsample_ratio) != int(hop):
+            raise NotImplementedError("SourceModule: upsample_ratio %d is not the product of the upsampling scales %d"
+                                      % (int(self.upsample_ratio), int(hop)))
+        c = self.ffn[0]
+        if c.in_channels != H1 or c.out_channels != 1 or c.kernel_size[0] != 1:
+            raise NotImplementedError("SourceModule: the source projection is not a 1x1 convolution H + 1 -> 1")
+        if not hip.has_nsf_train():
+            raise NotImplementedError("the loaded library has no kantts_nsf_draw_states / kantts_nsf_source_wgrad")
+        dev = c.bias.device if c.bias is not None else next(self.parameters()).device
+        seed = int(seed) & ((1 << 64) - 1)
+        self._draw_words = torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed, 0], dtype=torch.int64).to(dev)
+
+    def disable_device_draws(self):
+        """Back to ``excitation``: torch's generator, the reference's arithmetic."""
+        self._draw_words = None
+
+    @property
+    def device_draws(self):
+        return self._draw_words is not None
+
+    def draw_counter(self):
+        """Draws made so far (reads the device word: a synchronisation)."""
+        return int(self._draw_words[1])
+
+    def set_draw_counter(self, value):
+        """``value``: an int, or a one-element int64 device tensor (no synchronisation)."""
+        if torch.is_tensor(value):
+            self._draw_words[1:].copy_(value.reshape(1))
+        else:
+            self._draw_words[1:].fill_(int(value))
+
+    def _forward_device_draws(self, pitch, uv):
+        import kantts._hip as hip
+
+        S, Tc = pitch.size(0), pitch.size(-1)
+        H1, W = int(self.nb_harmonics) + 1, hip.NSF_STATE_WORDS
+        f0, uv = pitch.reshape(S, Tc).float().contiguous(), uv.reshape(S, Tc).float().contiguous()
+        # the drawn words and the source launch's state_out, fresh per forward: backward reads the words after later draws,
+        # and a captured graph keeps the addresses of BOTH (allocated inside a capture they live in the graph's pool; a
+        # buffer kept on the module and regrown for a larger batch would leave earlier graphs writing into freed memory)
+        states, scratch = torch.empty((2, S, W), device=f0.device, dtype=torch.int32)
+        if not hip.nsf_draw_states(self._draw_words, states, S=S, H1=H1):
+            raise NotImplementedError("kantts_nsf_draw_states takes fewer than 2^20 items, got %d" % S)
+        c = self.ffn[0]
+        w, _ = conv_weight(c)  # (1, H + 1, 1) or tap-major (1, 1, H + 1): the same H + 1 values in the same order
+        e = ops.nsf_excite(f0, uv, w, c.bias, states, scratch, hop=int(self.upsample_ratio), H1=H1,
+                           sr=float(self.sampling_rate), alpha=float(self.alpha), sigma=float(self.sigma))
+        return e.unsqueeze(-1)
 
     @torch.no_grad()
     def excitation(self, pitch, uv):
@@ -267,6 +343,8 @@ class SourceModule(torch.nn.Module):
 
     def forward_cl(self, pitch, uv):
         """-> (B, T, 1) channels-last excitation signal."""
+        if self._draw_words is not None:
+            return self._forward_device_draws(pitch, uv)
         e = self.excitation(pitch, uv).transpose(1, 2).contiguous()
         c = self.ffn[0]
         w, tap = conv_weight(c)

@@ -9,7 +9,10 @@ hipStreamBeginCapture; the per-discriminator / per-residual-stack streams of ops
 branches of the graph) and replayed per step:
   * inputs are static device buffers (``load_batch`` copies a new batch of the same shape in place);
   * learning rates and step counts of the three optimizers live in device memory (ArenaAdam.enable_device_state);
-  * nothing in the step reads a value back to the host.
+  * nothing in the step reads a value back to the host;
+  * an NSF generator draws its excitation on the device (``Generator.enable_device_excitation``): initial phases and the
+    noise key come from a seed and a draw counter in device memory that the draw launch itself advances, twice per step
+    (``generator_loss`` and the no-grad recomputation in ``discriminator_loss``), so every replay gets new numbers.
 The step must have both phases active (``steps`` past both start thresholds) -- before that the eager
 ``gan_train_step`` runs.  Data-parallel replicas capture the step as a chain of graph segments cut where a gradient bucket
 of the generator's / a discriminator's arena is complete, with the all-reduces issued between the replays
@@ -31,7 +34,22 @@ class CaptureRefused(NotImplementedError):
     of building a GraphedGanStep that the trainer answers with the eager step instead of propagating."""
 
 
+def excitation_seed(rank=0):
+    """The seed of a replica's device-drawn NSF excitation: torch's seed mixed with the rank, so that data-parallel replicas
+    (same torch seed, same weights) draw different phases and noise."""
+    from kantts.models.hifigan.chunked_nsf import rng_mix
+
+    return rng_mix(torch.initial_seed() & ((1 << 64) - 1), int(rank))
+
+
 class GraphedGanStep:
+    """An NSF generator is switched to device-drawn excitation here if it is not yet (seed: ``excitation_seed`` of the
+    replica's rank), and KEEPS it afterwards: every later eager step of the model -- a new batch shape's warm-up, a step no
+    graph is ready for, evaluation -- draws from the same device counter (``Generator.disable_device_excitation`` goes
+    back).  If no graph comes of the construction (``CaptureRefused``, ranks that do not agree), a module this constructor
+    switched goes back to its host-seeded draws before the exception leaves.  The warm-up steps consume no draws: the counter
+    is put back with the optimizer snapshots."""
+
     def __init__(self, model, optimizer, scheduler, criterion, config, y, x, warmup=2, steps=10 ** 9):
         self.model, self.optimizer, self.scheduler, self.criterion, self.config = model, optimizer, scheduler, criterion, config
         self.opts = [optimizer["generator"]] + list(optimizer["discriminator"].values())
@@ -41,8 +59,19 @@ class GraphedGanStep:
         self.distributed = any(o.arena.world_size > 1 for o in self.opts)
         if steps <= config.get("discriminator_train_start_steps", 0) or steps < config.get("generator_train_start_steps", 0):
             raise ValueError("both phases must be active in a captured GAN step")
-        if getattr(model["generator"], "nsf_enable", False):
-            raise NotImplementedError("the NSF excitation draws host-seeded random numbers per step: eager step only")
+        self._source, enabled_here = None, False
+        gen = model["generator"]
+        gen = getattr(gen, "module", gen)
+        if getattr(gen, "nsf_enable", False):
+            import kantts._hip as hip
+
+            if not hip.has_nsf_train():
+                raise NotImplementedError("the NSF excitation draws host-seeded random numbers per step and the loaded library "
+                                          "has no device draw (kantts_nsf_draw_states): eager step only")
+            enabled_here = not gen.source_module.device_draws
+            if enabled_here:  # the seed follows the replica layout of the optimizer's arena
+                gen.enable_device_excitation(excitation_seed(self.opts[0].arena.rank))  # NotImplementedError: geometry
+            self._source = gen.source_module
         self.steps = steps
         self.y, self.x = y.clone(), x.clone()
         self._nosched = {"generator": _NoSched(), "discriminator": {k: _NoSched() for k in scheduler["discriminator"]}}
@@ -52,6 +81,13 @@ class GraphedGanStep:
             o.enable_device_state()
         try:
             self._build(warmup)
+        except BaseException:
+            # no graph came of it (a capture the runtime refused, ranks that do not agree, an error of the warm-up): a source
+            # module that THIS constructor switched to device draws goes back to its host-seeded ones, so the eager step
+            # the trainer falls back to is the one it ran before; a caller's own enable_device_excitation stays
+            if enabled_here:
+                gen.disable_device_excitation()
+            raise
         finally:  # the eager step (a new batch shape's warm-up, a step no graph is ready for) keeps its own setting
             for o, ov in zip(self.opts, overlap_before):
                 o.arena.overlap = ov
@@ -62,6 +98,7 @@ class GraphedGanStep:
         snaps = [o.snapshot() for o in self.opts]
         bufs = self._module_buffers()
         buf_snap = [b.clone() for b in bufs]  # e.g. the spectral_norm power-iteration vectors of follow_official_norm
+        draws = None if self._source is None else self._source._draw_words[1:].clone()  # int64: not among the buffers above
         # one stream for warm-up and capture (AccumulateGrad nodes replay on the stream they were created on)
         self._cap_stream = torch.cuda.Stream()
         self._cap_stream.wait_stream(torch.cuda.current_stream())
@@ -75,6 +112,8 @@ class GraphedGanStep:
         with torch.no_grad():
             for b, v in zip(bufs, buf_snap):
                 b.copy_(v)
+            if draws is not None:
+                self._source.set_draw_counter(draws)  # the warm-up steps drew twice each
         for o in self.opts:
             o.zero_grad(set_to_none=True)
         self.graph, self.segments = None, None

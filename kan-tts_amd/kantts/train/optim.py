@@ -43,6 +43,7 @@ class ParamArena:
         self.grad_views = [self.grad[o:o + p.numel()].view(p.shape) for p, o in zip(self.params, self.offsets)]
         self._zero_cache = {}
         self.world_size = 1
+        self.rank = 0
         self.force_exchange = False
         self.bucket_ready = None  # set while a data-parallel step is being captured in segments (train/graph_step.py)
         self.capture_stream = None
@@ -398,6 +399,7 @@ class ParamArena:
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised")
         self.world_size = dist.get_world_size()
+        self.rank = dist.get_rank()
         self.n_buckets = n_buckets
         # replicas must start from identical weights (DDP broadcasts rank 0's copy at wrap time)
         dist.broadcast(self.flat, src=0)

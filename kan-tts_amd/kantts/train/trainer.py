@@ -360,8 +360,10 @@ class GAN_Trainer(Trainer):
                     g = self._graphs[key] = GraphedGanStep(self.model, self.optimizer, self.scheduler, self.criterion,
                                                            self.config, y, x, steps=self.steps)
                 except (NotImplementedError, ValueError) as exc:
-                    # NSF generators (host-seeded excitation), non-arena optimizers, a capture the runtime refused
-                    # (gan_graph_step.CaptureRefused; data-parallel: on any rank, agreed across ranks): the step cannot be
+                    # non-arena optimizers, an NSF generator the device-drawn excitation does not take (a library without
+                    # kantts_nsf_draw_states, more than 16 harmonics: it keeps its host-seeded draws), a capture the runtime refused
+                    # (gan_graph_step.CaptureRefused; data-parallel: on any rank, agreed across ranks; a source module that
+                    # GraphedGanStep had switched to device draws is back on host-seeded ones by then): the step cannot be
                     # captured.  Any other error (out of memory, a kernel's failed check in the warm-up steps) propagates.
                     # Say so once and keep training with the eager step (the run must not die thousands of steps in,
                     # when both phases first become active).
