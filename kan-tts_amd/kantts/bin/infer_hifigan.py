@@ -87,32 +87,15 @@ def _load_feats(model, path, device):
 
 
 def _chunked_vocoder(model, slots, device, seed):
-    """The chunked player of ``model``; either class refuses what it cannot play, loudly."""
-    if model.nsf_enable and not model.causal and model.out_channels == 1:
-        from kantts.models.hifigan.chunked_nc_nsf import ChunkedNCNSFVocoder
+    """The chunked player of ``model``; the class refuses what it cannot play, loudly."""
+    from kantts.models.hifigan import chunked_vocoder_class
 
-        vocoder = ChunkedNCNSFVocoder(model, slots=slots, graph=device.type == "cuda", seed=seed)
-        logging.info("Non-causal NSF generator: the waveform comes %d samples (%d frames) after the frames it is made of.",
-                     vocoder.delay_samples, vocoder.flush_frames)
-        return vocoder
-    if model.nsf_enable:
-        from kantts.models.hifigan.chunked_nsf import ChunkedNSFVocoder
-
-        return ChunkedNSFVocoder(model, slots=slots, graph=device.type == "cuda", seed=seed)
-    if model.out_channels > 1:
-        from kantts.models.hifigan.chunked_mb import ChunkedMBVocoder
-
-        return ChunkedMBVocoder(model, slots=slots, graph=device.type == "cuda")
-    if not model.causal:
-        from kantts.models.hifigan.chunked_nc import ChunkedNCVocoder
-
-        vocoder = ChunkedNCVocoder(model, slots=slots, graph=device.type == "cuda")
-        logging.info("Non-causal generator: the waveform comes %d samples (%d frames) after the frames it is made of.",
-                     vocoder.delay_samples, vocoder.flush_frames)
-        return vocoder
-    from kantts.models.hifigan.chunked import ChunkedVocoder
-
-    return ChunkedVocoder(model, slots=slots, graph=device.type == "cuda")
+    cls = chunked_vocoder_class(model, lookahead=True)
+    vocoder = cls(model, slots=slots, graph=device.type == "cuda", **({"seed": seed} if cls._plays_nsf else {}))
+    if cls._plays_noncausal:
+        logging.info("Non-causal%s generator: the waveform comes %d samples (%d frames) after the frames it is made of.",
+                     " NSF" if model.nsf_enable else "", vocoder.delay_samples, vocoder.flush_frames)
+    return vocoder
 
 
 def _infer_many(model, mel_lst, output_dir, sr, chunk_frames, slots, device, seed=0):

@@ -18,6 +18,10 @@ kantts_sconv_rows_launch.  ``play_many`` builds continuous batching on it:
     wav = v.step(mel, rows=[8, 3, 0, 8])                  # samples at and after rows[s] * hop of slot s are 0.0
     for index, wav in v.play_many(mels, chunk_frames=8): ...   # utterances of any lengths through all slots
 
+``synthesize`` and ``play_many`` are defined here once, for this class and its four subclasses (chunked_nsf, chunked_mb,
+chunked_nc, chunked_nc_nsf): one schedule (``schedule``) on three per-class facts, the emission contract in the hook block
+of the class.  kantts.models.streaming.StreamingTTS is written on the same three facts.
+
 History rows per layer (at that layer's token rate): ``(k - 1) * dilation`` for a convolution, ``J - 1`` input tokens
 for an upsampling stage (J polyphase taps: the transposed convolution alone has kernel / stride, the fused dual-path
 stage of ``Generator._dual_path_weight`` max(kernel / stride, 1 + ceil(6 / stride))).
@@ -37,6 +41,64 @@ _MAX_K, _MAX_STEP = 11, 7
 def sconv_supported(Cin, N, K, step):
     return (Cin % 8 == 0 and 16 <= Cin <= 512 and (N == 1 or 16 <= N <= 4096) and 1 <= K <= _MAX_K
             and 1 <= step <= _MAX_STEP)
+
+
+def slot_ints(vals, what, slots, bools=False):
+    """One integer per slot -- a sequence of ints, or an integer tensor of shape (slots,) on the host or on the device --
+    as a host list, or None for a device tensor (it is not read back).  The one check of ``rows``, ``end`` and ``last``;
+    what differs between the three is applied by the caller, on purpose:
+
+    rows   a count: host values must lie in [0, Tc] (a ValueError), device values are clamped by the kernel.  Bool tensors
+           are refused (``bools``) -- except that ``ChunkedMBVocoder.step`` takes a HOST bool tensor, which it hands on as
+           a list of 0 / 1 (a device one reaches the base class and is refused there): it always did
+    end    a frame count: values of a sequence below -1 become -1 ("open"); a tensor, on the host or on the device, is
+           copied as it is (the kernel reads any negative value as open).  Bool tensors are refused
+    last   a flag: host values become 0 / 1, device values are copied as they are (the kernel tests for non-zero); bool
+           tensors are accepted"""
+    if torch.is_tensor(vals):
+        if vals.dtype.is_floating_point or vals.dtype.is_complex or (vals.dtype == torch.bool and not bools):
+            raise ValueError("%s must be integers, got dtype %s" % (what, vals.dtype))
+        if tuple(vals.shape) != (slots,):
+            raise ValueError("%s must have shape (%d,), got %s" % (what, slots, tuple(vals.shape)))
+        if vals.device.type != "cpu":
+            return None
+        vals = vals.tolist()
+    try:
+        vals = [operator.index(v) for v in vals]
+    except TypeError:
+        raise ValueError("%s must be a sequence of %d ints or an integer tensor" % (what, slots)) from None
+    if len(vals) != slots:
+        raise ValueError("%s must hold one integer per slot (%d), got %d" % (what, slots, len(vals)))
+    return vals
+
+
+def schedule(lengths, slots, chunk_frames, flush_frames=0):
+    """The one schedule of continuous batching, on host integers alone: utterances of ``lengths`` frames through ``slots``
+    slots that take up to ``chunk_frames`` frames per step.  A free slot takes the next unassigned utterance, in input
+    order and slot order, before a step; a slot at ``pos`` of an utterance of T frames takes
+    min(chunk_frames, T + flush_frames - pos) frames, of which max(0, min(take, T - pos)) are live (the others are flush
+    frames behind the utterance's end), and is free again once pos >= T + flush_frames.  Yields, per step, one entry per
+    slot: None for an idle slot, else ``(index, pos, take, live, done)`` with ``pos`` the frames consumed BEFORE the step
+    (0: the slot has just taken the utterance) and ``done`` true when the slot is free after it."""
+    cur, pos, nxt = [None] * slots, [0] * slots, 0
+    while True:
+        for s in range(slots):
+            if cur[s] is None and nxt < len(lengths):
+                cur[s], pos[s], nxt = nxt, 0, nxt + 1
+        if all(c is None for c in cur):
+            return
+        plan = [None] * slots
+        for s, c in enumerate(cur):
+            if c is not None:
+                take = min(chunk_frames, lengths[c] + flush_frames - pos[s])
+                plan[s] = (c, pos[s], take, max(0, min(take, lengths[c] - pos[s])),
+                           pos[s] + take >= lengths[c] + flush_frames)
+        yield plan
+        for s, p in enumerate(plan):
+            if p is not None:
+                pos[s] += p[2]
+                if p[4]:
+                    cur[s] = None
 
 
 class _Layer:
@@ -222,6 +284,29 @@ class ChunkedVocoder:
     def _assign(self, slot, index):
         """``play_many``: ``slot`` (just reset) takes utterance ``index``."""
 
+    # The emission contract: three facts per class, on host integers alone.  ``pos``: frames the slot's vocoder has
+    # consumed since its reset, ``n``: the frames it takes now, ``T``: the frames of its utterance.  ``play_many``,
+    # ``synthesize`` and kantts.models.streaming.StreamingTTS are written on them and on nothing else of a subclass.
+    flush_frames = 0  # 1. frames a slot must take behind its utterance's last one
+    _end_kw = None    # 2. the keyword through which ``step`` is told an utterance's end (None: it is not told), and
+
+    def _end_of(self, pos, n, T):
+        """the slot's integer under that keyword; an idle slot asks with (0, 0, -1)."""
+
+    def _emitted(self, pos, n, T):
+        """3. (offset, count) of the slot's samples inside the step's output."""
+        return 0, n * self.hop
+
+    _solo = False  # ``synthesize`` advances its slot alone, through the ``rows`` form of a step (``_play_one``)
+
+    def _solo_end(self, slot, pos, n, T):
+        """The keyword arguments that tell a step of ``_play_one`` the end of ``slot`` alone: the others are idle."""
+        if self._end_kw is None:
+            return {}
+        ends = [self._end_of(0, 0, -1)] * self.slots
+        ends[slot] = self._end_of(pos, n, T)
+        return {self._end_kw: ends}
+
     def _save_state(self):
         return self.arena.clone()
 
@@ -311,22 +396,10 @@ class ChunkedVocoder:
 
     def _set_rows(self, rows, Tc):
         """Validate per-slot counts and copy them into the persistent device buffer the launches read."""
-        if torch.is_tensor(rows):
-            if rows.dtype.is_floating_point or rows.dtype.is_complex or rows.dtype == torch.bool:
-                raise ValueError("rows must be integers, got dtype %s" % rows.dtype)
-            if tuple(rows.shape) != (self.slots,):
-                raise ValueError("rows must have shape (%d,), got %s" % (self.slots, tuple(rows.shape)))
-            if rows.device.type == "cpu":
-                rows = rows.tolist()
-            else:  # not read back: the kernel clamps what it finds
-                self._rows.copy_(rows)
-                return
-        try:
-            vals = [operator.index(r) for r in rows]
-        except TypeError:
-            raise ValueError("rows must be a sequence of %d ints or an integer tensor" % self.slots) from None
-        if len(vals) != self.slots:
-            raise ValueError("rows must hold one count per slot (%d), got %d" % (self.slots, len(vals)))
+        vals = slot_ints(rows, "rows", self.slots)
+        if vals is None:  # on the device, not read back: the kernel clamps what it finds
+            self._rows.copy_(rows)
+            return
         if any(r < 0 or r > Tc for r in vals):
             raise ValueError("rows must lie in [0, Tc = %d], got %s" % (Tc, vals))
         self._rows.copy_(torch.tensor(vals, dtype=torch.int32))
@@ -354,34 +427,52 @@ class ChunkedVocoder:
         self._parity ^= 1
         return wav
 
-    def synthesize(self, mel_full, chunk_frames=8, slot=0):
-        """Generator over the chunks of one utterance: mel_full (C_mel, T) or (1, C_mel, T) played on ``slot`` from zero
-        state (the other slots are fed zeros and advance with it).  The last partial chunk is padded with zero frames and
-        its output trimmed.  Yields (1, n_samples) tensors."""
+    def synthesize(self, mel_full, chunk_frames=8, slot=0, **identity):
+        """Generator over the chunks of one utterance: mel_full (C, T) or (1, C, T), C what ``step`` takes, played on
+        ``slot`` from zero state; ``identity`` goes to ``reset`` (the NSF classes: ``key=``).  A causal single-band class
+        feeds the other slots zeros and they advance with it; every other class advances ``slot`` alone (``_play_one``).
+        The last partial chunk is padded with zero frames and its output trimmed; ``flush_frames`` frames follow the
+        utterance's last one.  Yields the (1, n_samples) tensors of the chunks that emit samples, T * hop in all."""
         if mel_full.dim() == 3:
             mel_full = mel_full[0]
         T = int(mel_full.shape[1])
         n = int(chunk_frames)
         if n < 1:
             raise ValueError("chunk_frames must be >= 1")
-        self.reset(slot)
+        self.reset(slot, **identity)
         yield from self._play_one(mel_full, T, n, slot)
 
     def _play_one(self, mel_full, T, n, slot):
-        for t0 in range(0, T, n):
-            t1 = min(T, t0 + n)
+        """The steps of ``synthesize`` on a slot that has just been reset."""
+        if not self._solo:
+            # The causal single-band classes keep the plain lockstep step ON PURPOSE: every slot advances (the others on
+            # zero frames), and the plain step has a graph key of its own, so what ``synthesize`` leaves in the other
+            # slots and in ``captures`` is observable and stays what it was.
+            for t0 in range(0, T, n):
+                t1 = min(T, t0 + n)
+                mel = torch.zeros(self.slots, self._step_channels, n, device=self.device, dtype=torch.float32)
+                mel[slot, :, :t1 - t0] = mel_full[:, t0:t1]
+                yield self.step(mel)[slot, :, :(t1 - t0) * self.hop]
+            return
+        for plan in schedule([T] if T + self.flush_frames else [], 1, n, self.flush_frames):  # nothing to take: no steps
+            _, pos, take, live, _ = plan[0]
             mel = torch.zeros(self.slots, self._step_channels, n, device=self.device, dtype=torch.float32)
-            mel[slot, :, :t1 - t0] = mel_full[:, t0:t1]
-            yield self.step(mel)[slot, :, :(t1 - t0) * self.hop]
+            mel[slot, :, :live] = mel_full[:, pos:pos + live]
+            rows = [0] * self.slots
+            rows[slot] = take
+            wav = self.step(mel, rows=rows, **self._solo_end(slot, pos, take, T))
+            off, cnt = self._emitted(pos, take, T)
+            if cnt:
+                yield wav[slot, :, off:off + cnt]
 
     def play_many(self, mels, chunk_frames=8):
-        """Continuous batching: a generator that plays the utterances ``mels`` -- a sequence of (C_mel, T_i) tensors,
-        T_i >= 1 -- through all slots, yielding ``(index, wav)`` with wav (1, n * hop) for the ``n`` frames utterance
-        ``index`` advanced by.  The schedule: ``reset()`` once; the slots take utterances in input order; every step has
-        room for ``chunk_frames`` frames per slot and slot ``s`` feeds min(chunk_frames, remaining) of its utterance (0
-        without one); after the step the live slots yield in slot order; a slot whose utterance has ended is
-        ``reset(slot)`` and takes the next unassigned utterance before the next step.  The concatenated chunks of an
-        utterance equal ``synthesize`` of it bit for bit."""
+        """Continuous batching, for every class: a generator that plays the utterances ``mels`` -- a sequence of (C, T_i)
+        tensors, T_i >= 1 -- through all slots, yielding ``(index, wav)`` with wav (1, samples) what utterance ``index``
+        emitted in a step (a causal single-band class: n * hop for the ``n`` frames it advanced by; steps in which it
+        emitted nothing yield nothing).  ``reset()`` once, then the steps of ``schedule``: the slots that have just taken
+        an utterance are named it (``_assign``) in slot order; one ``step`` with every slot's count and end; the slots
+        yield in slot order; a slot whose utterance is through (``flush_frames`` included) is ``reset(slot)``.  The
+        concatenated chunks of an utterance equal ``synthesize`` of it bit for bit."""
         n = int(chunk_frames)
         if n < 1:
             raise ValueError("chunk_frames must be >= 1")
@@ -389,28 +480,24 @@ class ChunkedVocoder:
         for i, m in enumerate(mels):
             if m.dim() != 2 or m.shape[0] != self._step_channels or m.shape[1] < 1:
                 raise ValueError("mels[%d] must be (%d, T >= 1), got %s" % (i, self._step_channels, tuple(m.shape)))
+        lengths = [int(m.shape[1]) for m in mels]
         self.reset()
-        cur, pos, nxt = [None] * self.slots, [0] * self.slots, 0
         buf = torch.zeros(self.slots, self._step_channels, n, device=self.device, dtype=torch.float32)
-        while True:
-            for s in range(self.slots):
-                if cur[s] is None and nxt < len(mels):
-                    cur[s], pos[s], nxt = nxt, 0, nxt + 1
-                    self._assign(s, cur[s])
-            if all(c is None for c in cur):
-                return
-            counts = [0] * self.slots
-            for s, c in enumerate(cur):
-                if c is not None:
-                    counts[s] = min(n, int(mels[c].shape[1]) - pos[s])
-                    buf[s, :, :counts[s]] = mels[c][:, pos[s]:pos[s] + counts[s]]
-            wav = self.step(buf, rows=counts)
-            for s, c in enumerate(cur):
-                if c is not None:
-                    yield c, wav[s, :, :counts[s] * self.hop]
-            for s, c in enumerate(cur):
-                if c is not None:
-                    pos[s] += counts[s]
-                    if pos[s] >= int(mels[c].shape[1]):
-                        self.reset(s)
-                        cur[s] = None
+        for plan in schedule(lengths, self.slots, n, self.flush_frames):
+            rows, ends = [0] * self.slots, [self._end_of(0, 0, -1)] * self.slots
+            for s, p in enumerate(plan):
+                if p is not None:
+                    c, pos, take, live, _ = p
+                    if pos == 0:
+                        self._assign(s, c)
+                    rows[s], ends[s] = take, self._end_of(pos, take, lengths[c])
+                    buf[s, :, :live] = mels[c][:, pos:pos + live]
+            wav = self.step(buf, rows=rows, **({} if self._end_kw is None else {self._end_kw: ends}))
+            for s, p in enumerate(plan):
+                if p is not None:
+                    off, cnt = self._emitted(p[1], p[2], lengths[p[0]])
+                    if cnt:
+                        yield p[0], wav[s, :, off:off + cnt]
+            for s, p in enumerate(plan):
+                if p is not None and p[4]:
+                    self.reset(s)

@@ -20,19 +20,27 @@ rows, emits late, and flushes when told that the utterance ends.  Everything els
 is up to ``D * B`` samples shorter than its frames, the chunk that carries ``last`` that much longer.  ``hip.mb_emit`` is
 the one host definition of the rule (the table is in include/kantts_hip.h).  After ``last`` the tail's own state of the slot
 is as after a reset; the layers in front of it are not: ``reset(slot)`` before the slot takes another utterance, as
-``play_many`` does.
+``play_many`` does.  ``synthesize`` and ``play_many`` are the base class's, on ``last`` from the utterance's frame cursor and
+``mb_emitted``, the stateless form of the rule.
 
 The emulated C ABI (oracle/cabi_numpy.py) has no entry point for the tail: the class says so at construction.
 """
-import operator
-
 import torch
 
 import kantts._hip as hip
-from kantts.models.hifigan.chunked import ChunkedVocoder
+from kantts.models.hifigan.chunked import ChunkedVocoder, slot_ints
 
 _NO_TAIL = ("the loaded C ABI has no multi-band tail (kantts_mb_tail_rows): ChunkedMBVocoder needs libkantts_hip.so, not the "
             "emulated ABI")
+
+
+def mb_emitted(pos, n, T, low_hop, D, B):
+    """(offset, count) of the samples a slot emits in the step that takes it from ``pos`` by ``n`` of its utterance's ``T``
+    frames (``low_hop`` sub-band rows per frame, a look-ahead of ``D`` rows, ``B`` bands).  No running count is needed:
+    after ``pos`` frames without ``last`` the synthesis holds back exactly min(pos * low_hop, D) rows, and ``last`` is set
+    in the step that reaches T.  ``hip.mb_emit`` stays the rule."""
+    e, _ = hip.mb_emit(min(pos * low_hop, D), n * low_hop, n > 0 and pos + n >= T, D)
+    return 0, e * B
 
 
 class ChunkedMBVocoder(ChunkedVocoder):
@@ -48,6 +56,7 @@ class ChunkedMBVocoder(ChunkedVocoder):
     multiple of 4 input channels in 4..512), and a library without the entry point."""
 
     _plays_multiband = True
+    _end_kw, _solo = "last", True
 
     def __init__(self, generator, pqmf=None, slots=1, graph=True, max_graphs=8):
         g = generator
@@ -126,24 +135,6 @@ class ChunkedMBVocoder(ChunkedVocoder):
             raise RuntimeError("kantts_mb_tail_rows declined the generator it was planned for")
         return out.view(S, 1, -1)
 
-    def _host_values(self, vals, what):
-        """``rows`` / ``last`` of a step as a host list, or None for a device tensor."""
-        if torch.is_tensor(vals):
-            if vals.dtype.is_floating_point or vals.dtype.is_complex:
-                raise ValueError("%s must be integers, got dtype %s" % (what, vals.dtype))
-            if tuple(vals.shape) != (self.slots,):
-                raise ValueError("%s must have shape (%d,), got %s" % (what, self.slots, tuple(vals.shape)))
-            if vals.device.type != "cpu":
-                return None
-            vals = vals.tolist()
-        try:
-            vals = [operator.index(v) for v in vals]
-        except TypeError:
-            raise ValueError("%s must be a sequence of %d ints or an integer tensor" % (what, self.slots)) from None
-        if len(vals) != self.slots:
-            raise ValueError("%s must hold one entry per slot (%d), got %d" % (what, self.slots, len(vals)))
-        return vals
-
     def step(self, mel, rows=None, last=None):
         """mel (slots, C_mel, Tc), Tc >= 1 -> wav (slots, 1, Tc * hop + D * B): the samples every slot emits in front, 0.0
         behind.  ``rows`` as in ``ChunkedVocoder.step`` (None: every slot takes Tc frames).  ``last``: ``slots`` flags (a
@@ -154,10 +145,10 @@ class ChunkedMBVocoder(ChunkedVocoder):
         if mel.dim() != 3 or mel.shape[0] != self.slots or mel.shape[1] != self._step_channels or mel.shape[2] < 1:
             raise ValueError("mel must be (slots=%d, %d, Tc >= 1), got %s" % (self.slots, self._step_channels, tuple(mel.shape)))
         Tc = int(mel.shape[2])
-        h_rows = [Tc] * self.slots if rows is None else self._host_values(rows, "rows")
+        h_rows = [Tc] * self.slots if rows is None else slot_ints(rows, "rows", self.slots, bools=True)  # see slot_ints
         if torch.is_tensor(rows) and h_rows is not None:
             rows = h_rows
-        h_last = [0] * self.slots if last is None else self._host_values(last, "last")
+        h_last = [0] * self.slots if last is None else slot_ints(last, "last", self.slots, bools=True)
         if h_last is None:
             self._last.copy_(last.to(torch.int32))
         else:
@@ -181,57 +172,13 @@ class ChunkedMBVocoder(ChunkedVocoder):
         flags = [int(slot is None or s == int(slot)) for s in range(self.slots)]
         return self.step(mel, rows=[0] * self.slots, last=flags)
 
+    def _end_of(self, pos, n, T):
+        return int(n > 0 and pos + n >= T)  # the end of an utterance: from its frame cursor
+
+    def _emitted(self, pos, n, T):
+        return mb_emitted(pos, n, T, self.low_hop, self.D, self.B)
+
     def _play_one(self, mel_full, T, n, slot):
-        """Only ``slot`` advances (the others keep their state); the final chunk carries ``last``.  Chunks that emit nothing
-        (the first frames of a short chunk size are all held back) are not yielded."""
         if self.pending is None:
             raise RuntimeError("ChunkedMBVocoder: the slots were advanced with device counts; reset() before synthesize")
-        for t0 in range(0, T, n):
-            t1 = min(T, t0 + n)
-            mel = torch.zeros(self.slots, self._step_channels, n, device=self.device, dtype=torch.float32)
-            mel[slot, :, :t1 - t0] = mel_full[:, t0:t1]
-            rows, last = [0] * self.slots, [0] * self.slots
-            rows[slot], last[slot] = t1 - t0, int(t1 == T)
-            wav = self.step(mel, rows=rows, last=last)
-            if self.counts[slot]:
-                yield wav[slot, :, :self.counts[slot]]
-
-    def play_many(self, mels, chunk_frames=8):
-        """``ChunkedVocoder.play_many`` for multi-band generators: the same schedule; the step in which an utterance's frame
-        cursor reaches its end carries ``last`` for that slot, so the chunks of utterance ``index`` have variable lengths
-        that add up to ``T_index * hop`` (chunks that emit nothing are not yielded), and equal ``synthesize`` of it bit for
-        bit."""
-        n = int(chunk_frames)
-        if n < 1:
-            raise ValueError("chunk_frames must be >= 1")
-        mels = list(mels)
-        for i, m in enumerate(mels):
-            if m.dim() != 2 or m.shape[0] != self._step_channels or m.shape[1] < 1:
-                raise ValueError("mels[%d] must be (%d, T >= 1), got %s" % (i, self._step_channels, tuple(m.shape)))
-        self.reset()
-        cur, pos, nxt = [None] * self.slots, [0] * self.slots, 0
-        buf = torch.zeros(self.slots, self._step_channels, n, device=self.device, dtype=torch.float32)
-        while True:
-            for s in range(self.slots):
-                if cur[s] is None and nxt < len(mels):
-                    cur[s], pos[s], nxt = nxt, 0, nxt + 1
-                    self._assign(s, cur[s])
-            if all(c is None for c in cur):
-                return
-            rows, last = [0] * self.slots, [0] * self.slots
-            for s, c in enumerate(cur):
-                if c is not None:
-                    T = int(mels[c].shape[1])
-                    rows[s] = min(n, T - pos[s])
-                    last[s] = int(pos[s] + rows[s] >= T)  # the end of an utterance: from its frame cursor
-                    buf[s, :, :rows[s]] = mels[c][:, pos[s]:pos[s] + rows[s]]
-            wav = self.step(buf, rows=rows, last=last)
-            for s, c in enumerate(cur):
-                if c is not None and self.counts[s]:
-                    yield c, wav[s, :, :self.counts[s]]
-            for s, c in enumerate(cur):
-                if c is not None:
-                    pos[s] += rows[s]
-                    if last[s]:
-                        self.reset(s)
-                        cur[s] = None
+        yield from super()._play_one(mel_full, T, n, slot)

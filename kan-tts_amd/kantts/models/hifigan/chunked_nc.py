@@ -16,7 +16,8 @@ of its stream, counted from the slot's reset, is true row n - d of the utterance
 Every layer's output is stored as 0.0 outside the utterance (the reference zero-pads every layer at the utterance's edges;
 zeros pass through LeakyReLU and sin(h) + h), input rows at or beyond the end are flush rows that are never loaded, and a
 slot is done ``flush_frames = ceil(delay_samples / hop)`` frames after its last one.  csrc/sconv_sym.hip is the kernel,
-kantts._hip.nc_emit the emission rule.
+kantts._hip.nc_emit the emission rule; ``synthesize`` and ``play_many`` are the base class's, fed ``flush_frames``, ``end``
+and that rule.
 
     v = ChunkedNCVocoder(generator, slots=S, graph=True)      # generator: causal=False, eval, on the device
     v.delay_samples, v.flush_frames                           # ChunkedNCVocoder.delay_of(generator) needs no device
@@ -24,13 +25,11 @@ kantts._hip.nc_emit the emission rule.
     for wav in v.synthesize(mel_full, chunk_frames=8): ...    # chunks add up to T * hop samples
     for index, wav in v.play_many(mels, chunk_frames=8): ...
 """
-import operator
-
 import torch
 
 import kantts._hip as hip
 from kantts._hip import ops
-from kantts.models.hifigan.chunked import ChunkedVocoder
+from kantts.models.hifigan.chunked import ChunkedVocoder, slot_ints
 from kantts.models.hifigan.layers import Conv1d, ConvTranspose1d, effective_weight
 
 
@@ -121,6 +120,7 @@ class ChunkedNCVocoder(ChunkedVocoder):
     layer contract declines."""
 
     _plays_noncausal = True
+    _end_kw, _solo = "end", True
     _conv_cls, _up_cls = Conv1d, ConvTranspose1d
 
     def __init__(self, generator, slots=1, graph=True, max_graphs=8):
@@ -241,20 +241,8 @@ class ChunkedNCVocoder(ChunkedVocoder):
             self._end[int(slot)] = -1
 
     def _set_end(self, end):
-        if torch.is_tensor(end):
-            if end.dtype.is_floating_point or end.dtype.is_complex or end.dtype == torch.bool:
-                raise ValueError("end must be integers, got dtype %s" % end.dtype)
-            if tuple(end.shape) != (self.slots,):
-                raise ValueError("end must have shape (%d,), got %s" % (self.slots, tuple(end.shape)))
-            self._end.copy_(end)
-            return
-        try:
-            vals = [operator.index(e) for e in end]
-        except TypeError:
-            raise ValueError("end must be a sequence of %d ints or an integer tensor" % self.slots) from None
-        if len(vals) != self.slots:
-            raise ValueError("end must hold one frame count per slot (%d), got %d" % (self.slots, len(vals)))
-        self._end.copy_(torch.tensor([max(e, -1) for e in vals], dtype=torch.int32))
+        vals = slot_ints(end, "end", self.slots)
+        self._end.copy_(end if torch.is_tensor(end) else torch.tensor([max(e, -1) for e in vals], dtype=torch.int32))
 
     def step(self, mel, rows=None, end=None):
         """mel (slots, C_mel, Tc) -> wav (slots, 1, Tc * hop), ``delay_samples`` late (see the class).  ``rows`` as in
@@ -268,75 +256,14 @@ class ChunkedNCVocoder(ChunkedVocoder):
             self._set_end(end)
         return super().step(mel, rows=[int(mel.shape[2])] * self.slots if rows is None else rows)
 
-    def _emit(self, wav, slot, pos, n, T):
-        off, cnt = hip.nc_emit(pos, n, T, self.delay_samples, self.hop)
-        return wav[slot, :, off:off + cnt]
+    def _end_of(self, pos, n, T):
+        return T
 
-    def synthesize(self, mel_full, chunk_frames=8, slot=0):
-        """Generator over the chunks of one utterance: mel_full (C_mel, T) or (1, C_mel, T) played on ``slot`` from zero
-        state, flush frames included (the other slots hold their state).  Yields (1, n_samples) tensors, the first after
-        about ``flush_frames`` frames; they add up to T * hop samples."""
-        if mel_full.dim() == 3:
-            mel_full = mel_full[0]
-        T = int(mel_full.shape[1])
-        n = int(chunk_frames)
-        if n < 1:
-            raise ValueError("chunk_frames must be >= 1")
-        self.reset(slot)
-        yield from self._play_flushed(mel_full, T, n, slot)
+    def _emitted(self, pos, n, T):
+        return hip.nc_emit(pos, n, T, self.delay_samples, self.hop)
 
-    def _play_flushed(self, mel_full, T, n, slot):
-        """The steps of ``synthesize`` on a slot that has just been reset: the utterance's T frames, then the flush frames."""
-        self._end[slot] = T
-        total = T + self.flush_frames
-        for t0 in range(0, total, n):
-            m = min(n, total - t0)
-            live = max(0, min(m, T - t0))
-            mel = torch.zeros(self.slots, self._step_channels, n, device=self.device, dtype=torch.float32)
-            mel[slot, :, :live] = mel_full[:, t0:t0 + live]
-            counts = [0] * self.slots
-            counts[slot] = m
-            wav = self._emit(self.step(mel, rows=counts), slot, t0, m, T)
-            if wav.shape[1]:
-                yield wav
-
-    def play_many(self, mels, chunk_frames=8):
-        """Continuous batching with the schedule of ``ChunkedVocoder.play_many``; a slot keeps taking flush frames after
-        its utterance's last frame and is reset, and takes the next utterance, when it has emitted T * hop samples.
-        Yields ``(index, wav)`` for every step in which utterance ``index`` emitted samples."""
-        n = int(chunk_frames)
-        if n < 1:
-            raise ValueError("chunk_frames must be >= 1")
-        mels = list(mels)
-        for i, m in enumerate(mels):
-            if m.dim() != 2 or m.shape[0] != self._step_channels or m.shape[1] < 1:
-                raise ValueError("mels[%d] must be (%d, T >= 1), got %s" % (i, self._step_channels, tuple(m.shape)))
-        self.reset()
-        cur, pos, nxt = [None] * self.slots, [0] * self.slots, 0
-        buf = torch.zeros(self.slots, self._step_channels, n, device=self.device, dtype=torch.float32)
-        while True:
-            for s in range(self.slots):
-                if cur[s] is None and nxt < len(mels):
-                    cur[s], pos[s], nxt = nxt, 0, nxt + 1
-                    self._assign(s, cur[s])
-            if all(c is None for c in cur):
-                return
-            counts, end = [0] * self.slots, [-1] * self.slots
-            for s, c in enumerate(cur):
-                if c is not None:
-                    T = end[s] = int(mels[c].shape[1])
-                    counts[s] = min(n, T + self.flush_frames - pos[s])
-                    live = max(0, min(counts[s], T - pos[s]))
-                    buf[s, :, :live] = mels[c][:, pos[s]:pos[s] + live]
-            wav = self.step(buf, rows=counts, end=end)
-            for s, c in enumerate(cur):
-                if c is not None:
-                    w = self._emit(wav, s, pos[s], counts[s], end[s])
-                    if w.shape[1]:
-                        yield c, w
-            for s, c in enumerate(cur):
-                if c is not None:
-                    pos[s] += counts[s]
-                    if pos[s] >= end[s] + self.flush_frames:
-                        self.reset(s)
-                        cur[s] = None
+    def _solo_end(self, slot, pos, n, T):
+        """The end is kept between steps: written once, for ``slot`` alone, so the other slots' ends stay what was given."""
+        if pos == 0:
+            self._end[slot] = T
+        return {}

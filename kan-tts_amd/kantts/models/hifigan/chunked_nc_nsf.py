@@ -145,13 +145,3 @@ class ChunkedNCNSFVocoder(_Excitation, ChunkedNCVocoder):
             return super().step(feats, rows=rows, end=end)
         finally:
             self._noise = None
-
-    def synthesize(self, feats_full, chunk_frames=8, slot=0, key=0):
-        """As ``ChunkedNCVocoder.synthesize`` on (C_mel + 2, T) features; the utterance plays as ``key``."""
-        if feats_full.dim() == 3:
-            feats_full = feats_full[0]
-        n = int(chunk_frames)
-        if n < 1:
-            raise ValueError("chunk_frames must be >= 1")
-        self.reset(slot, key=key)
-        yield from self._play_flushed(feats_full, int(feats_full.shape[1]), n, slot)

@@ -20,7 +20,7 @@ Its per-slot (start, count) pairs travel in ONE host-to-device copy, and a step 
 launches no vocoder step.  A multi-band voice (``generator.out_channels > 1``) plays through ``ChunkedMBVocoder``, whose
 synthesis bank holds back up to ``D * B`` samples per slot: the same copy then also carries a flag per slot, set in the step
 that hands over the utterance's last frame, and that step emits everything held back -- so the audio of a step is what the
-slot EMITTED (``hip.mb_emit`` on a host count of pending rows), not ``n * hop`` samples, and ``first_sample`` is the running
+slot EMITTED (the vocoder's ``_emitted``), not ``n * hop`` samples, and ``first_sample`` is the running
 sample count of the utterance.  The post-net's look-ahead delays the first frames of an utterance, so a slot is released only
 after its last frame has been VOCODED: until then it takes zero-count acoustic steps while the vocoder drains what is left.
 
@@ -29,7 +29,9 @@ after its last frame has been VOCODED: until then it takes zero-count acoustic s
 causal NSF voice, ``admit`` keys the utterance's excitation, flush frames are read by no launch): its audio
 comes ``vocoder.delay_samples`` late, so the upload also carries every slot's frame count (``end``) and the vocoder's own
 per-slot counts, which exceed the handed-over frames by flush frames once the acoustic frames have run out; the audio of a step
-is what the slot emitted (``hip.nc_emit``), and a slot is released only after the flush.  Without it such a generator is
+is what the slot emitted (``hip.nc_emit``), and a slot is released only after the flush.  ``step`` knows none of the
+classes: it runs on the emission contract of ``ChunkedVocoder`` (flush frames, the end argument, the emitted run) with the
+slot's vocoder at ``vocoded + flushed``, and ``kantts.models.hifigan.chunked_vocoder_class`` picks the class.  Without it such a generator is
 refused as before: the added latency (``vocoder.flush_frames`` frames before the first sample) is a decision.
 
 The emulated C ABI (oracle/cabi_numpy.py) has no hand-over entry point, as it has none of the per-slot ones: the class says
@@ -41,9 +43,7 @@ step.
 import torch
 
 import kantts._hip as hip
-from kantts.models.hifigan.chunked import ChunkedVocoder
-from kantts.models.hifigan.chunked_mb import ChunkedMBVocoder
-from kantts.models.hifigan.chunked_nsf import ChunkedNSFVocoder
+from kantts.models.hifigan import chunked_vocoder_class
 from kantts.models.sambert.slots import AcousticSlots
 
 _NO_HANDOVER = ("the loaded C ABI has no hand-over entry point (kantts_mel_handover_rows): StreamingTTS needs "
@@ -83,33 +83,19 @@ class StreamingTTS:
         self.nsf = None if nsf is None else (float(nsf[0]), float(nsf[1]))
         self.f0_threshold, self.uv_threshold = float(f0_threshold), float(uv_threshold)
         self.pool = AcousticSlots(fsnet, slots=slots, max_steps=max_steps)
-        self.mb = int(generator.out_channels) > 1
-        self.nc = bool(lookahead) and not getattr(generator, "causal", False) and not self.mb
-        if self.nc and nsf_enable:
-            from kantts.models.hifigan.chunked_nc_nsf import ChunkedNCNSFVocoder
-
-            self.vocoder = ChunkedNCNSFVocoder(generator, slots=slots, graph=graph, seed=seed)
-        elif self.nc:
-            from kantts.models.hifigan.chunked_nc import ChunkedNCVocoder
-
-            self.vocoder = ChunkedNCVocoder(generator, slots=slots, graph=graph)
-        elif self.mb:
-            self.vocoder = ChunkedMBVocoder(generator, slots=slots, graph=graph)
-        elif nsf_enable:
-            self.vocoder = ChunkedNSFVocoder(generator, slots=slots, graph=graph, seed=seed)
-        else:
-            self.vocoder = ChunkedVocoder(generator, slots=slots, graph=graph)
+        cls = chunked_vocoder_class(generator, lookahead)
+        self.mb, self.nc = cls._plays_multiband, cls._plays_noncausal
+        self.vocoder = cls(generator, slots=slots, graph=graph, **({"seed": seed} if cls._plays_nsf else {}))
         if self.vocoder.device != self.pool.dev:
             raise ValueError("the acoustic model is on %s, the generator on %s" % (self.pool.dev, self.vocoder.device))
         self.S, self.Tc, self.chunk_steps, self.hop = self.pool.S, int(chunk_frames), int(chunk_frames) // r, self.vocoder.hop
         self.buf = torch.zeros(self.S, want, self.Tc, device=self.pool.dev, dtype=torch.float32)  # the vocoder's step input
         # host cursors per slot: the request it plays (None: free), its live frames, how many are final, how many vocoded,
-        # the samples emitted so far, (multi-band) the low-rate rows the synthesis holds back and (lookahead) the flush
-        # frames the vocoder has taken behind the utterance's last one
+        # the samples emitted so far and (lookahead) the flush frames the vocoder has taken behind the utterance's last one
         self.index = [None] * self.S
         self.frames, self.final, self.vocoded = [0] * self.S, [0] * self.S, [0] * self.S
-        self.samples, self.pending, self.flushed = [0] * self.S, [0] * self.S, [0] * self.S
-        self.flush_frames = self.vocoder.flush_frames if self.nc else 0
+        self.samples, self.flushed = [0] * self.S, [0] * self.S
+        self.flush_frames = self.vocoder.flush_frames
 
     # ------------------------------------------------------------------------------------------------ slots
     def admit(self, s, index, request):
@@ -122,7 +108,7 @@ class StreamingTTS:
         self.vocoder._assign(s, index)
         self.index[s] = index
         self.frames[s] = self.pool.live_rows(s, 0, self.pool.T)
-        self.final[s] = self.vocoded[s] = self.samples[s] = self.pending[s] = self.flushed[s] = 0
+        self.final[s] = self.vocoded[s] = self.samples[s] = self.flushed[s] = 0
         return self.frames[s]
 
     def done(self, s):
@@ -143,7 +129,7 @@ class StreamingTTS:
         self.pool.release(s)
         self.vocoder.reset(s)
         self.index[s] = None
-        self.frames[s] = self.final[s] = self.vocoded[s] = self.samples[s] = self.pending[s] = self.flushed[s] = 0
+        self.frames[s] = self.final[s] = self.vocoded[s] = self.samples[s] = self.flushed[s] = 0
 
     # ------------------------------------------------------------------------------------------------ step
     @torch.no_grad()
@@ -161,49 +147,33 @@ class StreamingTTS:
             if self.index[s] is not None:
                 counts[s] = min(self.chunk_steps, pool.slot[s].steps - pool.slot[s].t)
         outs = pool.step(counts, capacity=self.chunk_steps)
-        rows = [0] * S
+        # the vocoder's side of the step, on the emission contract of ChunkedVocoder: slot s is at vocoded + flushed and
+        # takes the frames handed over plus, once every live frame is final, flush frames behind the last one
+        voc = self.vocoder
+        rows, take, ends = [0] * S, [0] * S, [voc._end_of(0, 0, -1)] * S
         for s in range(S):
             if self.index[s] is not None:
                 self.final[s] = max(self.final[s], min(outs[s][1], self.frames[s]))
-                rows[s] = min(Tc, self.final[s] - self.vocoded[s])
-        flush = [0] * S  # lookahead: frames the vocoder takes behind the last one, once every live frame is final
-        if self.nc:
-            for s in range(S):
-                if self.index[s] is not None and self.final[s] == self.frames[s]:
-                    flush[s] = min(Tc - rows[s], self.flush_frames - self.flushed[s])
+                rows[s] = take[s] = min(Tc, self.final[s] - self.vocoded[s])
+                if self.final[s] == self.frames[s]:
+                    take[s] += min(Tc - rows[s], self.flush_frames - self.flushed[s])
+                ends[s] = voc._end_of(self.vocoded[s] + self.flushed[s], take[s], self.frames[s])
         wav = None
-        if self.nc and (any(rows) or any(flush)):
-            end = [self.frames[s] if self.index[s] is not None else -1 for s in range(S)]
-            A = torch.tensor([self.vocoded, rows, [r + f for r, f in zip(rows, flush)], end],
+        if any(take):
+            A = torch.tensor([self.vocoded, rows, take] + ([ends] if voc._end_kw else []),
                              dtype=torch.int32).to(pool.dev, non_blocking=True)  # the ONE upload
             if any(rows):
                 hip.check(hip.mel_handover(pool.y, A[0], A[1], self.buf, nsf=self.nsf, f0_floor=self.f0_threshold,
                                            uv_threshold=self.uv_threshold), "mel_handover_rows")
-            wav = self.vocoder.step(self.buf, rows=A[2], end=A[3])
-        elif any(rows):
-            # multi-band: the utterance ends for the vocoder in the step that hands over its last frame
-            last = [int(rows[s] > 0 and self.vocoded[s] + rows[s] == self.frames[s]) for s in range(S)]
-            A = torch.tensor([self.vocoded, rows, last] if self.mb else [self.vocoded, rows],
-                             dtype=torch.int32).to(pool.dev, non_blocking=True)  # the ONE upload
-            hip.check(hip.mel_handover(pool.y, A[0], A[1], self.buf, nsf=self.nsf, f0_floor=self.f0_threshold,
-                                       uv_threshold=self.uv_threshold), "mel_handover_rows")
-            wav = self.vocoder.step(self.buf, rows=A[1], last=A[2]) if self.mb else self.vocoder.step(self.buf, rows=A[1])
+            wav = voc.step(self.buf, rows=A[2], **({voc._end_kw: A[3]} if voc._end_kw else {}))
         ret = [None] * S
         for s in range(S):
             if self.index[s] is not None:
                 lo, n = self.vocoded[s], rows[s]
-                m = n * self.hop
-                off = 0
-                if self.mb and n:
-                    v = self.vocoder
-                    e, self.pending[s] = hip.mb_emit(self.pending[s], n * v.low_hop, last[s], v.D)
-                    m = e * v.B
-                if self.nc:
-                    off, m = hip.nc_emit(lo + self.flushed[s], n + flush[s], self.frames[s], self.vocoder.delay_samples, self.hop)
-                    self.flushed[s] += flush[s]
+                off, m = voc._emitted(lo + self.flushed[s], take[s], self.frames[s])
                 audio = wav[s, :, off:off + m] if m else torch.zeros(1, 0, device=pool.dev, dtype=torch.float32)
                 ret[s] = (self.index[s], lo, n, audio)
-                self.vocoded[s] = lo + n
+                self.vocoded[s], self.flushed[s] = lo + n, self.flushed[s] + take[s] - n
         return ret
 
     def play_many(self, requests, results=None):

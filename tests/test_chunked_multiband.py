@@ -588,6 +588,33 @@ def _check_step_arguments(device, graph):
     assert v.counts == [8 * 4, 0] and not bool(tail[1].any())
 
 
+def _check_bool_rows(device):
+    """A HOST bool tensor is taken as ``rows`` (0 / 1 frames per slot), as it always was; a bool tensor on the device reaches
+    the base class and is refused, like every bool tensor given to ``ChunkedVocoder.step``."""
+    from kantts.models.hifigan.chunked_mb import ChunkedMBVocoder
+    from kantts.models.pqmf import PQMF
+
+    G = _gmb().to(device)
+    x = torch.randn(2, 80, 4, generator=torch.Generator().manual_seed(2)).to(device)
+    v, w = (ChunkedMBVocoder(G, pqmf=PQMF().to(device), slots=2, graph=False) for _ in range(2))
+    a = v.step(x, rows=[1, 0], last=[1, 0])
+    b = w.step(x, rows=torch.tensor([True, False]), last=[1, 0])
+    assert torch.equal(a, b) and v.counts == w.counts
+    if device != "cpu":
+        with pytest.raises(ValueError):
+            w.step(x, rows=torch.tensor([True, False]).to(device))
+
+
+def test_chunked_mb_bool_rows():
+    with kernel_source_on_cpu():
+        _check_bool_rows("cpu")
+
+
+@pytest.mark.gpu
+def test_chunked_mb_bool_rows_gpu():
+    _check_bool_rows("cuda")
+
+
 def test_chunked_mb_step_arguments():
     with kernel_source_on_cpu():
         _check_step_arguments("cpu", False)

@@ -624,6 +624,84 @@ def test_chunked_noncausal_bits_gpu():
     _check_bits("cuda", graphs=(False, True))
 
 
+def _check_synthesize_leaves_the_other_slots_alone(device, graph):
+    """Slot 1 is in the middle of an utterance whose ``end`` was given with its first step; ``synthesize`` on slot 0 runs
+    in between; slot 1's remaining bare steps (no ``end``) give the bits of an undisturbed run."""
+    import kantts._hip as hip
+    from kantts.models.hifigan.chunked_nc import ChunkedNCVocoder
+
+    hip.set_precision("fp32")
+    v = ChunkedNCVocoder(_gnc("s4x2", device), slots=2, graph=graph)
+    other, mine = _mels(device, [6, 9])
+    T, n = 9, 4
+
+    def play(disturb):
+        v.reset()
+        outs, pos = [], 0
+        while pos < T + v.flush_frames:
+            m = min(n, T + v.flush_frames - pos)
+            live = max(0, min(m, T - pos))
+            buf = torch.zeros(2, 80, n, device=device)
+            buf[1, :, :live] = mine[:, pos:pos + live]
+            wav = v.step(buf, rows=[0, m], end=[-1, T] if pos == 0 else None)
+            off, cnt = hip.nc_emit(pos, m, T, v.delay_samples, v.hop)
+            outs.append(wav[1, :, off:off + cnt].clone())
+            pos += m
+            if disturb and pos in (n, T + 3):  # once among the live frames, once among the flush frames
+                assert torch.cat(list(v.synthesize(other, chunk_frames=n, slot=0)), dim=1).shape == (1, 6 * v.hop)
+                assert v._end.tolist() == [6, T]
+        return torch.cat(outs, dim=1)
+
+    a, b = play(False), play(True)
+    assert a.shape == (1, T * v.hop) and torch.equal(a, b)
+
+
+def test_synthesize_leaves_the_other_slots_alone_kernel_source():
+    with kernel_source_on_cpu():
+        _check_synthesize_leaves_the_other_slots_alone("cpu", False)
+
+
+@pytest.mark.gpu
+def test_synthesize_leaves_the_other_slots_alone_gpu():
+    _check_synthesize_leaves_the_other_slots_alone("cuda", True)
+
+
+def test_end_as_a_tensor_is_copied_as_a_sequence_is_clamped():
+    from kantts.models.hifigan.chunked_nc import ChunkedNCVocoder
+
+    with kernel_source_on_cpu():
+        v = ChunkedNCVocoder(_gnc("s4x2"), slots=2, graph=False)
+        mel = torch.zeros(2, 80, 4)
+        v.step(mel, rows=[0, 0], end=[-5, 3])
+        assert v._end.tolist() == [-1, 3]
+        v.step(mel, rows=[0, 0], end=torch.tensor([-5, 3]))
+        assert v._end.tolist() == [-5, 3]
+
+
+def _check_play_many_bits(device, graph):
+    """More utterances than slots, one shorter than a chunk and than ``flush_frames``: play_many equals synthesize bit for
+    bit."""
+    import kantts._hip as hip
+    from kantts.models.hifigan.chunked_nc import ChunkedNCVocoder
+
+    hip.set_precision("fp32")
+    v = ChunkedNCVocoder(_gnc("s4x2", device), slots=2, graph=graph)
+    assert v.flush_frames > 1
+    syn, many = _chunked(v, _mels(device, [1, 5, 9]), 4)
+    for i, (a, b) in enumerate(zip(syn, many)):
+        assert torch.equal(a, b), "play_many utterance %d differs from synthesize" % i
+
+
+def test_chunked_noncausal_play_many_bits_kernel_source():
+    with kernel_source_on_cpu():
+        _check_play_many_bits("cpu", False)
+
+
+@pytest.mark.gpu
+def test_chunked_noncausal_play_many_bits_gpu():
+    _check_play_many_bits("cuda", True)
+
+
 @pytest.mark.gpu
 def test_chunked_noncausal_refusals_gpu():
     from kantts.models.hifigan.chunked_nc import ChunkedNCVocoder

@@ -682,6 +682,32 @@ def test_chunked_nsf_noise_argument_gpu(graph):
     _check_noise_argument("cuda", graph)
 
 
+def _check_short_utterances(device, graph):
+    """More utterances than slots, one shorter than a chunk: play_many equals synthesize(key=i) bit for bit."""
+    from kantts.models.hifigan.chunked_nsf import ChunkedNSFVocoder
+
+    G = _gnsf().to(device)
+    v = ChunkedNSFVocoder(G, slots=2, graph=graph, seed=5)
+    utts = [_feats(n, 40 + i).to(device) for i, n in enumerate((1, 5, 9))]
+    parts = {}
+    for i, wav in v.play_many(utts, chunk_frames=4):
+        parts.setdefault(i, []).append(wav.cpu())
+    for i, x in enumerate(utts):
+        want = torch.cat([c.cpu() for c in v.synthesize(x, chunk_frames=4, slot=i % 2, key=i)], dim=1)
+        assert want.shape == (1, x.shape[1] * v.hop)
+        assert torch.equal(torch.cat(parts[i], dim=1), want), "play_many utterance %d differs from synthesize" % i
+
+
+def test_chunked_nsf_play_many_short_utterances():
+    with kernel_source_on_cpu():
+        _check_short_utterances("cpu", False)
+
+
+@pytest.mark.gpu
+def test_chunked_nsf_play_many_short_utterances_gpu():
+    _check_short_utterances("cuda", True)
+
+
 @pytest.mark.gpu
 def test_chunked_nsf_graph_is_captured_once_gpu():
     """One capture per chunk size serves every count vector, key and reset: cursor, key and phases live on the device."""
