@@ -1682,6 +1682,57 @@ typedef struct {
 } kantts_mb_tail_args;
 int kantts_mb_tail_rows(const kantts_mb_tail_args* args, void* stream);
 
+/* ---- Filled-pause voices (FP: True; csrc/fp.hip) --------------------------------------------------------------------------
+ * B sequences of T token slots, C = encoder_projection_units channels, fp32, C % 4 == 0 (else KANTTS_E_UNSUPPORTED; so are
+ * C > 1024 where noted, B > 65535 and float tensors that are not 16-byte aligned).  NULL required pointers and negative
+ * sizes: KANTTS_E_BADARG.  No entry uses atomics: two calls on equal inputs give equal bits.
+ *
+ * kantts_fp_head: probs (B, T, 4) = softmax(rows (B T, C) . weight (4, C)^T + bias (4)), and the insertion decision:
+ *   fp_label == NULL (inference): for j < lens[b], m_c = (p_c == max_k p_k), c = 1..3; label[b, j] = the smallest c with
+ *     m_c, 0 if none (and 0 for j >= lens[b]); fp_number[b] = sum_j sum_c m_c -- ties count severally, a tie with class 0
+ *     still inserts (reference kantts_sambert.py:787-791, :830-844).
+ *   fp_label != NULL (int32 (B, T)): label = fp_label, fp_number[b] = #(fp_label[b] > 0) over all T slots, padding included.
+ *   C <= 1024.  One launch, a workgroup per sequence.
+ * kantts_fp_head_bwd: d_rows (N, C), d_weight (4, C), d_bias (4) from d_probs (N, 4), N = B T; probs as the forward wrote
+ *   them.  C <= 1024.  One launch; the two parameter gradients are sums over the rows in a fixed order.
+ *
+ * kantts_fp_plan: one workgroup per sequence scans label (B, T) (values outside [0, 3] count as 0) and writes
+ *   inter_len[b] = lens[b] + 3 fp_number[b];   meta[0] = T' = T + max_b inter_len[b] - max_b lens[b];
+ *   src (B, cap) int32, entries q < min(T', cap): >= 0 = that row of text_hid[b]; -(1 + 3 (c - 1) + k) = row k of filler c;
+ *   pos (B, T): the place of token j in the output (>= T' when the output ends before it); nins (B): labels > 0 in the row;
+ *   emo_out / spk_out (B, cap) int64: emo[b, q mod T] / spk[b, q mod T] for q < min(T', cap) (either pair may be NULL) --
+ *   the ids are NOT shifted by the insertions, as in the reference;
+ *   meta[1 + b]: 0, or the sum of 1 (cap < T': the caller must re-plan with a larger cap -- a second launch and a second
+ *   host read of meta; the Python side starts at cap = 4 T, which only tie-inflated counts exceed), 2 (lens[b] outside [0, T] or
+ *   fp_number[b] outside [0, 3 T]; clamped), 4 (a label outside [0, 3]).  meta has 1 + B words.
+ *   Nothing is written at or past column min(T', cap) of src, emo_out, spk_out.  B, T, cap >= 1; T <= 2^24.
+ *   The output of sequence b is the first T' rows of: for p = 0, 1, ...: [3 rows of filler label[b, p] if p < T and it is
+ *   > 0], text_hid[b, p mod T] -- rows past the end wrap to the start of the sequence, as the reference's padding does.
+ *
+ * kantts_fp_insert_fwd: out (B, Tp, C)[b, q] = src[b, q] >= 0 ? text_hid (B, T, C)[b, src] : fill (9, C)[-src - 1]; an entry
+ *   outside [-9, T) gives a zero row.  Tp <= cap, else KANTTS_E_BADARG.
+ * kantts_fp_insert_bwd: d_text_hid (B, T, C)[b, j] = sum of the rows of d_out (B, Tp, C) that hold token j (its place, then
+ *   the wrapped copies in ascending place); d_fill (9, C)[r] = sum over the batch of the rows that hold filler row r, in a
+ *   fixed order.  src, pos, nins as kantts_fp_plan wrote them.  C <= 1024.
+ *
+ * kantts_fp_ce: FpCELoss.  loss[0] = sum_{b, j < lens[b]} weight[y] * (-log softmax(probs[b, j])[y]) / sum_b min(lens[b], T),
+ *   y = label[b, j] -- the probabilities are taken as logits, a second softmax, as the reference does (loss.py:88-105);
+ *   d_probs (B, T, 4) (may be NULL) = d loss / d probs, zero on padding.  One launch, one workgroup.  A label outside [0, 3]
+ *   on a valid token, or no valid token, gives NaN. */
+int kantts_fp_head(const float* rows, const float* weight, const float* bias, const int32_t* lens, const int32_t* fp_label,
+                   float* probs, int32_t* label, int32_t* fp_number, int B, int T, int C, void* stream);
+int kantts_fp_head_bwd(const float* rows, const float* weight, const float* probs, const float* d_probs, float* d_rows,
+                       float* d_weight, float* d_bias, long long N, int C, void* stream);
+int kantts_fp_plan(const int32_t* label, const int32_t* lens, const int32_t* fp_number, const int64_t* emo, const int64_t* spk,
+                   int32_t* inter_len, int32_t* meta, int32_t* src, int32_t* pos, int32_t* nins, int64_t* emo_out,
+                   int64_t* spk_out, int B, int T, int cap, void* stream);
+int kantts_fp_insert_fwd(const float* text_hid, const float* fill, const int32_t* src, float* out, int B, int T, int Tp, int cap,
+                         int C, void* stream);
+int kantts_fp_insert_bwd(const float* d_out, const int32_t* src, const int32_t* pos, const int32_t* nins, float* d_text_hid,
+                         float* d_fill, int B, int T, int Tp, int cap, int C, void* stream);
+int kantts_fp_ce(const float* probs, const int32_t* label, const int32_t* lens, const float* weight, float* loss, float* d_probs,
+                 int B, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

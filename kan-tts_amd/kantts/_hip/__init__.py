@@ -551,9 +551,19 @@ def lib():
         if hasattr(L, "kantts_nsf_draw_states") and hasattr(L, "kantts_nsf_source_wgrad"):  # has_nsf_train(): a library
             L.kantts_nsf_draw_states.argtypes = [p, i, i, p, ll, p]                         # built before them still loads
             L.kantts_nsf_source_wgrad.argtypes = [POINTER(NsfWgradArgs), c_void_p]
+        if all(hasattr(L, s) for s in FP_SYMBOLS):  # has_fp(): a library built before them still loads
+            L.kantts_fp_head.argtypes = [p, p, p, p, p, p, p, p, i, i, i, p]
+            L.kantts_fp_head_bwd.argtypes = [p, p, p, p, p, p, p, ll, i, p]
+            L.kantts_fp_plan.argtypes = [p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, p]
+            L.kantts_fp_insert_fwd.argtypes = [p, p, p, p, i, i, i, i, i, p]
+            L.kantts_fp_insert_bwd.argtypes = [p, p, p, p, p, p, i, i, i, i, i, p]
+            L.kantts_fp_ce.argtypes = [p, p, p, p, p, p, i, i, p]
         _lib = L
     return _lib
 
+
+FP_SYMBOLS = ("kantts_fp_head", "kantts_fp_head_bwd", "kantts_fp_plan", "kantts_fp_insert_fwd", "kantts_fp_insert_bwd",
+              "kantts_fp_ce")  # the filled-pause entry points (csrc/fp.hip)
 
 EXPORTED_SYMBOLS = [
     "kantts_abi_version", "kantts_target_arch", "kantts_gemm_seg_launch", "kantts_gemm_plan", "kantts_layernorm_fwd",
@@ -580,6 +590,7 @@ EXPORTED_SYMBOLS = [
     "kantts_nsf_source_rows", "kantts_nsf_downs_rows", "kantts_mel_handover_rows",
     "kantts_mb_tail_rows", "kantts_sconv_sym_rows_launch", "kantts_lr_memory_fwd", "kantts_lr_memory_bwd",
     "kantts_nsf_source_end_rows", "kantts_nsf_downs_sym_rows", "kantts_nsf_draw_states", "kantts_nsf_source_wgrad",
+    *FP_SYMBOLS,
 ]
 
 
@@ -1699,6 +1710,62 @@ def nsf_source_wgrad(f0, uv, state_in, e, de, dw, dbias, ws, *, S, Tc, hop, H1, 
         return False
     check(rc, "nsf_source_wgrad")
     return True
+
+
+def missing_fp_symbols():
+    """The filled-pause entry points (csrc/fp.hip) the loaded library does NOT export; empty = all there."""
+    L = lib()
+    return [s for s in FP_SYMBOLS if not hasattr(L, s)]
+
+
+def has_fp():
+    """True when the loaded library exports the filled-pause entry points (FP: True models need them)."""
+    return not missing_fp_symbols()
+
+
+FP_ERR_CAP, FP_ERR_LENGTH, FP_ERR_LABEL = 1, 2, 4  # bits of kantts_fp_plan's per-sequence status words
+
+
+def fp_head(rows, weight, bias, lens32, fp_label, probs, label, fp_number, *, B, T, C):
+    """kantts_fp_head: fc + softmax + insertion decision in one launch.  Returns False when the kernel declines the shape."""
+    rc = lib().kantts_fp_head(ptr(rows, torch.float32), ptr(weight, torch.float32), ptr(bias, torch.float32),
+                              ptr(lens32, torch.int32), ptr(fp_label, torch.int32), ptr(probs, torch.float32),
+                              ptr(label, torch.int32), ptr(fp_number, torch.int32), int(B), int(T), int(C), stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "fp_head")
+    return True
+
+
+def fp_head_bwd(rows, weight, probs, d_probs, d_rows, d_weight, d_bias, *, N, C):
+    check(lib().kantts_fp_head_bwd(ptr(rows, torch.float32), ptr(weight, torch.float32), ptr(probs, torch.float32),
+                                   ptr(d_probs, torch.float32), ptr(d_rows, torch.float32), ptr(d_weight, torch.float32),
+                                   ptr(d_bias, torch.float32), int(N), int(C), stream()), "fp_head_bwd")
+
+
+def fp_plan(label, lens32, fp_number, emo, spk, inter_len, meta, src, pos, nins, emo_out, spk_out, *, B, T, cap):
+    """kantts_fp_plan; returns its code (0, or E_UNSUPPORTED / E_BADARG for the caller to judge)."""
+    return lib().kantts_fp_plan(ptr(label, torch.int32), ptr(lens32, torch.int32), ptr(fp_number, torch.int32),
+                                ptr(emo, torch.int64), ptr(spk, torch.int64), ptr(inter_len, torch.int32),
+                                ptr(meta, torch.int32), ptr(src, torch.int32), ptr(pos, torch.int32), ptr(nins, torch.int32),
+                                ptr(emo_out, torch.int64), ptr(spk_out, torch.int64), int(B), int(T), int(cap), stream())
+
+
+def fp_insert_fwd(text_hid, fill, src, out, *, B, T, Tp, cap, C):
+    return lib().kantts_fp_insert_fwd(ptr(text_hid, torch.float32), ptr(fill, torch.float32), ptr(src, torch.int32),
+                                      ptr(out, torch.float32), int(B), int(T), int(Tp), int(cap), int(C), stream())
+
+
+def fp_insert_bwd(d_out, src, pos, nins, d_text, d_fill, *, B, T, Tp, cap, C):
+    return lib().kantts_fp_insert_bwd(ptr(d_out, torch.float32), ptr(src, torch.int32), ptr(pos, torch.int32),
+                                      ptr(nins, torch.int32), ptr(d_text, torch.float32), ptr(d_fill, torch.float32), int(B),
+                                      int(T), int(Tp), int(cap), int(C), stream())
+
+
+def fp_ce(probs, label, lens32, weight, loss, d_probs, *, B, T):
+    return lib().kantts_fp_ce(ptr(probs, torch.float32), ptr(label, torch.int32), ptr(lens32, torch.int32),
+                              ptr(weight, torch.float32), ptr(loss, torch.float32), ptr(d_probs, torch.float32), int(B),
+                              int(T), stream())
 
 
 def mb_tail_entry_points():

@@ -2723,3 +2723,159 @@ class _AlignAttention(torch.autograd.Function):
 def align_attention(q, k, prior, in_lens_i32):
     """q (B, T_mel, C), k (B, T_text, C) -> (attn_soft, attn_logprob), each (B, 1, T_mel, T_text)."""
     return _AlignAttention.apply(q, k, prior, in_lens_i32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Filled-pause voices (FP: True; csrc/fp.hip): predictor head, device-side insertion, FpCELoss
+class _FpHead(torch.autograd.Function):
+    """softmax(x W^T + b) over 4 classes plus the insertion decision, one launch (kantts_fp_head); the labels and counts
+    carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, lens32, fp_label):
+        from . import fp_head as k_head
+
+        x, weight, bias = _c(x), _c(weight), _c(bias)
+        B, T, C = x.shape
+        probs = torch.empty((B, T, 4), device=x.device, dtype=torch.float32)
+        label = torch.empty((B, T), device=x.device, dtype=torch.int32)
+        number = torch.empty((B,), device=x.device, dtype=torch.int32)
+        if not k_head(x, weight, bias, lens32, fp_label, probs, label, number, B=B, T=T, C=C):
+            raise RuntimeError("kantts_fp_head declines C = %d (C %% 4 == 0 and C <= 1024 are required)" % C)
+        ctx.save_for_backward(x, weight, probs)
+        ctx.mark_non_differentiable(label, number)
+        return probs, label, number
+
+    @staticmethod
+    def backward(ctx, d_probs, _dl, _dn):
+        from . import fp_head_bwd as k_bwd
+
+        x, weight, probs = ctx.saved_tensors
+        B, T, C = x.shape
+        d_probs = _c(d_probs)
+        dx, dw = torch.empty_like(x), torch.empty_like(weight)
+        db = torch.empty((4,), device=x.device, dtype=torch.float32)
+        k_bwd(x, weight, probs, d_probs, dx, dw, db, N=B * T, C=C)
+        return dx, dw, db, None, None
+
+
+def fp_head(x, weight, bias, lens32, fp_label=None):
+    """x (B, T, C) -> probs (B, T, 4), label (B, T) int32 (0 = no insertion), fp_number (B) int32.  ``fp_label`` (int32
+    (B, T)): teacher forcing, the labels are taken as given."""
+    return _FpHead.apply(x, weight, bias, lens32, None if fp_label is None else _c(fp_label))
+
+
+class FpPlan:
+    """What kantts_fp_plan wrote for one batch: ``Tp`` (the host integer T'), ``inter_len`` (B) int32, the source map
+    ``src`` (B, cap), its inverse ``pos`` (B, T) / ``nins`` (B), and the extended ids (B, Tp) int64."""
+    __slots__ = ("B", "T", "Tp", "cap", "inter_len", "src", "pos", "nins", "emo", "spk")
+
+
+def fp_plan(label, lens32, fp_number, emo=None, spk=None, cap=None):
+    """Scan the labels into the insertion map (one launch) and read T' back -- the one host synchronisation of the
+    filled-pause path (a second one in the tie-inflated case below); the output width is data-dependent.  ``cap``: columns of the map; the default 4 T holds every
+    outcome without ties (at most one insertion per token), and a tie-inflated T' is planned again at its own width."""
+    from . import FP_ERR_CAP, FP_ERR_LABEL, FP_ERR_LENGTH
+    from . import fp_plan as k_plan
+
+    B, T = label.shape
+    dev = label.device
+    emo = None if emo is None else _c(emo)
+    spk = None if spk is None else _c(spk)
+    retry = cap is None
+    cap = 4 * T if cap is None else int(cap)
+    while True:
+        pl = FpPlan()
+        pl.B, pl.T, pl.cap = B, T, cap
+        pl.inter_len = torch.empty((B,), device=dev, dtype=torch.int32)
+        meta = torch.empty((1 + B,), device=dev, dtype=torch.int32)
+        pl.src = torch.empty((B, cap), device=dev, dtype=torch.int32)
+        pl.pos = torch.empty((B, T), device=dev, dtype=torch.int32)
+        pl.nins = torch.empty((B,), device=dev, dtype=torch.int32)
+        e_out = None if emo is None else torch.empty((B, cap), device=dev, dtype=torch.int64)
+        s_out = None if spk is None else torch.empty((B, cap), device=dev, dtype=torch.int64)
+        check(k_plan(_c(label), lens32, fp_number, emo, spk, pl.inter_len, meta, pl.src, pl.pos, pl.nins, e_out, s_out,
+                     B=B, T=T, cap=cap), "fp_plan")
+        host = meta.tolist()  # the host read
+        pl.Tp, flags = host[0], host[1:]
+        bad = 0
+        for f in flags:
+            bad |= f
+        if bad & FP_ERR_LENGTH:
+            raise ValueError("fp_plan: a sequence length outside [0, %d] or a negative insertion count" % T)
+        if bad & FP_ERR_LABEL:
+            raise ValueError("fp_plan: a filled-pause label outside [0, 3]")
+        if bad & FP_ERR_CAP:
+            if not retry:
+                raise ValueError("fp_plan: the insertion map has %d columns, the output needs %d" % (cap, pl.Tp))
+            cap, retry = pl.Tp, False
+            continue
+        pl.emo = None if e_out is None else e_out[:, :pl.Tp].contiguous()
+        pl.spk = None if s_out is None else s_out[:, :pl.Tp].contiguous()
+        return pl
+
+
+class _FpInsert(torch.autograd.Function):
+    """out[b, q] = text_hid[b, src] or a filler row (kantts_fp_insert_fwd); backward gathers through the same map
+    (kantts_fp_insert_bwd): fixed order, no atomics."""
+
+    @staticmethod
+    def forward(ctx, text_hid, fill, plan):
+        from . import fp_insert_fwd as k_fwd
+
+        text_hid, fill = _c(text_hid), _c(fill)
+        B, T, C = text_hid.shape
+        if (B, T) != (plan.B, plan.T) or fill.numel() != 9 * C:
+            raise ValueError("fp_insert: text_hid %s / fillers %s do not fit the plan (%d, %d)" % (
+                tuple(text_hid.shape), tuple(fill.shape), plan.B, plan.T))
+        out = torch.empty((B, plan.Tp, C), device=text_hid.device, dtype=torch.float32)
+        check(k_fwd(text_hid, fill, plan.src, out, B=B, T=T, Tp=plan.Tp, cap=plan.cap, C=C), "fp_insert_fwd")
+        ctx.plan, ctx.fill_shape = plan, fill.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        from . import fp_insert_bwd as k_bwd
+
+        plan = ctx.plan
+        d_out = _c(d_out)
+        C = d_out.size(-1)
+        d_text = torch.empty((plan.B, plan.T, C), device=d_out.device, dtype=torch.float32)
+        d_fill = torch.empty(ctx.fill_shape, device=d_out.device, dtype=torch.float32)
+        check(k_bwd(d_out, plan.src, plan.pos, plan.nins, d_text, d_fill, B=plan.B, T=plan.T, Tp=plan.Tp, cap=plan.cap, C=C),
+              "fp_insert_bwd")
+        return d_text, d_fill, None
+
+
+def fp_insert(text_hid, fill, plan):
+    """text_hid (B, T, C), fill (3, 3, C) = the three filler sequences -> (B, T', C) through ``plan`` (fp_plan)."""
+    return _FpInsert.apply(text_hid, fill, plan)
+
+
+class _FpCE(torch.autograd.Function):
+    """FpCELoss and its gradient with respect to the probabilities in one launch (kantts_fp_ce)."""
+
+    @staticmethod
+    def forward(ctx, probs, label, lens32, weight):
+        from . import fp_ce as k_ce
+
+        probs = _c(probs)
+        B, T, _ = probs.shape
+        loss = torch.empty((1,), device=probs.device, dtype=torch.float32)
+        d_probs = torch.empty_like(probs)
+        check(k_ce(probs, label, lens32, weight, loss, d_probs, B=B, T=T), "fp_ce")
+        ctx.save_for_backward(d_probs)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (d_probs,) = ctx.saved_tensors
+        return d_probs * g, None, None, None
+
+
+def fp_ce(probs, label, lens32, weight):
+    """probs (B, T, 4), label (B, T) int32, lens32 (B), weight (4) -> scalar: weighted cross entropy of the PROBABILITIES
+    taken as logits, over the tokens j < len_b, divided by their number."""
+    if probs.dim() != 3 or probs.size(2) != 4 or tuple(label.shape) != tuple(probs.shape[:2]):
+        raise ValueError("fp_ce: probs %s, label %s" % (tuple(probs.shape), tuple(label.shape)))
+    return _FpCE.apply(probs, _c(label), lens32, _c(weight))

@@ -47,7 +47,8 @@ def train(model_config, root_dir, stage_dir, resume_path=None, resume_bert_path=
     elif ds is not None:
         from torch.utils.data import DataLoader
 
-        meta = [os.path.join(d, "raw_metafile.txt") for d in root_dir]
+        fp_enable = config["Model"]["KanTtsSAMBERT"]["params"].get("FP", False)  # the metafile with the fillers removed
+        meta = [os.path.join(d, "fprm_metafile.txt" if fp_enable else "raw_metafile.txt") for d in root_dir]
         train_set, valid_set = ds.get_am_datasets(meta, root_dir, config, config["allow_cache"], split_ratio=0.98)
         if distributed:
             from torch.utils.data.distributed import DistributedSampler

@@ -65,10 +65,12 @@ def _pin(d, pin):
     return {k: (v.pin_memory() if torch.is_tensor(v) else v) for k, v in d.items()}
 
 
-def am_collate(batch, r, pad_ids, pin=False, se=False):
+def am_collate(batch, r, pad_ids, pin=False, se=False, fp=False):
     """batch: list of (ling_data, mel, dur, f0, energy, attn_prior, fp_label, se) as AM_Dataset.__getitem__ returns
     (ling_data = [sy, tone, syllable_flag, word_segment, emotion, speaker] integer arrays including the trailing "~");
-    pad_ids: the six per-stream pad ids (ling_unit._sub_unit_pad in stream order)."""
+    pad_ids: the six per-stream pad ids (ling_unit._sub_unit_pad in stream order).  ``fp``: filled-pause batches carry
+    ``fp_label`` (item slot 6, zero-padded to the input width) and pitch / energy as wide as the DURATIONS, which describe
+    the sequence after the insertion (reference dataset.py:773-779, :801-805)."""
     padder = Padder()
     with_duration = not any(item[2] is None for item in batch)
     max_in = max(len(x[0][0]) for x in batch)
@@ -77,6 +79,8 @@ def am_collate(batch, r, pad_ids, pin=False, se=False):
     out = {"input_lings": torch.stack(streams[:4], dim=2), "input_emotions": streams[4], "input_speakers": streams[5]}
     if se:  # speaker-embedding models: one (1, D) vector per utterance, repeated over its symbols (dataset.py:757-762)
         out["input_speakers"] = padder._prepare_targets([x[7].repeat(len(x[0][0]), axis=0) for x in batch], max_in, 0.0)
+    if fp:
+        out["fp_label"] = padder._prepare_scalar_inputs([x[6] for x in batch], max_in, 0).long()
     out["valid_input_lengths"] = torch.as_tensor([len(x[0][0]) - 1 for x in batch], dtype=torch.long)  # minus "~"
     out["valid_output_lengths"] = torch.as_tensor([len(x[1]) for x in batch], dtype=torch.long)
     max_out = padder._round_up(int(out["valid_output_lengths"].max()), r)
@@ -84,7 +88,7 @@ def am_collate(batch, r, pad_ids, pin=False, se=False):
     out["durations"] = padder._prepare_durations([x[2] for x in batch], max_dur, max_out) if with_duration else None
     # duration-free (MAS) batches carry FRAME-level pitch / energy (averaged per phoneme inside the model) and the
     # beta-binomial alignment prior, zero-padded to (max mel, max text) (reference dataset.py:798-827)
-    feat_len = max_in if with_duration else max_out
+    feat_len = (max_dur if fp else max_in) if with_duration else max_out
     out["pitch_contours"] = padder._prepare_scalar_inputs([x[3] for x in batch], feat_len, 0.0).float()
     out["energy_contours"] = padder._prepare_scalar_inputs([x[4] for x in batch], feat_len, 0.0).float()
     out["attn_priors"] = None

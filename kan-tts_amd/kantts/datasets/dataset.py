@@ -152,6 +152,57 @@ def get_voc_datasets(config, root_dir, split_ratio=0.98):
     return Voc_Dataset(train_meta_lst, root_dir, config), Voc_Dataset(valid_meta_lst, root_dir, config)
 
 
+_FP_FILLER_TAG = 3  # index into EMOTION_TYPES of the tag the preprocessing puts on filler tokens (emotion_disgust)
+
+
+def _fp_class(before, last):
+    """Insertion class of a filler run from the syllables of its last two positions: "ga ..." is the "a" filler (1),
+    "ge en_c" the "en" filler (2), anything else the "e" filler (3)."""
+    if before == "ga":
+        return 1
+    return 2 if (before == "ge" and last == "en_c") else 3
+
+
+def get_fp_label(aug_ling_txt):
+    """Insertion label per token of the ``fprm`` line (plus the trailing "~") from the ``fpadd`` line of the same
+    utterance, in which the filler tokens are tagged ``emotion_disgust`` (same results as reference dataset.py:348-388,
+    pinned by the recorded lines of tests/golden/sambert_tiny_fp.pt).  The rule, token by token with k counted from 0 and
+    the "~" slot appended as an untagged token:
+      * tagged tokens are fillers and give no label;
+      * from k = 2 on, the first untagged token behind a tagged one ENDS the run: it gives no label either, and the token
+        after it carries the run's class (``_fp_class`` of the two syllables in front of the ending token) -- also when that
+        token is itself tagged;
+      * every other token from k = 2 on is labelled 0;
+      * the first two tokens are special: unless the line STARTS with a filler both are labelled 0 and token 1 does not
+        count as tagged; if it does start with one, token 1 keeps the label of its own tag (none 0, neutral 1, angry 2,
+        fear 3, anything else no label)."""
+    from kantts.utils.ling_unit import EMOTION_TYPES
+
+    fields = [token.strip("{}").split("$") for token in aug_ling_txt.strip().split(" ")]
+    syl = [f[0] for f in fields] + ["~"]
+    tag = [f[4] for f in fields] + [EMOTION_TYPES[0]]
+    n = len(tag)
+    filler = [t == EMOTION_TYPES[_FP_FILLER_TAG] for t in tag]
+    starts_with_filler = filler[0]
+    if not starts_with_filler and n > 1:
+        filler[1] = False
+    ends_run = [2 <= k <= n - 2 and not filler[k] and filler[k - 1] for k in range(n)]
+    labels = []
+    for k in range(n):
+        if k >= 1 and ends_run[k - 1]:
+            labels.append(_fp_class(syl[k - 3], syl[k - 2]))
+        elif ends_run[k]:
+            continue
+        elif k < 2:
+            if not starts_with_filler:
+                labels.append(0)
+            elif k == 1 and tag[1] in (EMOTION_TYPES[0], EMOTION_TYPES[1], EMOTION_TYPES[2], EMOTION_TYPES[4]):
+                labels.append({EMOTION_TYPES[0]: 0, EMOTION_TYPES[1]: 1, EMOTION_TYPES[2]: 2, EMOTION_TYPES[4]: 3}[tag[1]])
+        elif not filler[k]:
+            labels.append(0)
+    return np.array(labels)
+
+
 class AM_Dataset(torch.utils.data.Dataset):
     """(linguistic ids, mel, durations, pitch, energy, alignment prior, fp label, speaker embedding) per utterance
     (reference dataset.py:391-545).  ``metafile``: path(s) of lines ``<id>\t{sy$tone$flag$ws$emo$spk} ...``; ``root_dir``:
@@ -159,8 +210,10 @@ class AM_Dataset(torch.utils.data.Dataset):
     AudioProcessor writes).  Behaviour kept from the reference: durations are used iff ``duration/`` exists and the model
     is not MAS (then a beta-binomial prior is attached instead); NSF models get frame-level f0 / voiced flag appended to
     the mel as two extra columns, f0 re-normalised to [global_min, global_max] when ``nsf_norm_type: global``; SE models
-    load one speaker embedding per data directory.  Filled-pause (FP) metafiles are not supported (the FP model variant
-    raises in this package).  Caching is a plain per-process dict (the reference shares a multiprocessing.Manager list)."""
+    load one speaker embedding per data directory; filled-pause (FP) models read ``fprm`` metafiles (the fillers removed)
+    and take each utterance's insertion labels from the ``fpadd`` twin next to it (the same path with "fprm" replaced by
+    "fpadd"; an utterance without a twin line is dropped with a warning).  Caching is a plain per-process dict (the
+    reference shares a multiprocessing.Manager list)."""
 
     def __init__(self, config, metafile, root_dir, allow_cache=False, ling_unit=None):
         from kantts.utils.ling_unit import KanTtsLinguisticUnit
@@ -173,9 +226,7 @@ class AM_Dataset(torch.utils.data.Dataset):
         self.nsf_f0_global_maximum = params.get("nsf_f0_global_maximum", 730.0)
         self.se_enable = bool(params.get("SE", False))
         self.mas_enable = bool(params.get("MAS", False))
-        if params.get("FP", False):
-            raise NotImplementedError("filled-pause (FP) metafiles are not supported")
-        self.fp_enable = False
+        self.fp_enable = bool(params.get("FP", False))
         self.r = params["outputs_per_step"]
         self.with_duration = True
         metafile = metafile if isinstance(metafile, list) else [metafile]
@@ -203,6 +254,13 @@ class AM_Dataset(torch.utils.data.Dataset):
         if self.se_enable and not os.path.exists(se_path):
             logging.warning("Missing se meta")
             return []
+        aug = {}
+        if self.fp_enable:  # reference :549-556
+            with open(metafile.replace("fprm", "fpadd"), "r") as f:
+                for line in f:
+                    if line.strip():
+                        index, aug_txt = line.strip().split("\t")
+                        aug[index] = aug_txt
         items = []
         with open(metafile, "r") as f:
             for line in f:
@@ -210,17 +268,20 @@ class AM_Dataset(torch.utils.data.Dataset):
                 if not line:
                     continue
                 index, ling_txt = line.split("\t")
+                if self.fp_enable and index not in aug:
+                    logging.warning("Missing fpadd meta for %s", index)
+                    continue
                 npy = index + ".npy"
                 items.append((ling_txt, os.path.join(sub["mel"], npy),
                               os.path.join(sub["duration"], npy) if self.with_duration else None,
                               os.path.join(sub["f0"], npy), os.path.join(sub["energy"], npy),
-                              os.path.join(sub["frame_f0"], npy), os.path.join(sub["frame_uv"], npy), None, se_path))
+                              os.path.join(sub["frame_f0"], npy), os.path.join(sub["frame_uv"], npy), aug.get(index), se_path))
         return items
 
     def __getitem__(self, idx):
         if self.allow_cache and idx in self.caches:
             return self.caches[idx]
-        ling_txt, mel_file, dur_file, f0_file, energy_file, frame_f0_file, frame_uv_file, _, se_path = self.meta[idx]
+        ling_txt, mel_file, dur_file, f0_file, energy_file, frame_f0_file, frame_uv_file, aug_txt, se_path = self.meta[idx]
         ling_data = self.ling_unit.encode_symbol_sequence(ling_txt)
         mel_data = np.load(mel_file)
         dur_data = np.load(dur_file) if dur_file is not None else None
@@ -236,14 +297,15 @@ class AM_Dataset(torch.utils.data.Dataset):
                 frame_f0 = ((frame_f0 * std + mean) - self.nsf_f0_global_minimum) / (
                     self.nsf_f0_global_maximum - self.nsf_f0_global_minimum)
             mel_data = np.concatenate([mel_data, frame_f0, np.load(frame_uv_file).reshape(-1, 1)], axis=1)
-        item = (ling_data, mel_data, dur_data, f0_data, energy_data, attn_prior, None, se_data)
+        fp_label = get_fp_label(aug_txt) if (self.fp_enable and aug_txt is not None) else None
+        item = (ling_data, mel_data, dur_data, f0_data, energy_data, attn_prior, fp_label, se_data)
         if self.allow_cache:
             self.caches[idx] = item
         return item
 
     def collate_fn(self, batch):
         pad_ids = [self.ling_unit._sub_unit_pad[t] for t in self.ling_unit._lfeat_type_list]
-        return am_collate(batch, self.r, pad_ids, se=self.se_enable)
+        return am_collate(batch, self.r, pad_ids, se=self.se_enable, fp=self.fp_enable)
 
     @staticmethod
     def gen_metafile(raw_meta_file, out_dir, train_meta_file, valid_meta_file, badlist=None, split_ratio=0.98,
@@ -279,11 +341,12 @@ def get_am_datasets(metafile, root_dir, config, allow_cache, split_ratio=0.98, s
     arguments go where their names say)."""
     root_dir = root_dir if isinstance(root_dir, list) else [root_dir]
     metafile = metafile if isinstance(metafile, list) else [metafile]
-    if config["Model"]["KanTtsSAMBERT"]["params"].get("FP", False):
-        raise NotImplementedError("filled-pause (FP) metafiles are not supported")
+    # FP: the lists of the ``fprm`` metafile; AM_Dataset finds their ``am_fpadd_*`` twins by name (reference :847-854)
+    fp = config["Model"]["KanTtsSAMBERT"]["params"].get("FP", False)
+    names = ("am_fprm_train.lst", "am_fprm_valid.lst") if fp else ("am_train.lst", "am_valid.lst")
     train_lst, valid_lst = [], []
     for raw_metafile, data_dir in zip(metafile, root_dir):
-        train_meta, valid_meta = os.path.join(data_dir, "am_train.lst"), os.path.join(data_dir, "am_valid.lst")
+        train_meta, valid_meta = os.path.join(data_dir, names[0]), os.path.join(data_dir, names[1])
         if not os.path.exists(train_meta) or not os.path.exists(valid_meta):
             AM_Dataset.gen_metafile(raw_metafile, data_dir, train_meta, valid_meta, split_ratio=split_ratio,
                                     se_enable=se_enable)

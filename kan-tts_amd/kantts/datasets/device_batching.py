@@ -274,7 +274,12 @@ def make_train_loader(kind, dataset, host_loader, device, batch_size, sampler=No
     "off" = ``host_loader`` as the reference builds it.  ``kind``: "am" (dataset items of AM_Dataset, duration-supervised)
     or "voc" (Voc_Dataset)."""
     device = torch.device(device)
-    if mode == "off" or device.type != "cuda":
+    if mode == "off":
+        return host_loader
+    if kind == "am" and getattr(dataset, "fp_enable", False):
+        raise NotImplementedError("--device_corpus with a filled-pause (FP) model: the device-side batch assembly has no "
+                                  "fp_label stream and pads pitch / energy to the input width; use --device_corpus off")
+    if device.type != "cuda":
         return host_loader
     r = getattr(dataset, "r", None) if kind == "am" else None
     if kind == "am" and getattr(dataset, "mas_enable", False):

@@ -35,6 +35,10 @@ def sambert_model_builder(config, device, rank, distributed, use_arena=None):
     mconf = config["Model"]["KanTtsSAMBERT"]
     net = KanTtsSAMBERT(mconf["params"]).to(device)
     model["KanTtsSAMBERT"] = net
+    if mconf["params"].get("FP", False):  # the filler ids of the filled-pause voice (reference :99-105)
+        from kantts.utils.ling_unit import get_fpdict
+
+        net.fp_dict = {k: torch.from_numpy(v).long().unsqueeze(0).to(device) for k, v in get_fpdict(config).items()}
     opt_type = mconf["optimizer"].get("type", "Adam")
     opt_params = mconf["optimizer"].get("params", {})
     if use_arena is None:

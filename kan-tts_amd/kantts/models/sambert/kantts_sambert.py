@@ -6,8 +6,9 @@ deliberate (documented in DESIGN.md):
   * attention probability tensors (8 + 24 dense (B*H, L, L) maps, ~1 GB at the training shape) are
     only materialised when ``model.return_attns`` is True; the dict keys are always present;
   * padding is described by lengths, never by materialised (B, L, L) masks;
-  * the MAS alignment path (sambert_16k_MAS.yaml) and speaker-embedding input (SE: True) are implemented;
-    FP / byte-input variants raise NotImplementedError.
+  * the MAS alignment path (sambert_16k_MAS.yaml), speaker-embedding input (SE: True) and the filled-pause voice
+    (FP: True, sambert_fp_8k.yaml) are implemented; byte-input variants and FP together with SE raise
+    NotImplementedError.
 """
 import contextlib
 import types
@@ -505,6 +506,45 @@ def average_frame_feat(pitch, durs):
     return torch.where(counts == 0.0, counts, sums / counts)
 
 
+class FP_Predictor(nn.Module):
+    """Filled-pause predictor (reference :677-709): Conv1d(k=3) -> ReLU -> LN -> dropout -> Conv1d(1) -> ReLU -> LN ->
+    dropout -> Linear(4) -> softmax, with NO padding mask (the k = 3 window of the last valid token reads the row behind
+    it).  The two convolutions and LayerNorms are the launches of the encoder's feed-forward; the tail -- fc, softmax and
+    the insertion decision -- is one launch (ops.fp_head, csrc/fp.hip).  Members are parameter holders with the reference's
+    names."""
+
+    def __init__(self, config):
+        super(FP_Predictor, self).__init__()
+        d_proj, d_hid = config["encoder_projection_units"], config["embedding_dim"] // 2
+        self.w_1 = nn.Conv1d(d_proj, d_hid, kernel_size=3, padding=1)
+        self.w_2 = nn.Conv1d(d_hid, d_proj, kernel_size=1, padding=0)
+        self.layer_norm1 = nn.LayerNorm(d_hid, eps=1e-6)
+        self.layer_norm2 = nn.LayerNorm(d_proj, eps=1e-6)
+        self.dropout_inner = nn.Dropout(0.1)
+        self.dropout = nn.Dropout(0.1)
+        self.fc = nn.Linear(d_proj, 4)
+
+    def hidden(self, x):
+        """Everything in front of ``fc``."""
+        p_in = float(self.dropout_inner.p) if self.training else 0.0
+        p_out = float(self.dropout.p) if self.training else 0.0
+        x = ops.linear(x, self.w_1.weight, self.w_1.bias, relu=True, pad=1, mode="conv")
+        x = ops.layer_norm(x, self.layer_norm1.weight, self.layer_norm1.bias, self.layer_norm1.eps)
+        x = ops.dropout2_add(x, p1=p_in)  # counter-based mask, regenerated in backward
+        x = ops.linear(x, self.w_2.weight, self.w_2.bias, relu=True)
+        x = ops.layer_norm(x, self.layer_norm2.weight, self.layer_norm2.bias, self.layer_norm2.eps)
+        return ops.dropout2_add(x, p1=p_out)
+
+    def decide(self, x, lens32, fp_label=None):
+        """(probabilities (B, T, 4), label (B, T) int32, fp_number (B) int32): see ops.fp_head."""
+        return ops.fp_head(self.hidden(x).float(), self.fc.weight, self.fc.bias, lens32, fp_label)
+
+    def forward(self, x):
+        B, T = x.shape[:2]
+        lens32 = torch.full((B,), T, device=x.device, dtype=torch.int32)
+        return self.decide(x, lens32)[0]
+
+
 class KanTtsSAMBERT(nn.Module):
     """SAM-BERT acoustic model (reference :712-1044)."""
 
@@ -530,7 +570,17 @@ class KanTtsSAMBERT(nn.Module):
                                                  n_att_channels=config["num_mels"])
         self.fp_enable = config.get("FP", False)
         if self.fp_enable:
-            raise NotImplementedError("filled-pause predictor is outside the hot path")
+            if self.se_enable:  # the reference's insert_fp repeats 2-D id tensors: a 3-D speaker input fails there too
+                raise NotImplementedError("FP together with SE (per-token speaker embeddings) is not a shipped configuration: "
+                                          "insert_fp extends integer speaker ids")
+            missing = hip_rt.missing_fp_symbols() if hip_rt.available() else []
+            if missing:
+                raise RuntimeError("this libkantts_hip.so was built before the filled-pause kernels; missing: %s "
+                                   "(rebuild kan-tts_amd/csrc)" % ", ".join(missing))
+            self.FP_predictor = FP_Predictor(config)
+            # {1, 2, 3: (1, 3, 4) int64}: the linguistic ids of the "en" / "a" / "e" fillers; attached by
+            # sambert_model_builder from kantts.utils.ling_unit.get_fpdict, as the reference does
+            self.fp_dict = None
         # the reference always returns 8 + 24 dense attention maps; here opt-in
         self.return_attns = False
         # True: the band width stays in device memory (no host sync) so that a whole training step can be
@@ -601,6 +651,26 @@ class KanTtsSAMBERT(nn.Module):
             plan["bw_dev"] = o["bw_dev"]
         return in_info, plan
 
+    def fp_fillers(self):
+        """F (3, 3, C): the text encoder's output for the three filler sequences, no mask, as ONE (3, 3) batch (a sequence's
+        rows depend on that sequence alone).  Gradient flows into the encoder through them.  Formed on every forward, also
+        in eval() where it is a constant of the weights: nothing here can tell that the weights have not moved (the arena
+        optimizer updates them in place from a kernel), and a stale F would be silent -- DESIGN section 5 has the cost."""
+        if not self.fp_dict:
+            raise RuntimeError("FP model without fp_dict: attach {1, 2, 3: (1, 3, 4) ids} (sambert_model_builder does, "
+                               "from kantts.utils.ling_unit.get_fpdict)")
+        dev = self.text_encoder.ling_proj.weight.device
+        ids = torch.cat([self.fp_dict[c].reshape(1, 3, -1)[:, :, :4] for c in (1, 2, 3)], dim=0).to(dev)
+        return self.text_encoder(ids, None, False)[0]
+
+    def insert_fp(self, text_hid, label, fp_number, inputs_emotion, inputs_speaker, lens32, fillers=None):
+        """The reference's insert_fp (:766-860) as two launches and one host read: the labels are scanned into a source map
+        (ops.fp_plan reads T' back), the rows are gathered through it.  Returns (text_hid', inputs_emotion', inputs_speaker',
+        inter_lengths int32)."""
+        plan = ops.fp_plan(label, lens32, fp_number, inputs_emotion, inputs_speaker)
+        out = ops.fp_insert(text_hid, self.fp_fillers() if fillers is None else fillers, plan)
+        return out, plan.emo, plan.spk, plan.inter_len
+
     def _embed_emo_spk(self, inputs_emotion, inputs_speaker):
         (emo_hid, _) = ops.embed_sum(inputs_emotion, [self.emo_tokenizer.weight])
         if self.se_enable:
@@ -634,10 +704,11 @@ class KanTtsSAMBERT(nn.Module):
                           "lfr_info", "out_info", "enc_sla_attn_lst", "LR_length_rounded", "log_duration_predictions",
                           "pitch_predictions", "energy_predictions", "duration_targets", "pitch_targets", "energy_targets",
                           "inter_lengths", "LR_text_outputs", "LR_emo_outputs", "LR_spk_outputs", "ling_embedding",
-                          "attn_soft", "attn_hard", "attn_logprob")
+                          "attn_soft", "attn_hard", "attn_logprob", "fp_predictions", "fp_decisions")
 
     def _token_side(self, inputs_ling, inputs_emotion, inputs_speaker, input_lengths, output_lengths=None,
-                    mel_targets=None, duration_targets=None, pitch_targets=None, energy_targets=None, attn_priors=None):
+                    mel_targets=None, duration_targets=None, pitch_targets=None, energy_targets=None, attn_priors=None,
+                    fp_label=None):
         """Everything of ``forward`` in front of the mel decoder: text encoder, variance adaptor (duration loop), length
         regulator, the decoder's memory, masks and band widths.  It fixes the utterance's frame count before the first
         decoder step; ``forward`` and the streaming session of chunked.py (ChunkedAcoustic.open) both start here."""
@@ -646,7 +717,9 @@ class KanTtsSAMBERT(nn.Module):
         T_in = inputs_ling.size(1)
         is_training = mel_targets is not None
         tplan = base_plan = in_info = None
-        teacher = (is_training and not self.MAS and not getattr(self, "inline_teacher_plan", False)
+        # FP: the targets are as wide as the sequences AFTER the insertion (T', known once the plan is read back), so the
+        # target-only plan cannot be formed beside the encoder from T_in: FP models take the inline (unfused) plan
+        teacher = (is_training and not self.MAS and not getattr(self, "inline_teacher_plan", False) and not self.fp_enable
                    and output_lengths is not None and duration_targets is not None and pitch_targets is not None
                    and energy_targets is not None)
         if (teacher and _PLAN_KERNEL and duration_targets.dtype == torch.int64 and mel_targets.dtype == torch.float32
@@ -674,6 +747,22 @@ class KanTtsSAMBERT(nn.Module):
             # the side stream, beside the encoder's own backward (no-op unless weight gradients are deferred)
             text_hid = ops.wgrad_flush_point(text_hid)
             inter_lengths = input_lengths
+            fp_predictions = fp_decisions = None
+            if self.fp_enable:
+                # predictor -> decision -> plan (the one host read: T') -> gather; everything downstream sees the extended
+                # sequences, lengths and ids (reference :885-899).  Inference: fp32 whatever the precision mode (this block
+                # sits inside ``front``) -- the decisions are index tensors
+                if inputs_speaker.dim() != 2:
+                    raise ValueError("FP models take integer speaker ids (B, T)")
+                label32 = None if fp_label is None else fp_label.to(torch.int32)
+                fp_predictions, label, fp_number = self.FP_predictor.decide(text_hid, in_info.lens32, label32)
+                # (the emotion / speaker ids are not shifted but repeated with period T, the padded width, as in the
+                # reference: an utterance gets the frames of its batch-1 run when that run sees the same padded row)
+                text_hid, inputs_emotion, inputs_speaker, inter32 = self.insert_fp(
+                    text_hid, label, fp_number, inputs_emotion, inputs_speaker, in_info.lens32)
+                inter_lengths = inter32.to(input_lengths.dtype)
+                fp_decisions = (label, fp_number)
+                in_info = SeqInfo(inter_lengths, text_hid.size(1))
             attn_soft = attn_hard = attn_logprob = None
             if self.MAS and is_training:
                 # Monotonic-Alignment-Search (reference :901-925): soft attention mel <-> (scaled) linguistic embedding,
@@ -738,8 +827,12 @@ class KanTtsSAMBERT(nn.Module):
     def forward(self, inputs_ling, inputs_emotion, inputs_speaker, input_lengths, output_lengths=None,
                 mel_targets=None, duration_targets=None, pitch_targets=None, energy_targets=None, attn_priors=None,
                 fp_label=None):
+        """FP models, batched inference: every utterance gets the frames of ITS ROW inferred at batch 1, at the same padded
+        width T -- not those of the utterance trimmed to its own length, because two reference quirks that are kept depend
+        on T: FP_Predictor's unmasked k = 3 window reads the row behind the last token, and the emotion / speaker ids of
+        the inserted positions repeat with period T.  (Without FP a batch equals its utterances at any width.)"""
         ts = self._token_side(inputs_ling, inputs_emotion, inputs_speaker, input_lengths, output_lengths, mel_targets,
-                              duration_targets, pitch_targets, energy_targets, attn_priors)
+                              duration_targets, pitch_targets, energy_targets, attn_priors, fp_label)
         batch_size, tplan, memory, bw_int, bw_dev = ts.batch_size, ts.tplan, ts.memory, ts.bw_int, ts.bw_dev
         lfr_info, out_info = ts.lfr_info, ts.out_info
         from kantts._hip import ops_bf16
@@ -788,7 +881,7 @@ class KanTtsSAMBERT(nn.Module):
             "duration_targets": ts.duration_targets,
             "pitch_targets": ts.pitch_targets,
             "energy_targets": ts.energy_targets,
-            "fp_predictions": None,
+            "fp_predictions": ts.fp_predictions,
             "valid_inter_lengths": ts.inter_lengths,
         }
         if ts.bw_dev is not None and ts.bw_dev.numel() == ts.batch_size and mel_targets is None:

@@ -59,7 +59,8 @@ class _Slot:
 class AcousticSlots:
     """``slots`` independently advancing streaming sessions of one ``KanTtsSAMBERT`` over buffers of ``max_steps`` decoder
     steps each: needs eval(), bf16 mode and the decoder shapes ``DecoderKernel.eligible`` accepts (the rules of
-    ChunkedAcoustic); raises otherwise."""
+    ChunkedAcoustic); raises otherwise.  The buffers are sized in decoder steps: for a filled-pause (FP) model the
+    inserted filler rows lengthen an utterance, and one that no longer fits is refused at ``admit`` like any other."""
 
     def __init__(self, fsnet, slots, max_steps):
         if fsnet.training:
@@ -164,7 +165,9 @@ class AcousticSlots:
         memory = ts.memory.contiguous().float()
         steps = int(memory.size(1))
         if steps > self.L:
-            raise ValueError("the utterance has %d decoder steps, the pool's buffers hold max_steps = %d" % (steps, self.L))
+            fp = (" (%d token rows after the filled-pause insertion)" % int(ts.inter_lengths.reshape(-1)[0])
+                  if getattr(fsnet, "fp_enable", False) else "")
+            raise ValueError("the utterance has %d decoder steps%s, the pool's buffers hold max_steps = %d" % (steps, fp, self.L))
         hkv = ops.linear(memory, dk.hkv_w, dk.hkv_b).float().contiguous()
         if self.memory is None:
             self.memory = torch.zeros((self.S, self.L, memory.size(2)), device=self.dev, dtype=torch.float32)

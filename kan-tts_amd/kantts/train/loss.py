@@ -62,6 +62,30 @@ class ProsodyReconLoss(torch.nn.Module):
         return dur_loss, pitch_loss, energy_loss
 
 
+class FpCELoss(torch.nn.Module):
+    """Filled-pause criterion (reference :88-105): CrossEntropyLoss(weight, reduction="none") applied to the predictor's
+    PROBABILITIES as if they were logits (a second softmax -- kept), masked to the tokens j < len with
+    ``max_len = fp_label.size(1)``, summed and divided by the unweighted number of valid tokens.  One launch gives the
+    scalar and its gradient (ops.fp_ce, csrc/fp.hip).  The reference's constructor calls ``.cuda()`` on the weight; here
+    it is a buffer that follows the module (``.to(device)``) and, failing that, the input."""
+
+    def __init__(self, loss_type="ce", weight=[1, 4, 4, 8]):
+        super(FpCELoss, self).__init__()
+        if loss_type != "ce":
+            raise ValueError("Unknown loss type: {}".format(loss_type))
+        if len(weight) != 4:
+            raise ValueError("FpCELoss takes one weight per class (4), got {}".format(len(weight)))
+        self.loss_type = loss_type
+        self.register_buffer("weight", torch.tensor([float(w) for w in weight], dtype=torch.float32), persistent=False)
+
+    def forward(self, input_lengths, fp_pd, fp_label):
+        dev = fp_pd.device
+        if fp_pd.size(1) != fp_label.size(1):
+            raise ValueError("fp_pd has {} token slots, fp_label {}".format(fp_pd.size(1), fp_label.size(1)))
+        return ops.fp_ce(fp_pd.float(), fp_label.to(device=dev, dtype=torch.int32),
+                         input_lengths.to(device=dev, dtype=torch.int32), self.weight.to(dev))
+
+
 def sambert_loss_sum(mel_criterion, prosody_criterion, batch, res, prosody_lengths=None):
     """The training objective of a SAM-BERT step as the reference's trainer forms it (kantts/train/trainer.py:940-975:
     mel_loss_ + mel_loss + dur_loss + pitch_loss + energy_loss) -> (total, {name: detached component}).
@@ -332,6 +356,7 @@ loss_dict = {
     "AttentionBinarizationLoss": AttentionBinarizationLoss,
     "AttentionCTCLoss": AttentionCTCLoss,
     "MelReconLoss": MelReconLoss,
+    "FpCELoss": FpCELoss,
     "ProsodyReconLoss": ProsodyReconLoss,
     "generator_adv_loss": GeneratorAdversarialLoss,
     "discriminator_adv_loss": DiscriminatorAdversarialLoss,

@@ -192,8 +192,12 @@ class Sambert_Trainer(Trainer):
         super().__init__(*args, **kwargs)
         params = self.config["Model"][self.KEY]["params"]
         self.with_MAS, self.fp_enable = params.get("MAS", False), params.get("FP", False)
-        if self.fp_enable:
-            raise NotImplementedError("filled-pause training is outside the hot path (DESIGN.md section 7)")
+        if self.fp_enable and graph:
+            raise NotImplementedError("graph=True with FP: the width T' of the sequences after the filled-pause insertion is "
+                                      "read back from the device for every batch, so the step cannot be captured; "
+                                      "train FP voices with the eager step")
+        if self.fp_enable and "FpCELoss" not in self.criterion:
+            raise ValueError("FP: True needs Loss.FpCELoss enabled in the configuration")
         # graph=True serves the MAS step too since round 6 (the CTC criterion is a device-side launch: csrc/ctc.hip)
         self.graph = graph
         self._graphs = {}
@@ -207,6 +211,8 @@ class Sambert_Trainer(Trainer):
                      input_lengths="valid_input_lengths", output_lengths="valid_output_lengths",
                      mel_targets="mel_targets", duration_targets="durations", pitch_targets="pitch_contours",
                      energy_targets="energy_contours", attn_priors="attn_priors")
+        if self.fp_enable:  # reference :820-822
+            names["fp_label"] = "fp_label"
         return {k: (batch[v].to(self.device, non_blocking=True) if batch.get(v) is not None else None)
                 for k, v in names.items()}
 
@@ -221,6 +227,10 @@ class Sambert_Trainer(Trainer):
             kl = self.criterion["AttentionBinarizationLoss"](self.epoch, res["attn_hard"], res["attn_soft"])
             total = total + ctc + kl
             losses.update(attn_ctc_loss=ctc, attn_kl_loss=kl)
+        if self.fp_enable:  # reference :865-869 / :964-968
+            fp_loss = self.criterion["FpCELoss"](b["input_lengths"], res["fp_predictions"], b["fp_label"])
+            total = total + fp_loss
+            losses["fp_loss"] = fp_loss
         losses["TotalLoss"] = total
         return total, losses
 

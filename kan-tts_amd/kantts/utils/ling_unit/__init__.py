@@ -4,4 +4,4 @@ package; the language RESOURCE files (PhoneSet.xml, tonelist.txt of a language) 
 directory the user points to (see ling_unit.language_directory).  The text front-end (ttsfrd: text -> symbols) is NOT
 part of this package."""
 from kantts.utils.ling_unit.ling_unit import (EMOTION_TYPES, SYLLABLE_FLAGS, WORD_SEGMENTS, KanTtsLinguisticUnit,  # noqa: F401
-                                              language_directory, load_language_symbols)
+                                              get_fpdict, language_directory, load_language_symbols)

@@ -69,6 +69,22 @@ def load_language_symbols(language="PinYin", language_dir=None):
     return phones, tones
 
 
+def get_fpdict(config, language_dir=None):
+    """{1: "en", 2: "a", 3: "e"} -> (3, 4) int arrays: the sy / tone / syllable_flag / word_segment ids of the three-token
+    filler sequences a filled-pause voice inserts (reference :24-41).  The emotion is neutral and the speaker the first of
+    ``speaker_list``; neither reaches the ids (columns 0..3 are kept)."""
+    default_sp = config["linguistic_unit"]["speaker_list"].split(",")[0]
+    unit = KanTtsLinguisticUnit(config, language_dir=language_dir)
+
+    def ids(filler):
+        seq = " ".join("{%s$emotion_neutral$%s}" % (g, default_sp) for g in (
+            "%s$tone5$s_begin$word_begin" % filler[0], "%s$tone5$s_end$word_end" % filler[1],
+            "#3$tone_none$s_none$word_none"))
+        return np.stack(unit.encode_symbol_sequence(seq), axis=1)[:3, :4]
+
+    return {1: ids(("ge", "en_c")), 2: ids(("ga", "a_c")), 3: ids(("ge", "e_c"))}
+
+
 class _Stream:
     """One id table: position of a symbol in ``symbols + [pad, eos, mask]``."""
 
@@ -101,6 +117,8 @@ class KanTtsLinguisticUnit:
         self._pad, self._eos, self._mask = PAD, EOS, MASK
         self._lfeat_type_list = [t.strip() for t in unit["lfeat_type_list"].strip().split(",")]
         self.fp_enable = bool(config.get("Model", {}).get("KanTtsSAMBERT", {}).get("params", {}).get("FP", False))
+        if self.fp_enable:  # the two fields an ``fpadd`` metafile line is read for (reference :80-82): sy and emo_category
+            self._fpadd_lfeat_type_list = [self._lfeat_type_list[0], self._lfeat_type_list[4]]
         self._streams = {}
         if self.using_byte():
             self._streams["byte_index"] = _Stream(["@%d" % i for i in range(256)])
