@@ -325,6 +325,23 @@ int kantts_fsmn_dwconv_bwd(const float* dy, const float* x, const float* w, cons
                            int left_pad, void* stream);
 /* floats of caller-owned workspace the backward needs (weight-gradient partials; 0 when none) */
 long long kantts_fsmn_dwconv_bwd_ws(int B, int T, int C, int K);
+/* The memory block of a training step with the two dropouts stacked on it and the residual add, one launch each way
+ * (K == 41; c, res, y, dy, dx, dym (B,T,C) fp32 contiguous, w (C,K), lens int64[B] or NULL):
+ *   fwd: y = keep2 * (keep1 * m) (+ res),  m = kantts_fsmn_dwconv_fwd(c, w, res = NULL, lens)
+ *   bwd: dym[b,t] = keep2 * (keep1 * dy) for t < lens[b], 0 for the other rows;  dx = kantts_fsmn_dwconv_bwd's dx of dym
+ * with keep_i the masks of kantts_dropout2_add(p1, seed1, p2, seed2, seed_dev) over the flat element index
+ * ((b*T + t)*C + c) (p_i == 0: no mask; seed_dev may be NULL).  Every product and the residual add round as in the two
+ * calls they replace, so y, dx and dym (rows t < lens[b]) are bit-identical to that pair; dym is what the filter gradient
+ * (kantts_fsmn_dwconv_bwd with dx = NULL) takes as dy.  c / dy rows at or after lens[b] are not used (they may hold
+ * anything); res is read and y, dx, dym are written at every row t < T.  res may be NULL.
+ * KANTTS_E_BADARG: a NULL tensor, left_pad outside [0, K), p outside [0, 1).  KANTTS_E_UNSUPPORTED (the caller runs the
+ * pair): K != 41, C % 4 != 0, a tensor that is not 16-byte aligned, more than 2^31 - 1 tiles. */
+int kantts_fsmn_memory_drop_fwd(const float* c, const float* w, const float* res, const int64_t* lens, float* y, int B,
+                                int T, int C, int K, int left_pad, float p1, uint64_t seed1, float p2, uint64_t seed2,
+                                const uint64_t* seed_dev, void* stream);
+int kantts_fsmn_memory_drop_bwd(const float* dy, const float* w, const int64_t* lens, float* dx, float* dym, int B, int T,
+                                int C, int K, int left_pad, float p1, uint64_t seed1, float p2, uint64_t seed2,
+                                const uint64_t* seed_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Masked L1 ("mae") reduction: loss_accum[0] += sum_{t<lens[b]} |target-pred| / (sum(lens)*C);

@@ -460,6 +460,9 @@ def lib():
         L.kantts_fsmn_dwconv_bwd.argtypes = [p, p, p, p, p, p, p, ll, i, i, i, i, i, p]
         L.kantts_fsmn_dwconv_bwd_ws.argtypes = [i, i, i, i]
         L.kantts_fsmn_dwconv_bwd_ws.restype = ll
+        if hasattr(L, "kantts_fsmn_memory_drop_fwd") and hasattr(L, "kantts_fsmn_memory_drop_bwd"):  # a library built
+            L.kantts_fsmn_memory_drop_fwd.argtypes = [p, p, p, p, p, i, i, i, i, i, f, u64, f, u64, p, p]  # before them
+            L.kantts_fsmn_memory_drop_bwd.argtypes = [p, p, p, p, p, i, i, i, i, i, f, u64, f, u64, p, p]  # still loads
         L.kantts_masked_l1.argtypes = [p, p, p, p, p, i, i, i, p]
         L.kantts_sumsq.argtypes = [p, p, ll, p]
         L.kantts_elem_loss.argtypes = [p, p, f, i, f, p, p, ll, p]
@@ -591,6 +594,7 @@ EXPORTED_SYMBOLS = [
     "kantts_mb_tail_rows", "kantts_sconv_sym_rows_launch", "kantts_lr_memory_fwd", "kantts_lr_memory_bwd",
     "kantts_nsf_source_end_rows", "kantts_nsf_downs_sym_rows", "kantts_nsf_draw_states", "kantts_nsf_source_wgrad",
     *FP_SYMBOLS,
+    "kantts_fsmn_memory_drop_fwd", "kantts_fsmn_memory_drop_bwd",
 ]
 
 

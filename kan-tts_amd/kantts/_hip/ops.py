@@ -1338,6 +1338,90 @@ def fsmn_memory(x, w, lens_i64, left_pad, res=None):
     return _FsmnMemory.apply(x, w, res, lens_i64, left_pad)
 
 
+class _FsmnMemoryDrop(torch.autograd.Function):
+    """The memory block of a training step, its own dropout, the encoder's dropout on its output and the residual add:
+    one launch forward, one backward (csrc/fsmn_drop.hip: kantts_fsmn_memory_drop_fwd / _bwd) where _FsmnMemory and
+    _Dropout2Add took two each.  Same seeds in the same order and the same roundings as that pair, so a step computes the
+    same bits.  A launch that declines (KANTTS_E_UNSUPPORTED) is replaced by the pair's two launches with the seeds
+    already drawn.  ``res_grad``: as for _Dropout2Add."""
+
+    @staticmethod
+    def forward(ctx, c, w, res, lens, lp, p1, p2, res_grad=None):
+        from . import rng_ptr
+
+        c, w = _c(c), _c(w)
+        B, T, C = c.shape
+        K = w.shape[-1]
+        r = None if res is None else _c(res)
+        y = torch.empty_like(c)
+        s1 = next_seed() if p1 > 0 else 0  # the draw order of _Dropout2Add at this point of the chain
+        s2 = next_seed() if p2 > 0 else 0
+        rc = lib().kantts_fsmn_memory_drop_fwd(ptr(c, torch.float32), ptr(w, torch.float32), ptr(r, torch.float32),
+                                               ptr(lens), ptr(y), B, T, C, K, int(lp), float(p1), s1, float(p2), s2,
+                                               rng_ptr(c.device), stream())
+        if rc == E_UNSUPPORTED:
+            m = torch.empty_like(c)
+            check(lib().kantts_fsmn_dwconv_fwd(ptr(c), ptr(w), None, ptr(lens), ptr(m), B, T, C, K, int(lp), stream()),
+                  "fsmn_dwconv_fwd")
+            rc = lib().kantts_dropout2_add(ptr(m), ptr(r, torch.float32), ptr(y), m.numel(), float(p1), s1, float(p2), s2,
+                                           rng_ptr(c.device), stream())
+        check(rc, "fsmn_memory_drop_fwd")
+        ctx.save_for_backward(c, w, lens)
+        ctx.cfg = (B, T, C, K, int(lp), float(p1), s1, float(p2), s2, res is not None)
+        ctx.res_grad = res_grad if (res is not None and res_grad is not None and res_grad.armed) else None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import rng_ptr
+
+        c, w, lens = ctx.saved_tensors
+        B, T, C, K, lp, p1, s1, p2, s2, has_res = ctx.cfg
+        dy = _c(dy)
+        dx, dym = torch.empty_like(c), torch.empty_like(c)
+        rc = lib().kantts_fsmn_memory_drop_bwd(ptr(dy, torch.float32), ptr(w), ptr(lens), ptr(dx), ptr(dym), B, T, C, K, lp,
+                                               p1, s1, p2, s2, rng_ptr(dy.device), stream())
+        if rc == E_UNSUPPORTED:
+            check(lib().kantts_dropout2_add(ptr(dy), None, ptr(dym), dy.numel(), p1, s1, p2, s2, rng_ptr(dy.device),
+                                            stream()), "dropout2_add")
+            rc = lib().kantts_fsmn_dwconv_bwd(ptr(dym), ptr(c), ptr(w), ptr(lens), ptr(dx), None, None, 0, B, T, C, K, lp,
+                                              stream())
+        check(rc, "fsmn_memory_drop_bwd")
+        # the filter gradient reads the masked dy the launch wrote beside dx: a leaf, on the weight-gradient stream when the
+        # step overlaps them (dw must NOT be in the keep-alive list: see _FsmnMemory.backward)
+        dw = gzeros_like(w)
+        ws_n = int(lib().kantts_fsmn_dwconv_bwd_ws(B, T, C, K))
+        ws = torch.empty(max(ws_n, 1), device=dy.device, dtype=torch.float32)
+        with wgrad_overlap.side(dym, c, ws):
+            check(lib().kantts_fsmn_dwconv_bwd(ptr(dym), ptr(c), ptr(w), ptr(lens), None, ptr(dw), ptr(ws), ws_n, B, T, C,
+                                               K, lp, stream()), "fsmn_dwconv_bwd (dw)")
+        # the residual's gradient is the UNMASKED dy
+        d_res = dy if has_res and ctx.needs_input_grad[2] else None
+        if d_res is not None and ctx.res_grad is not None:
+            ctx.res_grad.dres, d_res = d_res, None
+        return dx, dw, d_res, None, None, None, None, None
+
+
+FSMN_MEMORY_DROP = {"on": not os.environ.get("KANTTS_NO_FSMN_MEMORY_DROP")}  # A/B switch: off = the pair of launches
+
+
+def fsmn_memory_drop_entry_points():
+    """True when the loaded library exports the one-launch memory block (the numpy model of the C ABI does not)."""
+    L = lib()
+    return hasattr(L, "kantts_fsmn_memory_drop_fwd") and hasattr(L, "kantts_fsmn_memory_drop_bwd")
+
+
+def fsmn_memory_drop(x, w, lens_i64, left_pad, p1=0.0, p2=0.0, res=None, res_grad=None):
+    """dropout_{p2}(dropout_{p1}(fsmn_memory(x))) (+ res), p1 or p2 > 0.  One launch each way for the 41-tap fp32 block of
+    every shipped model; otherwise -- another filter length, another dtype, a library without the entry points, the switch
+    off -- the memory block followed by dropout2_add."""
+    if (FSMN_MEMORY_DROP["on"] and x.dtype == torch.float32 and w.dtype == torch.float32 and w.shape[-1] == 41
+            and x.dim() == 3 and x.shape[-1] % 4 == 0 and (res is None or (res.shape == x.shape and res.dtype == x.dtype))
+            and fsmn_memory_drop_entry_points()):
+        return _FsmnMemoryDrop.apply(x, w, res, lens_i64, left_pad, float(p1), float(p2), res_grad)
+    return dropout2_add(fsmn_memory(x, w, lens_i64, left_pad), p1, p2, res, res_grad=res_grad)
+
+
 # ================================================================================================
 # Masked L1
 # ================================================================================================

@@ -47,14 +47,13 @@ class MemoryBlockV2(nn.Module):
         self.dropout = nn.Dropout(dropout)
 
     def forward(self, input, mask=None, res=None, outer_p=0.0, res_grad=None):
-        """``outer_p``: the encoder's own dropout on this block's output (reference :118), applied in the same pass as
-        the block's dropout and the residual add (kantts_dropout2_add)."""
+        """``outer_p``: the encoder's own dropout on this block's output (reference :118), applied in the same launch as
+        the FIR, the block's dropout and the residual add (kantts_fsmn_memory_drop_fwd)."""
         info = SeqInfo.of(mask)
         lens = None if info is None else info.lens64
         p = float(self.dropout.p) if self.training else 0.0
         if p > 0.0 or outer_p > 0.0:
-            out = ops.fsmn_memory(input, self.conv_dw.weight, lens, self.lp)
-            return ops.dropout2_add(out, p, outer_p, res, res_grad=res_grad)
+            return ops.fsmn_memory_drop(input, self.conv_dw.weight, lens, self.lp, p, outer_p, res, res_grad=res_grad)
         return ops.fsmn_memory(input, self.conv_dw.weight, lens, self.lp, res=res)
 
 
