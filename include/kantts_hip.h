@@ -1750,6 +1750,63 @@ int kantts_fp_insert_bwd(const float* d_out, const int32_t* src, const int32_t* 
 int kantts_fp_ce(const float* probs, const int32_t* label, const int32_t* lens, const float* weight, float* loss, float* d_probs,
                  int B, int T, void* stream);
 
+/* ---- Speaker-embedding extractor for SE voices (csrc/spk_embed.hip) --------------------------------------------------------
+ * Kaldi fbank and the inference graph of the D-TDNN (CAM++ style) extractor, for a RAGGED batch: every entry takes the
+ * per-item lengths and no item reads a neighbour's or its own padding.  Everything is fp32 on the VALU; BatchNorm arrives
+ * folded into (scale, shift) tables, y = x * scale + shift.  No entry uses atomics: two calls on equal inputs give equal
+ * bits, and an item's result does not depend on what else is in the batch.  NULL required pointers and sizes < 1:
+ * KANTTS_E_BADARG; shapes outside the stated limits: KANTTS_E_UNSUPPORTED.  B <= 65535 everywhere.
+ *
+ * kantts_kaldi_fbank: wav (B, ld) fp32, nsamp (B) samples per item (clamped to ld) -> out (B, Tmax, nmel) log-mel, item b
+ *   has T_b = nsamp < 400 ? 0 : 1 + (nsamp - 400) / 160 frames (clamped to Tmax); rows T_b .. Tmax - 1 are written as zeros.
+ *   Per frame (400 samples, hop 160, snip_edges): subtract the frame mean, pre-emphasis 0.97 (the first sample against
+ *   itself), times window (400), zero-padded 512-point FFT with tw (512: cos(2 pi k / 512), k < 256, then sin), power
+ *   spectrum, mel bin m = sum_j mel_w[m, j] * power[mel_lo[m] + j], j < mel_n[m] (mel_w (nmel, wmax); mel_lo + mel_n <= 257),
+ *   log(max(., FLT_EPSILON)).  cmn != 0: a second launch subtracts from every bin its mean over the item's own T_b frames.
+ *   nmel <= 128.  The tables are the host's (kantts.preprocess.se_processor.kaldi_tables()).
+ *
+ * kantts_spk_conv2d: 3 x 3 convolution over (F, T) with stride (sf, 1) and padding 1, folded BN, optional residual, ReLU:
+ *   out (B, Cout, Fout, T)[b, co, fo, t] = relu((sum_{ci, r, k} w (Cout, Cin, 3, 3) * in[b, ci, fo sf - 1 + r, t - 1 + k])
+ *   * scale[co] + shift[co] + R), Fout = (Fin - 1) / sf + 1; `in` is read through the element strides (in_sb, in_sc, in_sf,
+ *   in_st); a tap outside [0, Fin) x [0, lens[b]) is zero and out is written as zero for t >= lens[b].  R: res == NULL: 0;
+ *   res (B, Cres, Fres, T) with sc_w == NULL: res[b, co, fo, t] (Cres == Cout, Fres == Fout); with sc_w (Cout, Cres): the
+ *   1 x 1 shortcut (sum_ci sc_w[co, ci] * res[b, ci, fo rsf, t]) * sc_scale[co] + sc_shift[co].
+ *   Cin <= 32, Cout % 8 == 0, Cout <= 32.
+ *
+ * kantts_spk_conv1d: y (B, CY, TY)[b, co_off + co, t] = post(sum_{ci < Cin, k < K} w (Cout, Cin, K)[co, ci, k] *
+ *   pre(x (B, CX, TX)[b, ci, t stride + (k - K / 2) dil])) for t < len_out(b) = (lens[b] - 1) / stride + 1; columns at or
+ *   past len_out(b) are not written.  pre (pre_scale != NULL) = relu(x * pre_scale[ci] + pre_shift[ci]); a tap outside
+ *   [0, lens[b]) is zero AFTER pre.  post (post_scale != NULL) = relu(. * post_scale[co] + post_shift[co]).  K odd.
+ *   psum != NULL (needs stride 1): per workgroup tile i of 64 columns, psum (B, NT, Cout)[b, i, co] = the sum of y over the
+ *   tile's valid columns and pmax (B, NT, 2, Cout)[b, i, s, co] = the maximum over those of them in 100-column segment
+ *   (64 i) / 100 + s (-FLT_MAX when there is none); NT = (max_out + 63) / 64, tiles at or past len_out(b) are not written.
+ *   max_out: the widest len_out of the batch (sizes the launch).  Any Cin, Cout (tails are handled).
+ *
+ * kantts_spk_cam_gate_conv: the context-aware mask of one dense layer and its dilated convolution, from the h, psum, pmax
+ *   of kantts_spk_conv1d: for item b and segment s, gate (G) = sigmoid(wb (G, Ch) . relu(wa (Ch, Cb) . (mean_b + segmax_b,s)
+ *   + ba) + bb), mean_b = sum of the item's psum tiles (ascending) / lens[b]; y (B, CY, TY)[b, co_off + o, t] =
+ *   gate[t / 100][o] * sum_{c, k < 3} w (G, Cb, 3)[o, c, k] * h (B, Cb, TH)[b, c, t + (k - 1) dil] for t < lens[b], taps
+ *   outside [0, lens[b]) zero; nothing else of y is written.  Cb <= 128, Ch <= 64, G in {8, 16, 32, 64}, 1 <= dil <= 4.
+ *
+ * kantts_spk_tail: out (B, E)[b] = (w (E, 2 C) . [mean_t v, std_t v]) * oscale + oshift with v = relu(x (B, CX, TX)[b, c, t] *
+ *   scale[c] + shift[c]) over t < lens[b]; std is the UNBIASED one (two passes; lens[b] == 1 gives NaN).  C <= 1024. */
+int kantts_kaldi_fbank(const float* wav, const int32_t* nsamp, const float* window, const float* tw, const int32_t* mel_lo,
+                       const int32_t* mel_n, const float* mel_w, float* out, int B, int ld, int Tmax, int nmel, int wmax,
+                       int cmn, void* stream);
+int kantts_spk_conv2d(const float* in, long long in_sb, long long in_sc, long long in_sf, long long in_st, const float* w,
+                      const float* scale, const float* shift, const float* res, const float* sc_w, const float* sc_scale,
+                      const float* sc_shift, const int32_t* lens, float* out, int B, int Cin, int Cout, int Fin, int T, int sf,
+                      int Cres, int Fres, int rsf, void* stream);
+int kantts_spk_conv1d(const float* x, const int32_t* lens, const float* w, const float* pre_scale, const float* pre_shift,
+                      const float* post_scale, const float* post_shift, float* y, float* psum, float* pmax, int B, int Cin,
+                      int CX, int TX, int Cout, int CY, int TY, int co_off, int K, int stride, int dil, int max_out,
+                      void* stream);
+int kantts_spk_cam_gate_conv(const float* h, const int32_t* lens, const float* psum, const float* pmax, const float* wa,
+                             const float* ba, const float* wb, const float* bb, const float* w, float* y, int B, int Cb,
+                             int TH, int Ch, int G, int CY, int TY, int co_off, int dil, int NT, int max_len, void* stream);
+int kantts_spk_tail(const float* x, const int32_t* lens, const float* scale, const float* shift, const float* w,
+                    const float* oscale, const float* oshift, float* out, int B, int C, int CX, int TX, int E, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

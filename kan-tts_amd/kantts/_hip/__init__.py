@@ -561,12 +561,21 @@ def lib():
             L.kantts_fp_insert_fwd.argtypes = [p, p, p, p, i, i, i, i, i, p]
             L.kantts_fp_insert_bwd.argtypes = [p, p, p, p, p, p, i, i, i, i, i, p]
             L.kantts_fp_ce.argtypes = [p, p, p, p, p, p, i, i, p]
+        if all(hasattr(L, s) for s in SPK_SYMBOLS):  # has_spk_embed(): a library built before them still loads
+            L.kantts_kaldi_fbank.argtypes = [p, p, p, p, p, p, p, p, i, i, i, i, i, i, p]
+            L.kantts_spk_conv2d.argtypes = [p, ll, ll, ll, ll, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, p]
+            L.kantts_spk_conv1d.argtypes = [p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, i, i, i, p]
+            L.kantts_spk_cam_gate_conv.argtypes = [p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, i, i, p]
+            L.kantts_spk_tail.argtypes = [p, p, p, p, p, p, p, p, i, i, i, i, i, p]
         _lib = L
     return _lib
 
 
 FP_SYMBOLS = ("kantts_fp_head", "kantts_fp_head_bwd", "kantts_fp_plan", "kantts_fp_insert_fwd", "kantts_fp_insert_bwd",
               "kantts_fp_ce")  # the filled-pause entry points (csrc/fp.hip)
+
+SPK_SYMBOLS = ("kantts_kaldi_fbank", "kantts_spk_conv2d", "kantts_spk_conv1d", "kantts_spk_cam_gate_conv",
+               "kantts_spk_tail")  # the speaker-embedding extractor (csrc/spk_embed.hip)
 
 EXPORTED_SYMBOLS = [
     "kantts_abi_version", "kantts_target_arch", "kantts_gemm_seg_launch", "kantts_gemm_plan", "kantts_layernorm_fwd",
@@ -594,6 +603,7 @@ EXPORTED_SYMBOLS = [
     "kantts_mb_tail_rows", "kantts_sconv_sym_rows_launch", "kantts_lr_memory_fwd", "kantts_lr_memory_bwd",
     "kantts_nsf_source_end_rows", "kantts_nsf_downs_sym_rows", "kantts_nsf_draw_states", "kantts_nsf_source_wgrad",
     *FP_SYMBOLS,
+    *SPK_SYMBOLS,
     "kantts_fsmn_memory_drop_fwd", "kantts_fsmn_memory_drop_bwd",
 ]
 
@@ -1770,6 +1780,64 @@ def fp_ce(probs, label, lens32, weight, loss, d_probs, *, B, T):
     return lib().kantts_fp_ce(ptr(probs, torch.float32), ptr(label, torch.int32), ptr(lens32, torch.int32),
                               ptr(weight, torch.float32), ptr(loss, torch.float32), ptr(d_probs, torch.float32), int(B),
                               int(T), stream())
+
+
+def missing_spk_symbols():
+    """The speaker-embedding entry points (csrc/spk_embed.hip) the loaded library does NOT export; empty = all there."""
+    L = lib()
+    return [s for s in SPK_SYMBOLS if not hasattr(L, s)]
+
+
+def has_spk_embed():
+    """True when the loaded library exports the speaker-embedding extractor (se_processor's kernel path needs it)."""
+    return not missing_spk_symbols()
+
+
+def kaldi_fbank(wav, nsamp, window, tw, mel_lo, mel_n, mel_w, out, *, B, ld, Tmax, nmel, wmax, cmn):
+    """kantts_kaldi_fbank: ragged (B, ld) waveforms -> (B, Tmax, nmel) log-mel, optionally mean-normalised per item."""
+    check(lib().kantts_kaldi_fbank(ptr(wav, torch.float32), ptr(nsamp, torch.int32), ptr(window, torch.float32),
+                                   ptr(tw, torch.float32), ptr(mel_lo, torch.int32), ptr(mel_n, torch.int32),
+                                   ptr(mel_w, torch.float32), ptr(out, torch.float32), int(B), int(ld), int(Tmax), int(nmel),
+                                   int(wmax), int(bool(cmn)), stream()), "kaldi_fbank")
+
+
+def spk_conv2d(x, strides, w, scale, shift, res, sc_w, sc_scale, sc_shift, lens, out, *, B, Cin, Cout, Fin, T, sf, Cres=0,
+               Fres=0, rsf=1):
+    """kantts_spk_conv2d; ``strides``: the element strides (batch, channel, F, T) of ``x``."""
+    sb, sc, sF, st = (int(v) for v in strides)
+    check(lib().kantts_spk_conv2d(ptr(x, torch.float32), sb, sc, sF, st, ptr(w, torch.float32), ptr(scale, torch.float32),
+                                  ptr(shift, torch.float32), ptr(res, torch.float32), ptr(sc_w, torch.float32),
+                                  ptr(sc_scale, torch.float32), ptr(sc_shift, torch.float32), ptr(lens, torch.int32),
+                                  ptr(out, torch.float32), int(B), int(Cin), int(Cout), int(Fin), int(T), int(sf), int(Cres),
+                                  int(Fres), int(rsf), stream()), "spk_conv2d")
+
+
+def spk_conv1d(x, lens, w, pre_scale, pre_shift, post_scale, post_shift, y, psum, pmax, *, B, Cin, CX, TX, Cout, CY, TY, co_off,
+               K, stride, dil, max_out):
+    check(lib().kantts_spk_conv1d(ptr(x, torch.float32), ptr(lens, torch.int32), ptr(w, torch.float32),
+                                  ptr(pre_scale, torch.float32), ptr(pre_shift, torch.float32), ptr(post_scale, torch.float32),
+                                  ptr(post_shift, torch.float32), ptr(y, torch.float32), ptr(psum, torch.float32),
+                                  ptr(pmax, torch.float32), int(B), int(Cin), int(CX), int(TX), int(Cout), int(CY), int(TY),
+                                  int(co_off), int(K), int(stride), int(dil), int(max_out), stream()), "spk_conv1d")
+
+
+def spk_cam_gate_conv(h, lens, psum, pmax, wa, ba, wb, bb, w, y, *, B, Cb, TH, Ch, G, CY, TY, co_off, dil, NT, max_len):
+    """kantts_spk_cam_gate_conv; returns its code (0 or E_UNSUPPORTED for the caller to word; anything else raises)."""
+    rc = lib().kantts_spk_cam_gate_conv(ptr(h, torch.float32), ptr(lens, torch.int32), ptr(psum, torch.float32),
+                                        ptr(pmax, torch.float32), ptr(wa, torch.float32), ptr(ba, torch.float32),
+                                        ptr(wb, torch.float32), ptr(bb, torch.float32), ptr(w, torch.float32),
+                                        ptr(y, torch.float32), int(B), int(Cb), int(TH), int(Ch), int(G), int(CY), int(TY),
+                                        int(co_off), int(dil), int(NT), int(max_len), stream())
+    if rc != E_UNSUPPORTED:
+        check(rc, "spk_cam_gate_conv")
+    return rc
+
+
+def spk_tail(x, lens, scale, shift, w, oscale, oshift, out, *, B, C, CX, TX, E):
+    check(lib().kantts_spk_tail(ptr(x, torch.float32), ptr(lens, torch.int32), ptr(scale, torch.float32),
+                                ptr(shift, torch.float32), ptr(w, torch.float32), ptr(oscale, torch.float32),
+                                ptr(oshift, torch.float32), ptr(out, torch.float32), int(B), int(C), int(CX), int(TX), int(E),
+                                stream()), "spk_tail")
 
 
 def mb_tail_entry_points():

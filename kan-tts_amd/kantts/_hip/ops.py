@@ -2963,3 +2963,125 @@ def fp_ce(probs, label, lens32, weight):
     if probs.dim() != 3 or probs.size(2) != 4 or tuple(label.shape) != tuple(probs.shape[:2]):
         raise ValueError("fp_ce: probs %s, label %s" % (tuple(probs.shape), tuple(label.shape)))
     return _FpCE.apply(probs, _c(label), lens32, _c(weight))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Speaker-embedding extractor for SE voices (csrc/spk_embed.hip): Kaldi fbank and the launches of the D-TDNN inference
+# graph over a ragged batch.  Inference only (no autograd); every op takes the items' own lengths (int32, on the device).
+def _spk_need():
+    from . import missing_spk_symbols
+
+    missing = missing_spk_symbols()
+    if missing:
+        raise RuntimeError("the loaded library lacks the speaker-embedding entry points (%s); there is no stock fallback"
+                           % ", ".join(missing))
+
+
+def kaldi_fbank(wav, nsamp, tables, Tmax, cmn=True):
+    """wav (B, ld) fp32, nsamp (B) int32 -> (B, Tmax, n_mels) log-mel; rows at or past an item's frame count are zero.
+    ``tables``: se_processor.fbank.kaldi_tables(device).  ``cmn``: subtract the mean over the item's own frames."""
+    from . import kaldi_fbank as k_fbank
+
+    _spk_need()
+    wav = _c(wav)
+    B, ld = wav.shape
+    nmel, wmax = tables["mel_w"].shape
+    out = torch.empty((B, int(Tmax), nmel), device=wav.device, dtype=torch.float32)
+    k_fbank(wav, nsamp, tables["window"], tables["tw"], tables["mel_lo"], tables["mel_n"], tables["mel_w"], out, B=B, ld=ld,
+            Tmax=int(Tmax), nmel=nmel, wmax=wmax, cmn=cmn)
+    return out
+
+
+def spk_conv2d(x, w, scale, shift, lens, sf=1, res=None, shortcut=None, rsf=1, feats_layout=False):
+    """3 x 3 convolution over (F, T), stride (sf, 1), folded BN (scale, shift), residual, ReLU -- one launch.
+    x (B, Cin, Fin, T), or (B, T, Fin) with ``feats_layout`` (Cin = 1: the fbank output as it is stored).  ``res``: the
+    tensor the residual is formed from; ``shortcut`` = (weight (Cout, Cres), scale, shift) for the 1 x 1 shortcut with
+    F-stride ``rsf``, None for the identity."""
+    from . import spk_conv2d as k_conv
+
+    _spk_need()
+    x = _c(x)
+    if feats_layout:
+        B, T, Fin = x.shape
+        Cin, strides = 1, (T * Fin, 0, 1, Fin)
+    else:
+        B, Cin, Fin, T = x.shape
+        strides = (Cin * Fin * T, Fin * T, T, 1)
+    Cout = w.shape[0]
+    out = torch.empty((B, Cout, (Fin - 1) // sf + 1, T), device=x.device, dtype=torch.float32)
+    sc_w = sc_s = sc_b = None
+    Cres = Fres = 0
+    if res is not None:
+        res = _c(res)
+        Cres, Fres = res.shape[1], res.shape[2]
+        if shortcut is not None:
+            sc_w, sc_s, sc_b = shortcut
+    k_conv(x, strides, w, scale, shift, res, sc_w, sc_s, sc_b, lens, out, B=B, Cin=Cin, Cout=Cout, Fin=Fin, T=T, sf=sf,
+           Cres=Cres, Fres=Fres, rsf=rsf)
+    return out
+
+
+def spk_conv1d(x, lens, w, y, max_out, Cin=None, co_off=0, pre=None, post=None, stride=1, dil=1, stats=None):
+    """y (B, CY, TY)[:, co_off : co_off + Cout] = post(conv1d(pre(x (B, CX, TX)[:, :Cin]))) with w (Cout, Cin, K), per item
+    over its own frames (``lens``: INPUT frames).  pre / post: (scale, shift) of a folded BatchNorm followed by ReLU.
+    ``stats`` = (psum, pmax): the CAM epilogue.  Writes into ``y`` and returns it."""
+    from . import spk_conv1d as k_conv
+
+    _spk_need()
+    B, CX, TX = x.shape
+    Cout, Cin_w, K = w.shape
+    Cin = Cin_w if Cin is None else Cin
+    if Cin != Cin_w or not x.is_contiguous() or not y.is_contiguous() or not w.is_contiguous():
+        raise ValueError("spk_conv1d: weight %s against %d input channels, or a tensor that is not contiguous"
+                         % (tuple(w.shape), Cin))
+    pre = pre or (None, None)
+    post = post or (None, None)
+    stats = stats or (None, None)
+    k_conv(x, lens, w, pre[0], pre[1], post[0], post[1], y, stats[0], stats[1], B=B, Cin=Cin, CX=CX, TX=TX, Cout=Cout,
+           CY=y.shape[1], TY=y.shape[2], co_off=co_off, K=K, stride=stride, dil=dil, max_out=max_out)
+    return y
+
+
+def spk_cam_work(B, Cb, T, device):
+    """The scratch of spk_cam_layer for items of up to T frames: h (B, Cb, T) and the per-tile partials."""
+    NT = (T + 63) // 64
+    return (torch.empty((B, Cb, T), device=device, dtype=torch.float32),
+            torch.empty((B, NT, Cb), device=device, dtype=torch.float32),
+            torch.empty((B, NT, 2, Cb), device=device, dtype=torch.float32))
+
+
+def spk_cam_layer(buf, lens, C_i, p, dil, max_len, work=None):
+    """One dense layer of a D-TDNN block, in place: reads channels [0, C_i) of ``buf`` (B, C_end, T) and writes channels
+    [C_i, C_i + growth) -- two launches, no concatenation.  ``p``: the layer's tables (bn1, w1, bn2, wa, ba, wb, bb,
+    w_stem).  ``max_len``: the longest item (host integer).  Returns ``buf``."""
+    from . import E_UNSUPPORTED
+    from . import spk_cam_gate_conv as k_cam
+
+    _spk_need()
+    B, CY, T = buf.shape
+    Cb = p["w1"].shape[0]
+    G, Ch = p["wb"].shape
+    h, psum, pmax = work if work is not None else spk_cam_work(B, Cb, T, buf.device)
+    NT = (max_len + 63) // 64
+    if psum.shape[1] != NT:  # the scratch was sized for a longer batch: the kernels index the partials by NT
+        psum, pmax = psum.view(-1)[:B * NT * Cb].view(B, NT, Cb), pmax.view(-1)[:B * NT * 2 * Cb].view(B, NT, 2, Cb)
+    spk_conv1d(buf, lens, p["w1"], h, max_len, Cin=C_i, pre=p["bn1"], post=p["bn2"], stats=(psum, pmax))
+    rc = k_cam(h, lens, psum, pmax, p["wa"], p["ba"], p["wb"], p["bb"], p["w_stem"], buf, B=B, Cb=Cb, TH=h.shape[2], Ch=Ch,
+               G=G, CY=CY, TY=T, co_off=C_i, dil=dil, NT=NT, max_len=max_len)
+    if rc == E_UNSUPPORTED:
+        raise RuntimeError("kantts_spk_cam_gate_conv declines bn_channels = %d, growth_rate = %d, dilation = %d "
+                           "(bn_channels <= 128, growth_rate in {8, 16, 32, 64}, dilation <= 4)" % (Cb, G, dil))
+    return buf
+
+
+def spk_tail(x, lens, bn, w, obn):
+    """x (B, C, T) -> (B, E): folded bn + ReLU, mean and unbiased std over each item's frames, dense (E, 2 C), folded
+    affine-free BatchNorm ``obn`` -- one launch."""
+    from . import spk_tail as k_tail
+
+    _spk_need()
+    B, CX, TX = x.shape
+    E, C2 = w.shape
+    out = torch.empty((B, E), device=x.device, dtype=torch.float32)
+    k_tail(x, lens, bn[0], bn[1], w, obn[0], obn[1], out, B=B, C=C2 // 2, CX=CX, TX=TX, E=E)
+    return out
