@@ -792,8 +792,12 @@ int kantts_relu_gate_bf16(const void* dy, int dy_bf16, const void* y, int y_bf16
  * FRAGMENT-MAJOR layout of kantts_fragmajor_bf16 -- the backward pass hands in the transposed weights (w1 := W2^T as
  * (F, 128), w2 := W1^T as (128, F)).  t_out (optional): bf16 (M, F) row-major, the intermediate the weight gradients need.
  * Taps do not cross sequence boundaries: rows are B sequences of T tokens.  Dropout indices: m*F + f (drop1), m*128 + n
- * (drop2); seeds are offset by *seed_dev (graph replay).  F = 1024.  KT2 = 3 (backward form only, M % T == 0): phase 2
- * sums three taps of the intermediate, w2 = three (128, F) images -- the input gradient of a k = 3 first convolution.  Returns KANTTS_E_UNSUPPORTED for other shapes: the
+ * (drop2); seeds are offset by *seed_dev (graph replay).  KT2 = 3 (backward form only, M % T == 0): phase 2
+ * sums three taps of the intermediate, w2 = three (128, F) images -- the input gradient of a k = 3 first convolution.
+ * Geometries (K1, N, F): (128, 128, 1024) -- everything above (the widths written as 128 are K1 / N in general); and the FSMN
+ * feed-forward nets (256, 256, 512) and (128, 128, 256) with KT = 1, KT2 <= 1 only, without ln_*, xdrop, xrowmask, rowmask1 /
+ * rowmask2: forward form (bias1, relu, drop1; t_out may be NULL: the intermediate is then not written) and backward form
+ * (gate, alpha1, t_out = dz, res = fp32 addend at row pitch ldr).  Returns KANTTS_E_UNSUPPORTED for anything else: the
  * caller falls back to two kantts_bgemm_nt launches. */
 typedef struct kantts_ffn_args {
   const void* x;

@@ -37,13 +37,27 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 #define FP_THREADS 512
-#define FP_BM 32
-#define FP_K1 128
-#define FP_N 128
-#define FP_F 1024
-#define FP_XP (FP_K1 + 16)   // X tile pitch in elements: 288 B = 32 mod 64 (conflict-free 16-byte fragment reads)
-#define FP_XROWS 40          // 32 tokens + halo of up to 4 rows either side
-#define FP_TP (FP_F + 16)    // T tile pitch in elements
+// Geometry is a template parameter of the kernel (ffn_pair_body.inc): input width K1, output width N, hidden width F, token
+// tile height BM, most taps of phase 1 MAXKT.  What is instantiated is what the model runs:
+//   (128, 128, 1024), BM 32, taps up to 9   the transformer blocks' feed-forward (all of the above)
+//   (256, 256,  512), BM FP_BM_WIDE, k = 1  FSMN postnet layers (M = 19 584 in the benchmarked step)
+//   (128, 128,  256), BM 32, k = 1          FSMN pitch / energy predictor layers (M = 2048: 64 workgroups)
+// At 32 tokens a 256 -> 512 -> 256 workgroup would stream 512 KB of weight fragments from L2 for 32 rows of work (612
+// workgroups, 313 MB): a fragment has to be reused over more tokens, so the wide shape takes a taller tile -- each wave
+// holds BM / 16 B-operand blocks per A fragment.  At N = 256 the eight waves cover the output rows (8 x 32) and each owns
+// its whole reduction: the cross-wave exchange of the halves drops out.  FP_BM_WIDE was chosen on the device: the launch alone
+// at M = 19 584 with rotating buffers (profiles/fsmn_ffn_pair_tile_sweep.txt), us forward / backward:
+//   BM 64   306 workgroups (a mostly empty second round), 104 KB LDS   32.8 / 38.2
+//   BM 80   245 workgroups (one round of 256 CUs),        130 KB LDS   24.4 / 29.0   <- kept
+//   BM 96   204 workgroups,                               156 KB LDS   26.0 / 30.8
+// against 48 / 62-73 us for the two bgemm_nt launches it replaces (DESIGN.md sections 4 and 5).
+#ifndef FP_BM_WIDE
+#define FP_BM_WIDE 80
+#endif
+// units of weight fragments in flight ahead of the one being consumed at a tile taller than 32 tokens (ffn_pair_body.inc)
+#ifndef FP_DEPTH_TALL
+#define FP_DEPTH_TALL 2
+#endif
 
 __device__ __forceinline__ unsigned fp_pack2(float a, float b) {
   bf16x4 t = {(__bf16)a, (__bf16)b, (__bf16)0.f, (__bf16)0.f};
@@ -55,17 +69,29 @@ __device__ __forceinline__ float fp_hi(unsigned u) { return __uint_as_float(u & 
 // KT2 = taps of PHASE 2 (the backward pass of a k = 3 first convolution: dh[m] = sum_tap dz[m + pad - tap] . W1[tap]):
 // the tile then covers 32 rows of the intermediate of which the inner 32 - (KT2 - 1) are output rows -- the halo rows are
 // recomputed by the neighbouring workgroup (6 % more phase-1 work instead of a second launch that re-reads dz).
-template <bool BWD, int KT2>
+template <bool BWD, int KT2, int K1, int N, int F, int BM, int MAXKT>
 __global__ __launch_bounds__(FP_THREADS) void ffn_pair_kernel(const kantts_ffn_args g) {
 #include "ffn_pair_body.inc"
 }
 static bool fp_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// the k = 1 geometries (FSMN feed-forward nets): forward form or backward form, nothing else
+template <int K1, int N, int F, int BM>
+static void fp_launch_k1(const kantts_ffn_args& g, hipStream_t st) {
+  if (g.gate)
+    hipLaunchKernelGGL((ffn_pair_kernel<true, 1, K1, N, F, BM, 1>), dim3(kantts_cdiv(g.M, BM)), dim3(FP_THREADS), 0, st, g);
+  else
+    hipLaunchKernelGGL((ffn_pair_kernel<false, 1, K1, N, F, BM, 1>), dim3(kantts_cdiv(g.M, BM)), dim3(FP_THREADS), 0, st, g);
+}
+
 extern "C" int kantts_ffn_pair(const kantts_ffn_args* gp, void* stream) {
   if (!gp) return KANTTS_E_BADARG;
   const kantts_ffn_args& g = *gp;
   if (!g.x || !g.w1 || !g.w2 || !g.y || g.M < 0 || g.KT < 1) return KANTTS_E_BADARG;
-  if (g.K1 != FP_K1 || g.N != FP_N || g.F != FP_F) return KANTTS_E_UNSUPPORTED;
+  const bool blk = g.K1 == 128 && g.N == 128 && g.F == 1024;   // transformer block
+  const bool wide = g.K1 == 256 && g.N == 256 && g.F == 512;   // FSMN postnet
+  const bool slim = g.K1 == 128 && g.N == 128 && g.F == 256;   // FSMN predictors
+  if (!blk && !wide && !slim) return KANTTS_E_UNSUPPORTED;
   if (g.KT > 9 || g.pad < 0 || g.pad >= g.KT || (g.KT > 1 && g.T <= 0)) return KANTTS_E_UNSUPPORTED;
   if ((g.ldx & 7) || (g.ldy & 3) || (g.res && (g.ldr & 3))) return KANTTS_E_UNSUPPORTED;
   if (!fp_aligned16(g.x) || !fp_aligned16(g.w1) || !fp_aligned16(g.w2) || !fp_aligned16(g.y) ||
@@ -82,14 +108,25 @@ extern "C" int kantts_ffn_pair(const kantts_ffn_args* gp, void* stream) {
     if (g.gate || kt2 != 1 || !fp_aligned16(g.ln_out) || !fp_aligned16(g.ln_gamma) || !fp_aligned16(g.ln_beta))
       return KANTTS_E_UNSUPPORTED;
   }
+  // the FSMN shapes carry only the ports an FSMN feed-forward net uses: k = 1 either way, no LayerNorm epilogue, no
+  // regenerated input dropout, no row masks
+  if (!blk && (g.KT != 1 || kt2 != 1 || g.ln_out || g.xdrop_p > 0.f || g.xrowmask || g.rowmask1 || g.rowmask2))
+    return KANTTS_E_UNSUPPORTED;
   if (g.M == 0) return KANTTS_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (kt2 == 3)
-    hipLaunchKernelGGL((ffn_pair_kernel<true, 3>), dim3(kantts_cdiv(g.M, FP_BM - 2)), dim3(FP_THREADS), 0, st, g);
+  if (wide)
+    fp_launch_k1<256, 256, 512, FP_BM_WIDE>(g, st);
+  else if (slim)
+    fp_launch_k1<128, 128, 256, 32>(g, st);
+  else if (kt2 == 3)
+    hipLaunchKernelGGL((ffn_pair_kernel<true, 3, 128, 128, 1024, 32, 9>), dim3(kantts_cdiv(g.M, 32 - 2)), dim3(FP_THREADS), 0,
+                       st, g);
   else if (g.gate)
-    hipLaunchKernelGGL((ffn_pair_kernel<true, 1>), dim3(kantts_cdiv(g.M, FP_BM)), dim3(FP_THREADS), 0, st, g);
+    hipLaunchKernelGGL((ffn_pair_kernel<true, 1, 128, 128, 1024, 32, 9>), dim3(kantts_cdiv(g.M, 32)), dim3(FP_THREADS), 0, st,
+                       g);
   else
-    hipLaunchKernelGGL((ffn_pair_kernel<false, 1>), dim3(kantts_cdiv(g.M, FP_BM)), dim3(FP_THREADS), 0, st, g);
+    hipLaunchKernelGGL((ffn_pair_kernel<false, 1, 128, 128, 1024, 32, 9>), dim3(kantts_cdiv(g.M, 32)), dim3(FP_THREADS), 0, st,
+                       g);
   KANTTS_CHECK_LAUNCH();
 }
 

@@ -899,8 +899,9 @@ def ffn_pair(x, w1, w2, y, *, M, T, F, KT=1, pad=0, bias1=None, bias2=None, relu
     """Both contractions of a feed-forward block in one launch (csrc/ffn_pair.hip; kantts_ffn_pair in the header).
     x (M, 128) bf16 / fp32; w1 / w2: FRAGMENT-MAJOR bf16 images (ops_bf16.frag_major) of the (KT*F, 128) and (128, F)
     weight matrices; y (M, 128) fp32 / bf16; t_out bf16 (M, F).  KT2 = 3 (backward form): phase 2 sums three taps of the
-    intermediate, y[m] = sum_t t[m + s2_first + t*s2_step] . w2[t]^T with w2 = three (128, F) images.  Returns False when
-    the library declines the shape."""
+    intermediate, y[m] = sum_t t[m + s2_first + t*s2_step] . w2[t]^T with w2 = three (128, F) images.  The FSMN
+    feed-forward shapes (x (M, 256), F = 512, y (M, 256); x (M, 128), F = 256, y (M, 128)) are taken with KT = KT2 = 1 and
+    without ln / xdrop / row masks; t_out may be None in the forward form.  Returns False when the library declines."""
     g = FfnArgs()
     g.x, g.ldx, g.x_f32 = ptr(x), int(x.shape[-1]), int(x.dtype == torch.float32)
     NY = int(y.shape[-1])

@@ -608,6 +608,17 @@ def linear(xs, weights, bias=None, *, mode=None, bias2=None, res=None, rowmask=N
     return ops_bf16._attach_token(_FusedLinear.apply(opts, bias, bias2, res, rowmask, *xs, *weights), token)
 
 
+def fsmn_ffn(x, w1, b1, w2, drop_p=0.0, res_grad=None):
+    """The feed-forward net of an FSMN layer (kantts/models/sambert/fsmn.py): Conv1d(1) + ReLU + dropout, Conv1d(1) without
+    bias.  bf16 mode: one autograd node, one launch each way where csrc/ffn_pair.hip has the shape (ops_bf16.fsmn_ffn);
+    fp32 mode, and anything the node does not take: two fused linears."""
+    if get_precision() == "bf16" and ops_bf16.fsmn_ffn_eligible(x, w1, b1, w2):
+        return ops_bf16.fsmn_ffn(x, w1, b1, w2, p=drop_p, res_grad=res_grad)
+    # the hidden activation only feeds the second contraction: bf16 in bf16 mode (fp32 mode ignores the flag)
+    h = linear(x, w1, b1, relu=True, drop_p=drop_p, out_bf16=True, res_grad=res_grad)
+    return linear(h, w2, None)
+
+
 def pnca_block_fused(blk, x, hkv, info, bw_x, bw_h, bw_dev, return_attn, next_ln, training):
     """bf16 mode on a HIP device: ops_bf16.pnca_block_fused (one launch for the block's forward pass); otherwise a no-op
     context (the fp32 parity path keeps its launches)."""

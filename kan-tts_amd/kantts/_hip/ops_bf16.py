@@ -21,7 +21,25 @@ from . import bgemm_nt, bgemm_tn, check, ffn_pair, lib, pnca_block_bwd, pnca_blo
 BF16 = torch.bfloat16
 _wcache = {}
 # the feed-forward pair as one launch (csrc/ffn_pair.hip); KANTTS_NO_FFN_PAIR=1 keeps the two-launch form (A/B runs)
-PAIR = {"on": os.environ.get("KANTTS_NO_FFN_PAIR", "") == ""}
+# ``fsmn``: the FSMN feed-forward nets (kantts/models/sambert/fsmn.py) through the same launch (tests, A/B runs)
+PAIR = {"on": os.environ.get("KANTTS_NO_FFN_PAIR", "") == "", "fsmn": True}
+# (input width, output width, hidden width) of the FSMN feed-forward nets csrc/ffn_pair.hip is instantiated for: the
+# postnet's and the pitch / energy predictors' layers behind the first (k = 1 both ways)
+FSMN_PAIR_SHAPES = ((256, 256, 512), (128, 128, 256))
+
+
+def frag_image_shape(role, shape):
+    """Does a Conv1d weight flagged ``_kantts_ffn_role`` get fragment-major images in the parameter arena?  w1 (F, C, k):
+    the transformer blocks' (1024, 128, odd k) and the FSMN shapes with k = 1; w2 (N, F, 1) likewise."""
+    if len(shape) != 3:
+        return False
+    if role == "w1":
+        F, C, kt = shape
+        return (F == 1024 and C == 128 and kt % 2 == 1) or (kt == 1 and any(C == c and F == f for c, _, f in FSMN_PAIR_SHAPES))
+    if role == "w2":
+        N, F, kt = shape
+        return kt == 1 and ((N == 128 and F == 1024) or any(N == n and F == f for _, n, f in FSMN_PAIR_SHAPES))
+    return False
 
 
 def _c(t):
@@ -1101,3 +1119,110 @@ def ffn(h, w1, b1, w2, b2, res, *, pad_rows=None, zero_rows=None, p_inner=0.0, p
     if pre is not None and pre.xn is not None:
         y._kantts_prenorm = pre
     return y
+
+
+# ================================================================================================
+# FSMN feed-forward net: Conv1d(1) + ReLU + dropout -> Conv1d(1, no bias)
+# ================================================================================================
+class _FusedFsmnFFNB(torch.autograd.Function):
+    """kantts/models/sambert/fsmn.py FeedForwardNet as ONE autograd node: y = dropout(relu(x W1^T + b1)) W2^T.  At the
+    shapes csrc/ffn_pair.hip is instantiated for (FSMN_PAIR_SHAPES) the forward pass is one launch and so is the pair of
+    input-gradient contractions (dz = gate_{hid > 0}(dy W2) / (1 - p), dx = dz W1 + the residual's gradient handed over by
+    ResGradToken); anywhere else -- the first layers (80 / 96 wide), the emulated ABI -- the node issues the two
+    kantts_bgemm_nt launches each way that two chained ops_bf16.linear calls issue.  Weight gradients as everywhere:
+    kantts_bgemm_tn from (dy, hid) and (dz, x), deferred and grouped by shape.  One seed, drawn where the two-launch form
+    draws it: same dropout masks."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, wb1, wb2, wf1, wf2, wt2, wt1, cfg):
+        from .ops import next_seed
+
+        x = _c(x)
+        lead, C = x.shape[:-1], x.shape[-1]
+        M = int(math.prod(lead))
+        F, N = w1.shape[0], w2.shape[0]
+        p = cfg["p"]
+        xd = x.detach()
+        seed = next_seed() if p > 0 else 0
+        # without autograd (inference) nothing reads the hidden tensor after the launch: the pair does not write it
+        hid = torch.empty((M, F), device=x.device, dtype=BF16) if cfg["save"] else None
+        out = torch.empty((M, N), device=x.device, dtype=torch.float32)
+        fused = cfg["pair"] and ffn_pair(xd.view(M, C), wf1, wf2, out, M=M, T=M, F=F, bias1=b1, relu=True, drop1_p=p,
+                                         drop1_seed=seed, t_out=hid)
+        if not fused:
+            if hid is None:
+                hid = torch.empty((M, F), device=x.device, dtype=BF16)
+            if not bgemm_nt([(xd, C, wb1, C, C, 0)], M, F, hid, F, bias=b1, relu=True, drop_p=p, drop_seed=seed):
+                raise RuntimeError("bgemm_nt declined the FSMN up-projection")
+            if not bgemm_nt([(hid, F, wb2, F, F, 0)], M, N, out, N):
+                raise RuntimeError("bgemm_nt declined the FSMN down-projection")
+        ctx.cfg, ctx.dims, ctx.lead, ctx.x_dtype = cfg, (M, F, C, N), lead, x.dtype
+        if cfg["save"]:
+            ctx.save_for_backward(xd, hid, wb1, wb2, wt2, wt1)
+        return out.view(*lead, N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .ops import gzeros, wgrad_overlap
+
+        x, hid, wb1, wb2, wt2, wt1 = ctx.saved_tensors
+        M, F, C, N = ctx.dims
+        cfg = ctx.cfg
+        p = cfg["p"]
+        dy = _c(dy).view(M, N)
+        dev = dy.device
+        a1 = 1.0 / (1.0 - p) if p > 0 else 1.0
+        need_dx = ctx.needs_input_grad[0]
+        rg = cfg.get("res_grad")
+        if rg is not None and rg.dres is not None and not need_dx:
+            raise RuntimeError("a residual gradient was handed to this net's input-gradient launch (ResGradToken), which "
+                               "does not run")
+        dres = None
+        if rg is not None and rg.dres is not None:  # the residual branch's gradient of x rides in on the ``res`` port
+            dres, rg.dres = _c(rg.dres).view(M, C), None
+        dz = torch.empty((M, F), device=dev, dtype=BF16)
+        dx = torch.empty((M, C), device=dev, dtype=ctx.x_dtype) if need_dx else None
+        fused = (cfg["pair"] and need_dx and wt1 is not None and wt2 is not None and dy.dtype == torch.float32
+                 and ffn_pair(dy, wt2, wt1, dx, M=M, T=M, F=F, alpha1=a1, gate=hid, t_out=dz, res=dres))
+        if not fused and not bgemm_nt([(dy, N, wb2, F, N, 0)], M, F, dz, F, b_kn=True, a_drop_ld=N, gate=hid, ldg=F, alpha=a1):
+            raise RuntimeError("bgemm_nt declined the FSMN hidden gradient")
+        dw2 = gzeros((N, F, 1), dev)
+        with wgrad_overlap.side(dy, hid):
+            if not bgemm_tn(dy, N, hid, F, M, N, F, dw2, F, 1):
+                raise RuntimeError("bgemm_tn declined dW2")
+        if not fused and need_dx:
+            rkw = dict(res=dres, ldr=C) if dres is not None else {}
+            if not bgemm_nt([(dz, F, wb1, C, F, 0)], M, C, dx, C, b_kn=True, a_drop_ld=F, **rkw):
+                raise RuntimeError("bgemm_nt declined the FSMN input gradient")
+        dw1 = gzeros((F, C, 1), dev)
+        db1 = gzeros((F,), dev)
+        with wgrad_overlap.side(dz, x):
+            if not bgemm_tn(dz, F, x, C, M, F, C, dw1, C, 1, db=db1):
+                raise RuntimeError("bgemm_tn declined dW1")
+        return (dx.view(*ctx.lead, C) if need_dx else None, dw1, db1, dw2) + (None,) * 7
+
+
+def fsmn_ffn_eligible(x, w1, b1, w2):
+    """Can the node take this net?  Conv1d(1) weights, a bias on the first, every extent a multiple of 8 (16-byte
+    vectors).  The node gates the hidden gradient in the epilogue of the launch that produces it, so the switch that asks
+    for the separate gate pass (RELUGATE off) keeps the two chained linears, as does PAIR["fsmn"] off."""
+    return (PAIR["fsmn"] and RELUGATE["on"] and w1.dim() == 3 and w2.dim() == 3 and w1.shape[2] == 1 and w2.shape[2] == 1 and b1 is not None
+            and x.numel() > 0 and x.shape[-1] == w1.shape[1] and w2.shape[1] == w1.shape[0]
+            and x.shape[-1] % 8 == 0 and w1.shape[0] % 8 == 0 and w2.shape[0] % 8 == 0)
+
+
+def fsmn_ffn(x, w1, b1, w2, *, p=0.0, res_grad=None):
+    """x (..., C) fp32 or bf16; w1 (F, C, 1), b1 (F), w2 (N, F, 1): dropout_p(relu(x W1^T + b1)) W2^T, fp32 (..., N).
+    ``res_grad``: as ops.linear."""
+    F, C, _ = w1.shape
+    N = w2.shape[0]
+    grad = torch.is_grad_enabled() and (x.requires_grad or w1.requires_grad or w2.requires_grad or b1.requires_grad)
+    pair = PAIR["on"] and (C, N, F) in FSMN_PAIR_SHAPES
+    cfg = dict(p=float(p), pair=pair, save=grad)
+    if (res_grad is not None and torch.is_grad_enabled() and x.dtype == torch.float32 and x.requires_grad and C % 4 == 0):
+        res_grad.armed = True
+        cfg["res_grad"] = res_grad
+    wf1 = wf2 = wt2 = wt1 = None
+    if pair:
+        wf1, wf2, wt2, wt1 = ffn_frag_weights(w1, w2)
+    return _FusedFsmnFFNB.apply(x, w1, b1, w2, bf16_weight(w1), bf16_weight(w2), wf1, wf2, wt2, wt1, cfg)

@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 from kantts._hip import ops
-from kantts._hip.ops_bf16 import ResGradToken
+from kantts._hip.ops_bf16 import FSMN_PAIR_SHAPES, ResGradToken
 from kantts.models.utils import SeqInfo
 
 
@@ -13,7 +13,8 @@ _RES_GRAD_PORT = not os.environ.get("KANTTS_NO_RES_GRAD_PORT")  # A/B switch: th
 
 
 class FeedForwardNet(nn.Module):
-    """Conv1d(k=1)+ReLU+dropout, Conv1d(k=1, no bias) == two GEMM launches (reference :8-40)."""
+    """Conv1d(k=1)+ReLU+dropout, Conv1d(k=1, no bias) (reference :8-40): ops.fsmn_ffn -- two GEMM launches, or one where
+    csrc/ffn_pair.hip has the shape (bf16 mode)."""
 
     def __init__(self, d_in, d_hid, d_out, kernel_size=[1, 1], dropout=0.1):
         super().__init__()
@@ -22,13 +23,15 @@ class FeedForwardNet(nn.Module):
         self.w_1 = nn.Conv1d(d_in, d_hid, k_in, padding=(k_in - 1) // 2)
         self.w_2 = nn.Conv1d(d_hid, d_out, k_out, padding=(k_out - 1) // 2, bias=False)
         self.dropout = nn.Dropout(dropout)
+        # bf16 mode: the parameter arena keeps the fragment-major images csrc/ffn_pair.hip streams, at the shapes it takes
+        if (d_in, d_out, d_hid) in FSMN_PAIR_SHAPES and k_in == 1 and k_out == 1:
+            self.w_1.weight._kantts_ffn_role = "w1"
+            self.w_2.weight._kantts_ffn_role = "w2"
 
     def forward(self, x, res_grad=None):
         """``res_grad``: x is also the residual of the layer this FFN opens (FsmnEncoderV2.forward)."""
         p = float(self.dropout.p) if self.training else 0.0
-        # the hidden activation only feeds the second contraction: bf16 in bf16 mode (fp32 mode ignores the flag)
-        h = ops.linear(x, self.w_1.weight, self.w_1.bias, relu=True, drop_p=p, out_bf16=True, res_grad=res_grad)
-        return ops.linear(h, self.w_2.weight, None)
+        return ops.fsmn_ffn(x, self.w_1.weight, self.w_1.bias, self.w_2.weight, drop_p=p, res_grad=res_grad)
 
 
 class MemoryBlockV2(nn.Module):

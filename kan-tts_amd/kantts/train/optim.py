@@ -307,8 +307,11 @@ class ParamArena:
             self._tap_blocks = max(self._tap_blocks, min(64, (n * cin * kt + 1023) // 1024))
         self._tap_table = torch.tensor(tab, dtype=torch.int64, device=dev) if tab else None
         # fragment-major images of the feed-forward weights (csrc/ffn_pair.hip; kantts_fragmajor_desc = src_off, dst_off,
-        # sr, sk (int64), R, K (int32)): forward images for every flagged pair of the supported shape and images of the
+        # sr, sk (int64), R, K (int32)): forward images for every flagged pair of a supported shape (the transformer blocks' and
+        # the FSMN nets', ops_bf16.frag_image_shape) and images of the
         # transposed weights (the backward operands), one per tap
+        from kantts._hip import ops_bf16
+
         ftab, foff = [], 0
         self._frag_blocks = 1
 
@@ -324,11 +327,11 @@ class ParamArena:
         views = []
         for p, o in zip(self.params, self.offsets):
             role = getattr(p, "_kantts_ffn_role", None)
-            if role == "w1" and p.dim() == 3 and p.shape[0] == 1024 and p.shape[1] == 128 and p.shape[2] % 2 == 1:
+            if role == "w1" and ops_bf16.frag_image_shape(role, p.shape):
                 F_, C_, KT_ = p.shape
                 views.append(image(p, o, F_, C_, C_ * KT_, KT_, "_kantts_frag", n_img=KT_))
                 views.append(image(p, o, C_, F_, KT_, C_ * KT_, "_kantts_fragT", n_img=KT_))  # W1[tap]^T: rows tap*C + c
-            elif role == "w2" and p.dim() == 3 and p.shape[0] == 128 and p.shape[1] == 1024 and p.shape[2] == 1:
+            elif role == "w2" and ops_bf16.frag_image_shape(role, p.shape):
                 N_, F_, _ = p.shape
                 views.append(image(p, o, N_, F_, F_, 1, "_kantts_frag"))
                 views.append(image(p, o, F_, N_, 1, F_, "_kantts_fragT"))
