@@ -220,6 +220,28 @@ int kantts_lstm_fwd_range(const float* gx, const float* whh, const float* bhh, c
 int kantts_lstm_fwd_slots(const float* gx, const float* whh, const float* bhh, const int32_t* lens, float* out,
                           float* gates_save, float* c_save, int B, int T, int H, const int32_t* t0, const int32_t* t1,
                           int precision, void* stream);
+/* TWO bidirectional layers of one shape (B, T, H = 128) over the same lengths in ONE launch each way: the pitch and the energy
+ * predictor's BiLSTMs (kantts/models/sambert/adaptors.py:109-134), which are independent and would otherwise run one after
+ * the other.  Every problem is computed exactly as its own kantts_lstm_fwd / kantts_lstm_bwd call with ndir = 2,
+ * reverse_first = 0 computes it (same bits in out, gates_save, c_save, dgates); tensors as documented there, except that the
+ * recurrent weights and biases are given PER DIRECTION (whh[d]: (4H,H), bhh[d]: (4H) or NULL), so the caller stacks nothing.
+ * precision must be 1 (the bf16 recurrent product): anything else, H != 128 or KANTTS_LSTM_PAIR=0 / KANTTS_LSTM_PAIR_BWD=0
+ * (the quad kernels have no such form) is KANTTS_E_UNSUPPORTED.  fwd reads gx, whh, bhh and writes out, gates_save, c_save;
+ * bwd reads dout, whh, gates_save, c_save and writes dgates; the other fields may be NULL. */
+typedef struct kantts_bilstm_args {
+  const float* gx;      /* (B,T,2*4H) */
+  const float* whh[2];
+  const float* bhh[2];
+  float* out;           /* (B,T,2H) */
+  float* gates_save;    /* (2,B,T,H,4) */
+  float* c_save;        /* (2,B,T,H) */
+  const float* dout;    /* (B,T,2H) */
+  float* dgates;        /* (2,B,T,4H) */
+} kantts_bilstm_args;
+int kantts_bilstm_pair_fwd(const kantts_bilstm_args* a, const kantts_bilstm_args* b, const int32_t* lens, int B, int T,
+                           int H, int precision, void* stream);
+int kantts_bilstm_pair_bwd(const kantts_bilstm_args* a, const kantts_bilstm_args* b, const int32_t* lens, int B, int T,
+                           int H, int precision, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Embedding gather-sum: out[row] = scale * sum_k table_k[ids[row,k]] (+ pos[row % T]);
@@ -342,6 +364,22 @@ int kantts_fsmn_memory_drop_fwd(const float* c, const float* w, const float* res
 int kantts_fsmn_memory_drop_bwd(const float* dy, const float* w, const int64_t* lens, float* dx, float* dym, int B, int T,
                                 int C, int K, int left_pad, float p1, uint64_t seed1, float p2, uint64_t seed2,
                                 const uint64_t* seed_dev, void* stream);
+/* TWO memory blocks of one shape (B, T, C, K, left_pad) over the same lengths in one launch each way (the pitch and the
+ * energy predictor's): each problem has its own operands, dropout probabilities and seeds, is checked as the single call
+ * checks it and gets that call's bits.  fwd: x = c, y = y, res optional, dym unused; bwd: x = dy, y = dx, dym required. */
+typedef struct kantts_fsmn_drop_args {
+  const float* x;
+  const float* w;
+  const float* res;
+  float* y;
+  float* dym;
+  float p1, p2;
+  uint64_t seed1, seed2;
+} kantts_fsmn_drop_args;
+int kantts_fsmn_memory_drop_fwd_pair(const kantts_fsmn_drop_args* a, const kantts_fsmn_drop_args* b, const int64_t* lens,
+                                     int B, int T, int C, int K, int left_pad, const uint64_t* seed_dev, void* stream);
+int kantts_fsmn_memory_drop_bwd_pair(const kantts_fsmn_drop_args* a, const kantts_fsmn_drop_args* b, const int64_t* lens,
+                                     int B, int T, int C, int K, int left_pad, const uint64_t* seed_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Masked L1 ("mae") reduction: loss_accum[0] += sum_{t<lens[b]} |target-pred| / (sum(lens)*C);
@@ -710,6 +748,10 @@ typedef struct kantts_bgemm_args {
   float* ln_rstd;
 } kantts_bgemm_args;
 int kantts_bgemm_nt(const kantts_bgemm_args* args, void* stream);
+/* Two kantts_bgemm_nt problems in ONE launch (third grid dimension = problem): each is checked and computed exactly as its
+ * own kantts_bgemm_nt call (same bits), with its own operands, epilogue options and dropout seed.  Both must have the same
+ * M, N, A dtype (a_f32), b_kn and tile choice, else KANTTS_E_UNSUPPORTED (nothing is launched); so is KANTTS_BGEMM_BM=128. */
+int kantts_bgemm_nt_pair(const kantts_bgemm_args* a, const kantts_bgemm_args* b, void* stream);
 
 /* kantts_bgemm_nt with the BACKWARD of a LayerNorm(128) as its epilogue.  The contraction's result (N == 128, b_kn) is
  * the gradient dy of a LayerNorm's output -- the input gradient of the projection that consumes the normalised rows of a
@@ -839,6 +881,10 @@ typedef struct kantts_ffn_args {
   float* ln_rstd;
 } kantts_ffn_args;
 int kantts_ffn_pair(const kantts_ffn_args* args, void* stream);
+/* Two kantts_ffn_pair problems of the (K1, N, F) = (128, 128, 256) geometry in ONE launch (second grid dimension = problem):
+ * each is checked and computed exactly as its own kantts_ffn_pair call (same bits).  Both must have the same M and the same
+ * form (forward: no gate; backward: gate); another geometry or a mismatch is KANTTS_E_UNSUPPORTED and launches nothing. */
+int kantts_ffn_pair2(const kantts_ffn_args* a, const kantts_ffn_args* b, void* stream);
 
 /* [round 5] One PNCA decoder block forward as ONE launch (csrc/pnca_block.hip; reference
  * kantts/models/sambert/__init__.py:212-348 with the feed-forward of :134-149; band masks kantts_sambert.py:135-166):

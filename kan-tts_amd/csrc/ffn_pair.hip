@@ -84,7 +84,9 @@ static void fp_launch_k1(const kantts_ffn_args& g, hipStream_t st) {
     hipLaunchKernelGGL((ffn_pair_kernel<false, 1, K1, N, F, BM, 1>), dim3(kantts_cdiv(g.M, BM)), dim3(FP_THREADS), 0, st, g);
 }
 
-extern "C" int kantts_ffn_pair(const kantts_ffn_args* gp, void* stream) {
+// The argument checks of kantts_ffn_pair, shared with the two-problem form.  *launch = false: M == 0, nothing to do.
+static int fp_check(const kantts_ffn_args* gp, bool* launch) {
+  *launch = false;
   if (!gp) return KANTTS_E_BADARG;
   const kantts_ffn_args& g = *gp;
   if (!g.x || !g.w1 || !g.w2 || !g.y || g.M < 0 || g.KT < 1) return KANTTS_E_BADARG;
@@ -112,7 +114,17 @@ extern "C" int kantts_ffn_pair(const kantts_ffn_args* gp, void* stream) {
   // regenerated input dropout, no row masks
   if (!blk && (g.KT != 1 || kt2 != 1 || g.ln_out || g.xdrop_p > 0.f || g.xrowmask || g.rowmask1 || g.rowmask2))
     return KANTTS_E_UNSUPPORTED;
-  if (g.M == 0) return KANTTS_OK;
+  *launch = g.M > 0;
+  return KANTTS_OK;
+}
+
+extern "C" int kantts_ffn_pair(const kantts_ffn_args* gp, void* stream) {
+  bool launch = false;
+  const int rc = fp_check(gp, &launch);
+  if (rc != KANTTS_OK || !launch) return rc;
+  const kantts_ffn_args& g = *gp;
+  const bool wide = g.K1 == 256, slim = g.F == 256;  // (fp_check took one of the three geometries)
+  const int kt2 = g.KT2 < 1 ? 1 : g.KT2;
   hipStream_t st = (hipStream_t)stream;
   if (wide)
     fp_launch_k1<256, 256, 512, FP_BM_WIDE>(g, st);
@@ -127,6 +139,42 @@ extern "C" int kantts_ffn_pair(const kantts_ffn_args* gp, void* stream) {
   else
     hipLaunchKernelGGL((ffn_pair_kernel<false, 1, 128, 128, 1024, 32, 9>), dim3(kantts_cdiv(g.M, 32)), dim3(FP_THREADS), 0, st,
                        g);
+  KANTTS_CHECK_LAUNCH();
+}
+
+// Two feed-forward nets of the (128, 128, 256) geometry in ONE launch (the same layer of the pitch and of the energy
+// predictor): blockIdx.y picks the argument block (a uniform index into the kernel arguments), the body is that of
+// ffn_pair_kernel -- it places its tile by blockIdx.x alone -- so each problem gets the bits of its own kantts_ffn_pair call.
+struct FfnPair2Args {
+  kantts_ffn_args p[2];
+};
+template <bool BWD>
+__global__ __launch_bounds__(FP_THREADS) void ffn_pair2_kernel(const FfnPair2Args pa) {
+  constexpr int KT2 = 1, K1 = 128, N = 128, F = 256, BM = 32, MAXKT = 1;
+  const kantts_ffn_args& g = pa.p[blockIdx.y];
+#include "ffn_pair_body.inc"
+}
+
+extern "C" int kantts_ffn_pair2(const kantts_ffn_args* a, const kantts_ffn_args* b, void* stream) {
+  bool la = false, lb = false;
+  int rc = fp_check(a, &la);
+  if (rc != KANTTS_OK) return rc;
+  rc = fp_check(b, &lb);
+  if (rc != KANTTS_OK) return rc;
+  const kantts_ffn_args* both[2] = {a, b};
+  for (const kantts_ffn_args* g : both)
+    if (g->K1 != 128 || g->N != 128 || g->F != 256) return KANTTS_E_UNSUPPORTED;
+  // one grid and one form (forward / backward) for both
+  if (a->M != b->M || (a->gate != nullptr) != (b->gate != nullptr)) return KANTTS_E_UNSUPPORTED;
+  if (!la) return KANTTS_OK;
+  FfnPair2Args pa;
+  pa.p[0] = *a;
+  pa.p[1] = *b;
+  const dim3 grid(kantts_cdiv(a->M, 32), 2);
+  if (a->gate)
+    hipLaunchKernelGGL(ffn_pair2_kernel<true>, grid, dim3(FP_THREADS), 0, (hipStream_t)stream, pa);
+  else
+    hipLaunchKernelGGL(ffn_pair2_kernel<false>, grid, dim3(FP_THREADS), 0, (hipStream_t)stream, pa);
   KANTTS_CHECK_LAUNCH();
 }
 

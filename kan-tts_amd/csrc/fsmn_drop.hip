@@ -33,15 +33,29 @@
 #define FD_WQ (FD_Q + 1)                     // tap row pitch in float4: 68 floats, so the transposing writes spread over banks
 static_assert((FD_TT * FD_Q) % FD_THREADS == 0, "the padded-tile loop has no remainder");
 
+// The operands of one problem: the single launch passes one block, the pair launch (two memory blocks of one shape over the
+// same lengths: the pitch and the energy predictor's) two, picked by blockIdx.y.
+struct FdProblem {
+  const float* x;
+  const float* w;
+  const float* res;
+  float* y;
+  float* dym;
+  float p1, p2;
+  uint64_t seed1, seed2;
+};
+struct FdPairArgs {
+  FdProblem p[2];
+};
+
 // BWD = false: x = c (the projection's output), y = keep1 * keep2 * len-masked(FIR(c) + c) (+ res); dym unused.
 // BWD = true:  x = dy, dym = len-masked(keep1 * keep2 * dy) (the tile's own rows), y = dx = len-masked(FIRflip(dym) + dym).
 template <bool BWD>
-__global__ __launch_bounds__(FD_THREADS) void fsmn_drop41_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                 const float* __restrict__ res,
-                                                                 const int64_t* __restrict__ lens, float* __restrict__ y,
-                                                                 float* __restrict__ dym, int B, int T, int C, int lp,
-                                                                 float p1, uint64_t seed1, float p2, uint64_t seed2,
-                                                                 const uint64_t* __restrict__ seed_dev) {
+__device__ __forceinline__ void fsmn_drop41_body(const float* __restrict__ x, const float* __restrict__ w,
+                                                 const float* __restrict__ res, const int64_t* __restrict__ lens,
+                                                 float* __restrict__ y, float* __restrict__ dym, int B, int T, int C, int lp,
+                                                 float p1, uint64_t seed1, float p2, uint64_t seed2,
+                                                 const uint64_t* __restrict__ seed_dev) {
   __shared__ float4 sx[FD_ROWS * FD_Q];
   __shared__ float4 sw[FD_K * FD_WQ];
   // XCD-aware order (see fsmn_fir41_kernel): consecutive workgroup ids are dealt to the 8 XCDs in turn, each with its own L2,
@@ -202,6 +216,22 @@ __global__ __launch_bounds__(FD_THREADS) void fsmn_drop41_kernel(const float* __
   }
 }
 
+template <bool BWD>
+__global__ __launch_bounds__(FD_THREADS) void fsmn_drop41_kernel(const FdProblem a, const int64_t* __restrict__ lens, int B,
+                                                                 int T, int C, int lp,
+                                                                 const uint64_t* __restrict__ seed_dev) {
+  fsmn_drop41_body<BWD>(a.x, a.w, a.res, lens, a.y, a.dym, B, T, C, lp, a.p1, a.seed1, a.p2, a.seed2, seed_dev);
+}
+
+// grid (tiles of one problem, 2): the XCD-aware order of the body runs over gridDim.x, i.e. per problem
+template <bool BWD>
+__global__ __launch_bounds__(FD_THREADS) void fsmn_drop41_pair_kernel(const FdPairArgs pa, const int64_t* __restrict__ lens,
+                                                                      int B, int T, int C, int lp,
+                                                                      const uint64_t* __restrict__ seed_dev) {
+  const FdProblem& a = pa.p[blockIdx.y];
+  fsmn_drop41_body<BWD>(a.x, a.w, a.res, lens, a.y, a.dym, B, T, C, lp, a.p1, a.seed1, a.p2, a.seed2, seed_dev);
+}
+
 static bool fd_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 static int fd_check(const void* a, const void* w, const void* o, int B, int T, int C, int K, int left_pad, float p1, float p2,
@@ -215,16 +245,33 @@ static int fd_check(const void* a, const void* w, const void* o, int B, int T, i
   return KANTTS_OK;
 }
 
+// one problem's checks: the forward form (c, res, y) or the backward form (dy, dx, dym)
+static int fd_check_fwd(const float* c, const float* w, const float* res, float* y, int B, int T, int C, int K, int left_pad,
+                        float p1, float p2, long long* blocks) {
+  const int rc = fd_check(c, w, y, B, T, C, K, left_pad, p1, p2, blocks);
+  if (rc != KANTTS_OK) return rc;
+  if (!fd_aligned16(c) || !fd_aligned16(res) || !fd_aligned16(y)) return KANTTS_E_UNSUPPORTED;
+  return KANTTS_OK;
+}
+static int fd_check_bwd(const float* dy, const float* w, float* dx, float* dym, int B, int T, int C, int K, int left_pad,
+                        float p1, float p2, long long* blocks) {
+  const int rc = fd_check(dy, w, dx, B, T, C, K, left_pad, p1, p2, blocks);
+  if (rc != KANTTS_OK) return rc;
+  if (!dym) return KANTTS_E_BADARG;
+  if (!fd_aligned16(dy) || !fd_aligned16(dx) || !fd_aligned16(dym)) return KANTTS_E_UNSUPPORTED;
+  return KANTTS_OK;
+}
+
 extern "C" int kantts_fsmn_memory_drop_fwd(const float* c, const float* w, const float* res, const int64_t* lens, float* y,
                                            int B, int T, int C, int K, int left_pad, float p1, uint64_t seed1, float p2,
                                            uint64_t seed2, const uint64_t* seed_dev, void* stream) {
   long long blocks = 0;
-  const int rc = fd_check(c, w, y, B, T, C, K, left_pad, p1, p2, &blocks);
+  const int rc = fd_check_fwd(c, w, res, y, B, T, C, K, left_pad, p1, p2, &blocks);
   if (rc != KANTTS_OK) return rc;
-  if (!fd_aligned16(c) || !fd_aligned16(res) || !fd_aligned16(y)) return KANTTS_E_UNSUPPORTED;
   if (blocks == 0) return KANTTS_OK;
-  hipLaunchKernelGGL(fsmn_drop41_kernel<false>, dim3((unsigned)blocks), dim3(FD_THREADS), 0, (hipStream_t)stream, c, w, res,
-                     lens, y, (float*)nullptr, B, T, C, left_pad, p1, seed1, p2, seed2, seed_dev);
+  const FdProblem a = {c, w, res, y, nullptr, p1, p2, seed1, seed2};
+  hipLaunchKernelGGL(fsmn_drop41_kernel<false>, dim3((unsigned)blocks), dim3(FD_THREADS), 0, (hipStream_t)stream, a, lens, B,
+                     T, C, left_pad, seed_dev);
   KANTTS_CHECK_LAUNCH();
 }
 
@@ -232,12 +279,51 @@ extern "C" int kantts_fsmn_memory_drop_bwd(const float* dy, const float* w, cons
                                            int T, int C, int K, int left_pad, float p1, uint64_t seed1, float p2,
                                            uint64_t seed2, const uint64_t* seed_dev, void* stream) {
   long long blocks = 0;
-  const int rc = fd_check(dy, w, dx, B, T, C, K, left_pad, p1, p2, &blocks);
+  const int rc = fd_check_bwd(dy, w, dx, dym, B, T, C, K, left_pad, p1, p2, &blocks);
   if (rc != KANTTS_OK) return rc;
-  if (!dym) return KANTTS_E_BADARG;
-  if (!fd_aligned16(dy) || !fd_aligned16(dx) || !fd_aligned16(dym)) return KANTTS_E_UNSUPPORTED;
   if (blocks == 0) return KANTTS_OK;
-  hipLaunchKernelGGL(fsmn_drop41_kernel<true>, dim3((unsigned)blocks), dim3(FD_THREADS), 0, (hipStream_t)stream, dy, w,
-                     (const float*)nullptr, lens, dx, dym, B, T, C, left_pad, p1, seed1, p2, seed2, seed_dev);
+  const FdProblem a = {dy, w, nullptr, dx, dym, p1, p2, seed1, seed2};
+  hipLaunchKernelGGL(fsmn_drop41_kernel<true>, dim3((unsigned)blocks), dim3(FD_THREADS), 0, (hipStream_t)stream, a, lens, B, T,
+                     C, left_pad, seed_dev);
+  KANTTS_CHECK_LAUNCH();
+}
+
+// Two memory blocks of one shape (B, T, C, K, left_pad) over the same lengths in one launch each way; every problem keeps its
+// own operands, dropout probabilities and seeds, and gets the bits of its own single call.
+extern "C" int kantts_fsmn_memory_drop_fwd_pair(const kantts_fsmn_drop_args* a, const kantts_fsmn_drop_args* b,
+                                                const int64_t* lens, int B, int T, int C, int K, int left_pad,
+                                                const uint64_t* seed_dev, void* stream) {
+  if (!a || !b) return KANTTS_E_BADARG;
+  long long blocks = 0;
+  FdPairArgs pa;
+  const kantts_fsmn_drop_args* both[2] = {a, b};
+  for (int i = 0; i < 2; ++i) {
+    const kantts_fsmn_drop_args& g = *both[i];
+    const int rc = fd_check_fwd(g.x, g.w, g.res, g.y, B, T, C, K, left_pad, g.p1, g.p2, &blocks);
+    if (rc != KANTTS_OK) return rc;
+    pa.p[i] = {g.x, g.w, g.res, g.y, nullptr, g.p1, g.p2, g.seed1, g.seed2};
+  }
+  if (blocks == 0) return KANTTS_OK;
+  hipLaunchKernelGGL(fsmn_drop41_pair_kernel<false>, dim3((unsigned)blocks, 2), dim3(FD_THREADS), 0, (hipStream_t)stream, pa,
+                     lens, B, T, C, left_pad, seed_dev);
+  KANTTS_CHECK_LAUNCH();
+}
+
+extern "C" int kantts_fsmn_memory_drop_bwd_pair(const kantts_fsmn_drop_args* a, const kantts_fsmn_drop_args* b,
+                                                const int64_t* lens, int B, int T, int C, int K, int left_pad,
+                                                const uint64_t* seed_dev, void* stream) {
+  if (!a || !b) return KANTTS_E_BADARG;
+  long long blocks = 0;
+  FdPairArgs pa;
+  const kantts_fsmn_drop_args* both[2] = {a, b};
+  for (int i = 0; i < 2; ++i) {
+    const kantts_fsmn_drop_args& g = *both[i];
+    const int rc = fd_check_bwd(g.x, g.w, g.y, g.dym, B, T, C, K, left_pad, g.p1, g.p2, &blocks);
+    if (rc != KANTTS_OK) return rc;
+    pa.p[i] = {g.x, g.w, nullptr, g.y, g.dym, g.p1, g.p2, g.seed1, g.seed2};
+  }
+  if (blocks == 0) return KANTTS_OK;
+  hipLaunchKernelGGL(fsmn_drop41_pair_kernel<true>, dim3((unsigned)blocks, 2), dim3(FD_THREADS), 0, (hipStream_t)stream, pa,
+                     lens, B, T, C, left_pad, seed_dev);
   KANTTS_CHECK_LAUNCH();
 }

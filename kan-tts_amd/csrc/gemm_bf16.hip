@@ -178,7 +178,9 @@ static void bg_launch_nt(const kantts_bgemm_args& g, dim3 grid, hipStream_t st) 
 
 static bool bg_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-extern "C" int kantts_bgemm_nt(const kantts_bgemm_args* gp, void* stream) {
+// The argument checks and the tile choice of kantts_bgemm_nt, shared with the pair form.  *bm = 0: nothing to launch.
+static int bg_nt_check(const kantts_bgemm_args* gp, int* bm_out) {
+  *bm_out = 0;
   if (!gp) return KANTTS_E_BADARG;
   const kantts_bgemm_args& g = *gp;
   if (g.nseg < 1 || g.nseg > KANTTS_BGEMM_MAX_SEG || g.M < 0 || g.N < 0 || !g.c) return KANTTS_E_BADARG;
@@ -209,6 +211,16 @@ extern "C" int kantts_bgemm_nt(const kantts_bgemm_args* gp, void* stream) {
   // M = 19584, 512 -> 256: 28.1 us against 34.9 (profiles/r03_runU_postnet_gemm_tiles.log)
   int bm = (wg64 >= 256 && !g.a_f32) ? 64 : 32;
   if (force_bm) bm = atoi(force_bm);
+  *bm_out = bm == 128 ? 128 : (bm == 64 ? 64 : 32);
+  return KANTTS_OK;
+}
+
+extern "C" int kantts_bgemm_nt(const kantts_bgemm_args* gp, void* stream) {
+  int bm = 0;
+  const int rc = bg_nt_check(gp, &bm);
+  if (rc != KANTTS_OK || bm == 0) return rc;
+  const kantts_bgemm_args& g = *gp;
+  const long long nt = kantts_cdiv(g.N, BG_BN);
   hipStream_t st = (hipStream_t)stream;
   if (bm == 128)
     bg_launch_nt<128>(g, dim3(nt, kantts_cdiv(g.M, 128)), st);
@@ -216,6 +228,60 @@ extern "C" int kantts_bgemm_nt(const kantts_bgemm_args* gp, void* stream) {
     bg_launch_nt<64>(g, dim3(nt, kantts_cdiv(g.M, 64)), st);
   else
     bg_launch_nt<32>(g, dim3(nt, kantts_cdiv(g.M, 32)), st);
+  KANTTS_CHECK_LAUNCH();
+}
+
+// Two problems of one shape in ONE launch: blockIdx.z picks the argument block (a uniform index into the kernel arguments:
+// scalar loads), the body is that of bgemm_nt_kernel, the XCD remap runs over the x-y grid of one problem -- every problem
+// gets the bits of its own kantts_bgemm_nt call.
+struct BgPairArgs {
+  kantts_bgemm_args p[2];
+};
+template <int BM, bool A_F32, bool B_KN>
+__global__ __launch_bounds__(BG_THREADS) void bgemm_nt_pair_kernel(const BgPairArgs pa) {
+  constexpr bool LNB = false;
+  const kantts_lnbwd_args* const lnb = nullptr;
+  const kantts_bgemm_args& g = pa.p[blockIdx.z];
+#include "gemm_bf16_nt_body.inc"
+}
+
+template <int BM>
+static void bg_launch_nt_pair(const BgPairArgs& pa, dim3 grid, hipStream_t st) {
+  const bool af = pa.p[0].a_f32 != 0, kn = pa.p[0].b_kn != 0;
+  if (af) {
+    if (kn)
+      hipLaunchKernelGGL((bgemm_nt_pair_kernel<BM, true, true>), grid, dim3(BG_THREADS), 0, st, pa);
+    else
+      hipLaunchKernelGGL((bgemm_nt_pair_kernel<BM, true, false>), grid, dim3(BG_THREADS), 0, st, pa);
+  } else {
+    if (kn)
+      hipLaunchKernelGGL((bgemm_nt_pair_kernel<BM, false, true>), grid, dim3(BG_THREADS), 0, st, pa);
+    else
+      hipLaunchKernelGGL((bgemm_nt_pair_kernel<BM, false, false>), grid, dim3(BG_THREADS), 0, st, pa);
+  }
+}
+
+extern "C" int kantts_bgemm_nt_pair(const kantts_bgemm_args* a, const kantts_bgemm_args* b, void* stream) {
+  int bma = 0, bmb = 0;
+  int rc = bg_nt_check(a, &bma);
+  if (rc != KANTTS_OK) return rc;
+  rc = bg_nt_check(b, &bmb);
+  if (rc != KANTTS_OK) return rc;
+  // one grid and one instantiation for both: same M, N, tile and template variant (128-row tiles are an experiment of the
+  // single launch only)
+  if (a->M != b->M || a->N != b->N || bma != bmb || (a->a_f32 != 0) != (b->a_f32 != 0) || (a->b_kn != 0) != (b->b_kn != 0) ||
+      bma == 128)
+    return KANTTS_E_UNSUPPORTED;
+  if (bma == 0) return KANTTS_OK;
+  BgPairArgs pa;
+  pa.p[0] = *a;
+  pa.p[1] = *b;
+  const long long nt = kantts_cdiv(a->N, BG_BN);
+  hipStream_t st = (hipStream_t)stream;
+  if (bma == 64)
+    bg_launch_nt_pair<64>(pa, dim3(nt, kantts_cdiv(a->M, 64), 2), st);
+  else
+    bg_launch_nt_pair<32>(pa, dim3(nt, kantts_cdiv(a->M, 32), 2), st);
   KANTTS_CHECK_LAUNCH();
 }
 

@@ -246,14 +246,15 @@ __global__ __launch_bounds__(LG) void lstm_fwd_kernel(const float* __restrict__ 
 // v_dot2: 0.70 us per step against 0.57 -- the step is a latency chain, not an issue-bound loop, and the accumulators of
 // four dependent 16-cycle MFMAs arrive later than the last v_dot2.
 // RANGE: as in lstm_fwd_kernel.
+// The body is shared by lstm_fwd_pair_kernel and lstm_fwd_duo_kernel (two BiLSTMs in one launch): whh / bhh point at THIS
+// direction's (4H, H) / (4H) block, `dir` places the direction inside gx / out / the saved tensors.
 template <int RANGE>
-__global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
-                                                           const float* __restrict__ bhh, const int32_t* __restrict__ lens,
-                                                           float* __restrict__ out, float* __restrict__ gates_out,
-                                                           float* __restrict__ c_out, int B, int T, int ndir,
-                                                           int reverse_first, int t0, int t1,
-                                                           const int32_t* __restrict__ t0_seq,
-                                                           const int32_t* __restrict__ t1_seq) {
+__device__ __forceinline__ void lstm_fwd_pair_body(const float* __restrict__ gx, const float* __restrict__ whh,
+                                                   const float* __restrict__ bhh, const int32_t* __restrict__ lens,
+                                                   float* __restrict__ out, float* __restrict__ gates_out,
+                                                   float* __restrict__ c_out, int B, int T, int ndir, const int dir,
+                                                   const bool rev, int t0, int t1, const int32_t* __restrict__ t0_seq,
+                                                   const int32_t* __restrict__ t1_seq) {
   if (RANGE == 2) {
     t0 = min(max(t0_seq[blockIdx.x], 0), T);
     t1 = min(max(t1_seq[blockIdx.x], t0), T);
@@ -261,8 +262,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restr
   }
   __shared__ __attribute__((aligned(16))) __bf16 h_b[2][LH];
   const int tid = threadIdx.x, j = tid >> 1, p = tid & 1;
-  const int b = blockIdx.x, dir = blockIdx.y;
-  const bool rev = RANGE ? false : (reverse_first ? true : (dir == 1));
+  const int b = blockIdx.x;
   const int len = lens ? min(max(lens[b], 0), T) : T;  // clamped into [0, T]: the tail loops below start at len
   const int s_beg = RANGE ? t0 : 0, s_end = RANGE ? min(len, t1) : len;  // the steps this launch runs
   lstm_bf16x2 wq[4 * 32];
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restr
   for (int g = 0; g < 4; ++g) {
     // slot g of lane p holds gate g ^ 2 p: every lane KEEPS slots 0, 1 (its own gate pair) and SENDS slots 2, 3 (its
     // partner's pair) -- the exchange below needs no select
-    const float4* wp = reinterpret_cast<const float4*>(whh + ((long long)dir * LG + (g ^ (2 * p)) * LH + j) * LH + p * 64);
+    const float4* wp = reinterpret_cast<const float4*>(whh + ((long long)(g ^ (2 * p)) * LH + j) * LH + p * 64);
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
       const float4 t = wp[k];
@@ -279,8 +279,8 @@ __global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restr
     }
   }
   // lane p brings in gx + bias of the gates 2 p and 2 p + 1
-  const float bias0 = bhh ? bhh[dir * LG + (2 * p) * LH + j] : 0.f;
-  const float bias1 = bhh ? bhh[dir * LG + (2 * p + 1) * LH + j] : 0.f;
+  const float bias0 = bhh ? bhh[(2 * p) * LH + j] : 0.f;
+  const float bias1 = bhh ? bhh[(2 * p + 1) * LH + j] : 0.f;
   if (p == 0) h_b[0][j] = (__bf16)0.f;
   float c = 0.f;
   const int gx_ld = ndir * LG;  // offsets inside one sequence are 32-bit (T * ndir * 4H < 2^31: checked by the launchers)
@@ -369,6 +369,35 @@ __global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restr
   for (int tt = RANGE ? max(len, t0) : len; tt < (RANGE ? t1 : T); ++tt)
     if (tid < LH) outb[(long long)tt * ndir * LH + tid] = 0.f;
   if ((LSTM_ABL & 1) && p_sink == 123.456f) outb[0] = p_sink;
+}
+
+template <int RANGE>
+__global__ __launch_bounds__(256) void lstm_fwd_pair_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
+                                                           const float* __restrict__ bhh, const int32_t* __restrict__ lens,
+                                                           float* __restrict__ out, float* __restrict__ gates_out,
+                                                           float* __restrict__ c_out, int B, int T, int ndir,
+                                                           int reverse_first, int t0, int t1,
+                                                           const int32_t* __restrict__ t0_seq,
+                                                           const int32_t* __restrict__ t1_seq) {
+  const int dir = blockIdx.y;
+  const bool rev = RANGE ? false : (reverse_first ? true : (dir == 1));
+  lstm_fwd_pair_body<RANGE>(gx, whh + (long long)dir * LG * LH, bhh ? bhh + dir * LG : nullptr, lens, out, gates_out, c_out,
+                            B, T, ndir, dir, rev, t0, t1, t0_seq, t1_seq);
+}
+
+// Two BiLSTMs of one shape in ONE launch (the pitch and the energy predictor, which share their input rows and lengths):
+// grid (B, 4), blockIdx.y = 2 * problem + direction.  The problem's pointers are picked from the kernel arguments (scalar
+// loads at a uniform index); the recurrence is lstm_fwd_pair_body / lstm_bwd_pair_body, unchanged, so every problem gets the
+// bits of its own kantts_lstm_fwd / kantts_lstm_bwd call.
+struct LstmDuoArgs {
+  kantts_bilstm_args p[2];
+};
+__global__ __launch_bounds__(256) void lstm_fwd_duo_kernel(const LstmDuoArgs a, const int32_t* __restrict__ lens, int B,
+                                                          int T) {
+  const int prob = blockIdx.y >> 1, dir = blockIdx.y & 1;
+  const kantts_bilstm_args& g = a.p[prob];
+  lstm_fwd_pair_body<0>(g.gx, g.whh[dir], g.bhh[dir], lens, g.out, g.gates_save, g.c_save, B, T, 2, dir, dir == 1, 0, T,
+                        nullptr, nullptr);
 }
 
 __device__ __forceinline__ float lstm_dpp_half_mirror(float v) {
@@ -543,22 +572,22 @@ __global__ __launch_bounds__(LG) void lstm_bwd_kernel(const float* __restrict__ 
 // slot with one bit flipped -- xor 1: g(l ^ 1) = g(l) ^ 1 -> slot s ^ 1; xor 2 -> slot s ^ 2; row_half_mirror = xor 7:
 // g(l ^ 7) = g(l) ^ 4 -> slot s ^ 4; row_ror:8 = xor 8: same g, slot 0 -- so every lane keeps the even slots, then slots 0
 // and 4, then slot 0, and lanes l and l ^ 8 (the two gate pairs of cell g(l & 7)) both end with that cell's dh.
-__global__ __launch_bounds__(256) void lstm_bwd_pair_kernel(const float* __restrict__ dout, const float* __restrict__ whh,
-                                                           const int32_t* __restrict__ lens, const float* __restrict__ gates,
-                                                           const float* __restrict__ cst, float* __restrict__ dgates, int B,
-                                                           int T, int ndir, int reverse_first) {
+// The body is shared by lstm_bwd_pair_kernel and lstm_bwd_duo_kernel: whh points at THIS direction's (4H, H) block.
+__device__ __forceinline__ void lstm_bwd_pair_body(const float* __restrict__ dout, const float* __restrict__ whh,
+                                                   const int32_t* __restrict__ lens, const float* __restrict__ gates,
+                                                   const float* __restrict__ cst, float* __restrict__ dgates, int B, int T,
+                                                   int ndir, const int dir, const bool rev) {
   __shared__ __attribute__((aligned(16))) __bf16 dg_b[2][LG];
   const int tid = threadIdx.x, row = tid >> 4, l = tid & 15;
   const int g3 = (l & 1) ^ (((l >> 1) & 1) * 2) ^ (((l >> 2) & 1) * 7);  // g(l & 7)
   const int k = row * 8 + g3, gp = l >> 3;  // phase-A identity: cell, gate pair
-  const int b = blockIdx.x, dir = blockIdx.y;
-  const bool rev = reverse_first ? true : (dir == 1);
+  const int b = blockIdx.x;
   const int len = lens ? min(max(lens[b], 0), T) : T;  // clamped into [0, T]: the tail loops below start at len
   // phase-B weights: slot s = W_hh[32 l + rr][8 row + (s ^ g3)], s < 8, rr < 32 (pairs over rr)
   lstm_bf16x2 wq[8 * 16];
 #pragma unroll
   for (int rr = 0; rr < 32; rr += 2) {
-    const float* r0 = whh + ((long long)dir * LG + l * 32 + rr) * LH + row * 8;
+    const float* r0 = whh + ((long long)l * 32 + rr) * LH + row * 8;
     const float4 w00 = *reinterpret_cast<const float4*>(r0), w01 = *reinterpret_cast<const float4*>(r0 + 4);
     const float4 w10 = *reinterpret_cast<const float4*>(r0 + LH), w11 = *reinterpret_cast<const float4*>(r0 + LH + 4);
     const float a0[8] = {w00.x, w00.y, w00.z, w00.w, w01.x, w01.y, w01.z, w01.w};
@@ -673,6 +702,22 @@ __global__ __launch_bounds__(256) void lstm_bwd_pair_kernel(const float* __restr
   }
 }
 
+__global__ __launch_bounds__(256) void lstm_bwd_pair_kernel(const float* __restrict__ dout, const float* __restrict__ whh,
+                                                           const int32_t* __restrict__ lens, const float* __restrict__ gates,
+                                                           const float* __restrict__ cst, float* __restrict__ dgates, int B,
+                                                           int T, int ndir, int reverse_first) {
+  const int dir = blockIdx.y;
+  lstm_bwd_pair_body(dout, whh + (long long)dir * LG * LH, lens, gates, cst, dgates, B, T, ndir, dir,
+                     reverse_first ? true : (dir == 1));
+}
+
+__global__ __launch_bounds__(256) void lstm_bwd_duo_kernel(const LstmDuoArgs a, const int32_t* __restrict__ lens, int B,
+                                                          int T) {
+  const int prob = blockIdx.y >> 1, dir = blockIdx.y & 1;
+  const kantts_bilstm_args& g = a.p[prob];
+  lstm_bwd_pair_body(g.dout, g.whh[dir], lens, g.gates_save, g.c_save, g.dgates, B, T, 2, dir, dir == 1);
+}
+
 extern "C" int kantts_lstm_fwd(const float* gx, const float* whh, const float* bhh, const int32_t* lens, float* out,
                                float* gates_save, float* c_save, int B, int T, int H, int ndir, int reverse_first,
                                int precision, void* stream) {
@@ -756,6 +801,49 @@ extern "C" int kantts_lstm_bwd(const float* dout, const float* whh, const int32_
   else
     hipLaunchKernelGGL(lstm_bwd_kernel<false>, dim3(B, ndir), dim3(LG), 0, (hipStream_t)stream, dout, whh, lens,
                        gates_save, c_save, dgates, B, T, ndir, reverse_first);
+  KANTTS_CHECK_LAUNCH();
+}
+
+// Two BiLSTMs in one launch (bf16 mode, the pair-of-lanes kernels).  Each struct is checked as kantts_lstm_fwd / _bwd check
+// their arguments; KANTTS_LSTM_PAIR[_BWD]=0 (the quad kernels) has no such form: KANTTS_E_UNSUPPORTED.
+static int lstm_duo_check(const kantts_bilstm_args* a, const kantts_bilstm_args* b, bool bwd, int B, int T, int H,
+                          int precision) {
+  if (!a || !b || B < 0 || T < 0) return KANTTS_E_BADARG;
+  const kantts_bilstm_args* both[2] = {a, b};
+  for (const kantts_bilstm_args* g : both) {
+    if (!g->whh[0] || !g->whh[1] || !g->gates_save || !g->c_save) return KANTTS_E_BADARG;
+    if (bwd ? (!g->dout || !g->dgates) : (!g->gx || !g->out)) return KANTTS_E_BADARG;
+  }
+  if (H != LH || precision != 1) return KANTTS_E_UNSUPPORTED;
+  if ((long long)T * 2 * LG >= (1ll << 31)) return KANTTS_E_UNSUPPORTED;  // 32-bit offsets inside one sequence
+  return KANTTS_OK;
+}
+
+extern "C" int kantts_bilstm_pair_fwd(const kantts_bilstm_args* a, const kantts_bilstm_args* b, const int32_t* lens, int B,
+                                      int T, int H, int precision, void* stream) {
+  const int rc = lstm_duo_check(a, b, false, B, T, H, precision);
+  if (rc != KANTTS_OK) return rc;
+  static const char* env_pair = getenv("KANTTS_LSTM_PAIR");  // the A/B switch of kantts_lstm_fwd (read once per process)
+  if (env_pair && atoi(env_pair) == 0) return KANTTS_E_UNSUPPORTED;
+  if (B == 0 || T == 0) return KANTTS_OK;
+  LstmDuoArgs d;
+  d.p[0] = *a;
+  d.p[1] = *b;
+  hipLaunchKernelGGL(lstm_fwd_duo_kernel, dim3(B, 4), dim3(256), 0, (hipStream_t)stream, d, lens, B, T);
+  KANTTS_CHECK_LAUNCH();
+}
+
+extern "C" int kantts_bilstm_pair_bwd(const kantts_bilstm_args* a, const kantts_bilstm_args* b, const int32_t* lens, int B,
+                                      int T, int H, int precision, void* stream) {
+  const int rc = lstm_duo_check(a, b, true, B, T, H, precision);
+  if (rc != KANTTS_OK) return rc;
+  static const char* env_pair = getenv("KANTTS_LSTM_PAIR_BWD");  // the A/B switch of kantts_lstm_bwd
+  if (env_pair && atoi(env_pair) == 0) return KANTTS_E_UNSUPPORTED;
+  if (B == 0 || T == 0) return KANTTS_OK;
+  LstmDuoArgs d;
+  d.p[0] = *a;
+  d.p[1] = *b;
+  hipLaunchKernelGGL(lstm_bwd_duo_kernel, dim3(B, 4), dim3(256), 0, (hipStream_t)stream, d, lens, B, T);
   KANTTS_CHECK_LAUNCH();
 }
 

@@ -244,6 +244,18 @@ class BGemmArgs(Structure):
     ]
 
 
+class BiLstmArgs(Structure):
+    """kantts_bilstm_args (include/kantts_hip.h)."""
+    _fields_ = [("gx", c_void_p), ("whh", c_void_p * 2), ("bhh", c_void_p * 2), ("out", c_void_p), ("gates_save", c_void_p),
+                ("c_save", c_void_p), ("dout", c_void_p), ("dgates", c_void_p)]
+
+
+class FsmnDropArgs(Structure):
+    """kantts_fsmn_drop_args (include/kantts_hip.h)."""
+    _fields_ = [("x", c_void_p), ("w", c_void_p), ("res", c_void_p), ("y", c_void_p), ("dym", c_void_p), ("p1", c_float),
+                ("p2", c_float), ("seed1", c_uint64), ("seed2", c_uint64)]
+
+
 class LnBwdArgs(Structure):
     """kantts_lnbwd_args (include/kantts_hip.h)."""
     _fields_ = [
@@ -567,6 +579,13 @@ def lib():
             L.kantts_spk_conv1d.argtypes = [p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, i, i, i, p]
             L.kantts_spk_cam_gate_conv.argtypes = [p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, i, i, p]
             L.kantts_spk_tail.argtypes = [p, p, p, p, p, p, p, p, i, i, i, i, i, p]
+        if all(hasattr(L, s) for s in PREDICTOR_PAIR_SYMBOLS):  # predictor_pair_entry_points(): an older library still loads
+            L.kantts_bgemm_nt_pair.argtypes = [POINTER(BGemmArgs), POINTER(BGemmArgs), c_void_p]
+            L.kantts_ffn_pair2.argtypes = [POINTER(FfnArgs), POINTER(FfnArgs), c_void_p]
+            L.kantts_fsmn_memory_drop_fwd_pair.argtypes = [POINTER(FsmnDropArgs), POINTER(FsmnDropArgs), p, i, i, i, i, i, p, p]
+            L.kantts_fsmn_memory_drop_bwd_pair.argtypes = [POINTER(FsmnDropArgs), POINTER(FsmnDropArgs), p, i, i, i, i, i, p, p]
+            L.kantts_bilstm_pair_fwd.argtypes = [POINTER(BiLstmArgs), POINTER(BiLstmArgs), p, i, i, i, i, p]
+            L.kantts_bilstm_pair_bwd.argtypes = [POINTER(BiLstmArgs), POINTER(BiLstmArgs), p, i, i, i, i, p]
         _lib = L
     return _lib
 
@@ -576,6 +595,16 @@ FP_SYMBOLS = ("kantts_fp_head", "kantts_fp_head_bwd", "kantts_fp_plan", "kantts_
 
 SPK_SYMBOLS = ("kantts_kaldi_fbank", "kantts_spk_conv2d", "kantts_spk_conv1d", "kantts_spk_cam_gate_conv",
                "kantts_spk_tail")  # the speaker-embedding extractor (csrc/spk_embed.hip)
+
+PREDICTOR_PAIR_SYMBOLS = ("kantts_bgemm_nt_pair", "kantts_ffn_pair2", "kantts_fsmn_memory_drop_fwd_pair",
+                          "kantts_fsmn_memory_drop_bwd_pair", "kantts_bilstm_pair_fwd",
+                          "kantts_bilstm_pair_bwd")  # two problems of one shape per launch (the pitch / energy predictors)
+
+
+def predictor_pair_entry_points():
+    """True when the loaded library has the two-problem launches the paired pitch / energy predictors use."""
+    return all(hasattr(lib(), s) for s in PREDICTOR_PAIR_SYMBOLS)
+
 
 EXPORTED_SYMBOLS = [
     "kantts_abi_version", "kantts_target_arch", "kantts_gemm_seg_launch", "kantts_gemm_plan", "kantts_layernorm_fwd",
@@ -605,6 +634,7 @@ EXPORTED_SYMBOLS = [
     *FP_SYMBOLS,
     *SPK_SYMBOLS,
     "kantts_fsmn_memory_drop_fwd", "kantts_fsmn_memory_drop_bwd",
+    *PREDICTOR_PAIR_SYMBOLS,
 ]
 
 
@@ -822,38 +852,10 @@ def bgemm_nt(segs, M, N, c, ldc, *, T=0, b_kn=False, bias=None, bias2=None, alph
     ``lnb`` = (x, gamma, mean, rstd, dres | None, zero_rows | None, dx, dgamma, dbeta): the epilogue is the BACKWARD of a
     LayerNorm(128) whose output gradient is this contraction's result (kantts_bgemm_nt_lnbwd); ``c`` may then be None (the
     result itself is not stored) with ``c_bf16`` saying whether it is rounded to bf16 first, as the two-launch form would."""
-    g = BGemmArgs()
-    assert 1 <= len(segs) <= BGEMM_MAX_SEG
+    g = _bgemm_nt_args(segs, M, N, c, ldc, T=T, b_kn=b_kn, bias=bias, bias2=bias2, alpha=alpha, relu=relu, drop_p=drop_p,
+                       drop_seed=drop_seed, res=res, ldr=ldr, gate=gate, ldg=ldg, rowmask=rowmask, a_drop_p=a_drop_p,
+                       a_drop_seed=a_drop_seed, a_drop_ld=a_drop_ld, ln=ln, lnb=lnb, c_bf16=c_bf16)
     a0 = segs[0][0][0] if isinstance(segs[0][0], tuple) else segs[0][0]
-    for k, (a, lda, b, ldb, klen, a_shift) in enumerate(segs):
-        at = a[0] if isinstance(a, tuple) else a
-        bt = b[0] if isinstance(b, tuple) else b
-        if at.dtype != a0.dtype or bt.dtype != torch.bfloat16:
-            raise TypeError("bgemm_nt: mixed A dtypes or a non-bf16 B operand")
-        s = g.seg[k]
-        s.a, s.b, s.lda, s.ldb, s.klen, s.a_shift = _addr(a), _addr(b), int(lda), int(ldb), int(klen), int(a_shift)
-    g.nseg, g.M, g.N, g.T = len(segs), int(M), int(N), int(T)
-    g.a_f32, g.b_kn = int(a0.dtype == torch.float32), int(bool(b_kn))
-    if c is None:
-        assert lnb is not None and c_bf16 is not None
-        g.c, g.ldc, g.c_bf16 = None, int(ldc), int(bool(c_bf16))
-    else:
-        g.c, g.ldc, g.c_bf16 = _addr(c), int(ldc), int((c[0] if isinstance(c, tuple) else c).dtype == torch.bfloat16)
-    g.relu = int(bool(relu))
-    g.bias, g.bias2 = ptr(bias, torch.float32), ptr(bias2, torch.float32)
-    g.alpha, g.drop_p, g.drop_seed = float(alpha), float(drop_p), int(drop_seed)
-    g.res, g.ldr = ptr(res, torch.float32), int(ldr)
-    if gate is not None:
-        g.gate, g.ldg, g.gate_bf16 = ptr(gate), int(ldg), int(gate.dtype == torch.bfloat16)
-    g.a_drop_p, g.a_drop_seed, g.a_drop_ld = float(a_drop_p), int(a_drop_seed), int(a_drop_ld)
-    g.rowmask = ptr(rowmask)
-    if ln is not None:
-        gamma, beta, eps, ln_out, ln_mean, ln_rstd = ln
-        g.ln_gamma, g.ln_beta, g.ln_eps = ptr(gamma, torch.float32), ptr(beta, torch.float32), float(eps)
-        g.ln_out, g.ln_out_bf16 = ptr(ln_out), int(ln_out.dtype == torch.bfloat16)
-        g.ln_mean, g.ln_rstd = ptr(ln_mean, torch.float32), ptr(ln_rstd, torch.float32)
-    dev = a0.device
-    g.seed_dev = rng_ptr(dev) if (drop_p > 0 or a_drop_p > 0) else None
     if _profile is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -893,6 +895,56 @@ def bgemm_nt(segs, M, N, c, ldc, *, T=0, b_kn=False, bias=None, bias2=None, alph
     return True
 
 
+def bgemm_nt_pair(first, second):
+    """Two bgemm_nt problems in one launch (kantts_bgemm_nt_pair): ``first`` / ``second`` are (segs, M, N, c, ldc, kwargs) as
+    bgemm_nt takes them (no ``lnb``).  Returns False when the library declines (unequal M / N / operand forms): nothing ran."""
+    ga, gb = (_bgemm_nt_args(*pr[:5], **pr[5]) for pr in (first, second))
+    rc = lib().kantts_bgemm_nt_pair(ctypes.byref(ga), ctypes.byref(gb), stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "bgemm_nt_pair")
+    return True
+
+
+def _bgemm_nt_args(segs, M, N, c, ldc, *, T=0, b_kn=False, bias=None, bias2=None, alpha=1.0, relu=False, drop_p=0.0,
+                   drop_seed=0, res=None, ldr=0, gate=None, ldg=0, rowmask=None, a_drop_p=0.0, a_drop_seed=0, a_drop_ld=0,
+                   ln=None, lnb=None, c_bf16=None):
+    """The kantts_bgemm_args of a bgemm_nt call."""
+    g = BGemmArgs()
+    assert 1 <= len(segs) <= BGEMM_MAX_SEG
+    a0 = segs[0][0][0] if isinstance(segs[0][0], tuple) else segs[0][0]
+    for k, (a, lda, b, ldb, klen, a_shift) in enumerate(segs):
+        at = a[0] if isinstance(a, tuple) else a
+        bt = b[0] if isinstance(b, tuple) else b
+        if at.dtype != a0.dtype or bt.dtype != torch.bfloat16:
+            raise TypeError("bgemm_nt: mixed A dtypes or a non-bf16 B operand")
+        s = g.seg[k]
+        s.a, s.b, s.lda, s.ldb, s.klen, s.a_shift = _addr(a), _addr(b), int(lda), int(ldb), int(klen), int(a_shift)
+    g.nseg, g.M, g.N, g.T = len(segs), int(M), int(N), int(T)
+    g.a_f32, g.b_kn = int(a0.dtype == torch.float32), int(bool(b_kn))
+    if c is None:
+        assert lnb is not None and c_bf16 is not None
+        g.c, g.ldc, g.c_bf16 = None, int(ldc), int(bool(c_bf16))
+    else:
+        g.c, g.ldc, g.c_bf16 = _addr(c), int(ldc), int((c[0] if isinstance(c, tuple) else c).dtype == torch.bfloat16)
+    g.relu = int(bool(relu))
+    g.bias, g.bias2 = ptr(bias, torch.float32), ptr(bias2, torch.float32)
+    g.alpha, g.drop_p, g.drop_seed = float(alpha), float(drop_p), int(drop_seed)
+    g.res, g.ldr = ptr(res, torch.float32), int(ldr)
+    if gate is not None:
+        g.gate, g.ldg, g.gate_bf16 = ptr(gate), int(ldg), int(gate.dtype == torch.bfloat16)
+    g.a_drop_p, g.a_drop_seed, g.a_drop_ld = float(a_drop_p), int(a_drop_seed), int(a_drop_ld)
+    g.rowmask = ptr(rowmask)
+    if ln is not None:
+        gamma, beta, eps, ln_out, ln_mean, ln_rstd = ln
+        g.ln_gamma, g.ln_beta, g.ln_eps = ptr(gamma, torch.float32), ptr(beta, torch.float32), float(eps)
+        g.ln_out, g.ln_out_bf16 = ptr(ln_out), int(ln_out.dtype == torch.bfloat16)
+        g.ln_mean, g.ln_rstd = ptr(ln_mean, torch.float32), ptr(ln_rstd, torch.float32)
+    dev = a0.device
+    g.seed_dev = rng_ptr(dev) if (drop_p > 0 or a_drop_p > 0) else None
+    return g
+
+
 def ffn_pair(x, w1, w2, y, *, M, T, F, KT=1, pad=0, bias1=None, bias2=None, relu=False, alpha1=1.0, drop1_p=0.0,
              drop1_seed=0, drop2_p=0.0, drop2_seed=0, xdrop_p=0.0, xdrop_seed=0, gate=None, rowmask1=None, rowmask2=None,
              xrowmask=None, t_out=None, res=None, KT2=1, s2_first=0, s2_step=0, ln=None):
@@ -902,6 +954,44 @@ def ffn_pair(x, w1, w2, y, *, M, T, F, KT=1, pad=0, bias1=None, bias2=None, relu
     intermediate, y[m] = sum_t t[m + s2_first + t*s2_step] . w2[t]^T with w2 = three (128, F) images.  The FSMN
     feed-forward shapes (x (M, 256), F = 512, y (M, 256); x (M, 128), F = 256, y (M, 128)) are taken with KT = KT2 = 1 and
     without ln / xdrop / row masks; t_out may be None in the forward form.  Returns False when the library declines."""
+    g = _ffn_args(x, w1, w2, y, M=M, T=T, F=F, KT=KT, pad=pad, bias1=bias1, bias2=bias2, relu=relu, alpha1=alpha1,
+                  drop1_p=drop1_p, drop1_seed=drop1_seed, drop2_p=drop2_p, drop2_seed=drop2_seed, xdrop_p=xdrop_p,
+                  xdrop_seed=xdrop_seed, gate=gate, rowmask1=rowmask1, rowmask2=rowmask2, xrowmask=xrowmask, t_out=t_out,
+                  res=res, KT2=KT2, s2_first=s2_first, s2_step=s2_step, ln=ln)
+    NY = int(y.shape[-1])
+    if _profile is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    rc = lib().kantts_ffn_pair(ctypes.byref(g), stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "ffn_pair")
+    if _profile is not None:
+        e1.record()
+        fl = 2.0 * M * F * (x.shape[-1] * KT + NY * KT2)
+        _profile.append((e0, e1, fl))
+        # x + hidden tile (written forward / read as the gate and written as dz backward) + residual / output + weights
+        nb = M * (x.shape[-1] * x.element_size() + F * 2 * (2 if gate is not None else 1) + NY * 4 * (2 if res is not None else 1)) \
+            + 2 * F * (x.shape[-1] * KT + NY * KT2)
+        _profile_families.append(("ffn_pair", e0, e1, fl, float(nb)))
+    return True
+
+
+def ffn_pair2(first, second):
+    """Two ffn_pair problems of the (128, 128, 256) geometry in one launch (kantts_ffn_pair2): ``first`` / ``second`` are
+    ((x, w1, w2, y), kwargs) as ffn_pair takes them.  Returns False when the library declines: nothing ran."""
+    ga, gb = (_ffn_args(*pr[0], **pr[1]) for pr in (first, second))
+    rc = lib().kantts_ffn_pair2(ctypes.byref(ga), ctypes.byref(gb), stream())
+    if rc == E_UNSUPPORTED:
+        return False
+    check(rc, "ffn_pair2")
+    return True
+
+
+def _ffn_args(x, w1, w2, y, *, M, T, F, KT=1, pad=0, bias1=None, bias2=None, relu=False, alpha1=1.0, drop1_p=0.0,
+              drop1_seed=0, drop2_p=0.0, drop2_seed=0, xdrop_p=0.0, xdrop_seed=0, gate=None, rowmask1=None, rowmask2=None,
+              xrowmask=None, t_out=None, res=None, KT2=1, s2_first=0, s2_step=0, ln=None):
+    """The kantts_ffn_args of an ffn_pair call."""
     g = FfnArgs()
     g.x, g.ldx, g.x_f32 = ptr(x), int(x.shape[-1]), int(x.dtype == torch.float32)
     NY = int(y.shape[-1])
@@ -923,22 +1013,7 @@ def ffn_pair(x, w1, w2, y, *, M, T, F, KT=1, pad=0, bias1=None, bias2=None, relu
         g.ln_gamma, g.ln_beta, g.ln_eps = ptr(gamma, torch.float32), ptr(beta, torch.float32), float(eps)
         g.ln_out, g.ln_out_bf16 = ptr(ln_out), int(ln_out.dtype == torch.bfloat16)
         g.ln_mean, g.ln_rstd = ptr(ln_mean, torch.float32), ptr(ln_rstd, torch.float32)
-    if _profile is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = lib().kantts_ffn_pair(ctypes.byref(g), stream())
-    if rc == E_UNSUPPORTED:
-        return False
-    check(rc, "ffn_pair")
-    if _profile is not None:
-        e1.record()
-        fl = 2.0 * M * F * (x.shape[-1] * KT + NY * KT2)
-        _profile.append((e0, e1, fl))
-        # x + hidden tile (written forward / read as the gate and written as dz backward) + residual / output + weights
-        nb = M * (x.shape[-1] * x.element_size() + F * 2 * (2 if gate is not None else 1) + NY * 4 * (2 if res is not None else 1)) \
-            + 2 * F * (x.shape[-1] * KT + NY * KT2)
-        _profile_families.append(("ffn_pair", e0, e1, fl, float(nb)))
-    return True
+    return g
 
 
 def pnca_block_fwd(x, xn, hkv, ldh, B, L, *, lens, bw_dev, bw_x, bw_h, rowmask, wqkv, bqkv, wfcx, wfch, bfcx, bfch, ln1, w1, w2,

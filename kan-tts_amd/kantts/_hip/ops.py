@@ -1116,6 +1116,132 @@ def lstm(xs, params, lens_i32=None):
     return _LSTM.apply(len(xs), ndir, lens_i32, *xs, *params)
 
 
+class _BiLSTM2(torch.autograd.Function):
+    """TWO bidirectional layers of one shape over the same lengths (the pitch and the energy predictor's BiLSTMs), bf16
+    mode: every launch of _LSTM issued once for both -- the input projection of a direction (kantts_bgemm_nt_pair), the
+    recurrence (kantts_bilstm_pair_fwd / _bwd: four workgroups per sequence instead of two launches of two) and each
+    direction's share of the input gradient.  The recurrent weights go to the kernel as pointers, not
+    stacked.  Per problem the bits are those of its own _LSTM node; the weight gradients are queued as there.
+    params: the eight tensors of the first layer (forward direction, then reverse), then of the second."""
+
+    @staticmethod
+    def forward(ctx, lens, xa, xb, *params):
+        import ctypes
+
+        from . import BiLstmArgs
+
+        xs = [_c(xa), _c(xb)]
+        pr = [list(params[:8]), list(params[8:])]
+        B, T, K = xs[0].shape
+        H = pr[0][1].shape[1]
+        G, M = 4 * H, B * T
+        dev = xs[0].device
+        gxs = [torch.empty((M, 2 * G), device=dev, dtype=torch.float32) for _ in xs]
+        wbs = [[ops_bf16.bf16_weight(p[4 * d]) for d in range(2)] for p in pr]
+        for d in range(2):
+            if not ops_bf16.bgemm_nt_pair(*(([(x, K, (wb[d], 0), K, K, 0)], M, G, (gx, d * G), 2 * G, dict(bias=p[4 * d + 2]))
+                                            for x, wb, gx, p in zip(xs, wbs, gxs, pr))):
+                raise RuntimeError("bgemm_nt_pair declined the LSTM input projections")
+        outs = [torch.empty((B, T, 2 * H), device=dev, dtype=torch.float32) for _ in xs]
+        gates = [torch.empty((2, B, T, G), device=dev, dtype=torch.float32) for _ in xs]
+        csts = [torch.empty((2, B, T, H), device=dev, dtype=torch.float32) for _ in xs]
+        args = []
+        for gx, p, out, gt, cst in zip(gxs, pr, outs, gates, csts):
+            a = BiLstmArgs()
+            a.gx, a.out, a.gates_save, a.c_save = ptr(gx), ptr(out), ptr(gt), ptr(cst)
+            for d in range(2):
+                a.whh[d], a.bhh[d] = ptr(p[4 * d + 1], torch.float32), ptr(p[4 * d + 3], torch.float32)
+            args.append(a)
+        check(lib().kantts_bilstm_pair_fwd(ctypes.byref(args[0]), ctypes.byref(args[1]), ptr(lens), B, T, H, 1, stream()),
+              "bilstm_pair_fwd")
+        ctx.cfg = (B, T, H, K)
+        ctx.save_for_backward(lens, *xs, *outs, *gates, *csts, *params, *wbs[0], *wbs[1])
+        return outs[0], outs[1]
+
+    @staticmethod
+    def backward(ctx, *douts):
+        import ctypes
+
+        from . import BiLstmArgs, deferred_tn
+
+        B, T, H, K = ctx.cfg
+        G, M = 4 * H, B * T
+        sv = ctx.saved_tensors
+        lens, xs, outs, gates, csts = sv[0], sv[1:3], sv[3:5], sv[5:7], sv[7:9]
+        pr, wbs = [sv[9:17], sv[17:25]], [sv[25:27], sv[27:29]]
+        douts = [_c(d) for d in douts]
+        dev = douts[0].device
+        dgs = [torch.empty((2, B, T, G), device=dev, dtype=torch.float32) for _ in xs]
+        args = []
+        for dout, p, gt, cst, dg in zip(douts, pr, gates, csts, dgs):
+            a = BiLstmArgs()
+            a.dout, a.gates_save, a.c_save, a.dgates = ptr(dout, torch.float32), ptr(gt), ptr(cst), ptr(dg)
+            for d in range(2):
+                a.whh[d] = ptr(p[4 * d + 1], torch.float32)
+            args.append(a)
+        check(lib().kantts_bilstm_pair_bwd(ctypes.byref(args[0]), ctypes.byref(args[1]), ptr(lens), B, T, H, 1, stream()),
+              "bilstm_pair_bwd")
+        need_dx = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dxs = [torch.empty_like(x) if need_dx else None for x in xs]
+        # dx = dg_fwd W_ih_fwd + dg_rev W_ih_rev as in _LSTM.backward: the reverse direction's launch adds onto the forward
+        # direction's result (read as the fp32 residual), each launch for both problems.  (One launch with a K segment per
+        # direction sums in another order: the shared input's gradient then differs from the separate calls' in the last bit,
+        # and the bf16 roundings upstream turn that into 1.7e-4 rel-L2 of the step's gradients --
+        # profiles/predictor_pair_dump_outputs_parent_vs_change.txt.)
+        for d in range(2 if need_dx else 0):
+            kw = dict(b_kn=True) if d == 0 else None
+            if not ops_bf16.bgemm_nt_pair(*(([(dg[d].view(M, G), G, (wb[d], 0), K, G, 0)], M, K, dx, K,
+                                             kw or dict(b_kn=True, res=dx, ldr=K)) for dg, wb, dx in zip(dgs, wbs, dxs))):
+                raise RuntimeError("bgemm_nt_pair declined the LSTM input gradients")
+        dparams = []
+        for x, out, p, dg in zip(xs, outs, pr, dgs):
+            for d in range(2):
+                dgd = dg[d].view(M, G)
+                dw_ih = gzeros_like(p[4 * d])
+                db = gzeros((G,), dev)
+                with wgrad_overlap.side(dgd, x):
+                    if not bgemm_tn(dgd, G, x, K, M, G, K, (dw_ih, 0), K, 1, db=db):
+                        raise RuntimeError("bgemm_tn declined the LSTM input-weight gradient")
+                dw_hh = gzeros((G, H), dev)
+                shift = 1 if d == 1 else -1  # h_{prev}: previous step in this direction's time order
+                with wgrad_overlap.side(dgd, out):
+                    if not bgemm_tn(dgd, G, (out, d * H), 2 * H, M, G, H, dw_hh, H, 1, T=T, shift0=shift):
+                        raise RuntimeError("bgemm_tn declined the LSTM recurrent-weight gradient")
+                # b_ih and b_hh share one gradient (see deferred_tn.shared_gradient)
+                dparams += [dw_ih, dw_hh, db, deferred_tn.shared_gradient(db)]
+        return (None, dxs[0], dxs[1], *dparams)
+
+
+def _env_is_zero(name):
+    """The library's reading of its A/B switches: set, and atoi() of it is 0."""
+    v = os.environ.get(name)
+    if v is None:
+        return False
+    try:
+        return int(v.strip() or 0) == 0
+    except ValueError:
+        return True
+
+
+def bilstm2_eligible(xs, params_a, params_b):
+    """Can _BiLSTM2 take the two layers?  bf16 mode, equal fp32 inputs (B, T, K) with K % 8 == 0, H = 128, contiguous
+    fp32 parameters of equal shapes, a library with the pair entry points."""
+    from . import predictor_pair_entry_points
+
+    xa, xb = xs
+    return (get_precision() == "bf16" and len(params_a) == 8 and len(params_b) == 8 and xa.dim() == 3
+            and xa.shape == xb.shape and xa.dtype == xb.dtype == torch.float32 and xa.numel() > 0 and xa.shape[-1] % 8 == 0
+            and all(p.shape == q.shape and p.dtype == q.dtype == torch.float32 and p.is_contiguous() and q.is_contiguous()
+                    for p, q in zip(params_a, params_b))
+            and params_a[1].shape == (512, 128) and predictor_pair_entry_points()
+            and not _env_is_zero("KANTTS_LSTM_PAIR") and not _env_is_zero("KANTTS_LSTM_PAIR_BWD"))
+
+
+def bilstm2(xs, params_a, params_b, lens_i32=None):
+    """lstm() for two BiLSTMs of one shape at once (bilstm2_eligible): returns (out_a, out_b)."""
+    return _BiLSTM2.apply(lens_i32, xs[0], xs[1], *params_a, *params_b)
+
+
 # ================================================================================================
 # Embedding gather-sum
 # ================================================================================================
@@ -1431,6 +1557,75 @@ def fsmn_memory_drop(x, w, lens_i64, left_pad, p1=0.0, p2=0.0, res=None, res_gra
             and fsmn_memory_drop_entry_points()):
         return _FsmnMemoryDrop.apply(x, w, res, lens_i64, left_pad, float(p1), float(p2), res_grad)
     return dropout2_add(fsmn_memory(x, w, lens_i64, left_pad), p1, p2, res, res_grad=res_grad)
+
+
+def _fsmn_drop_args(x, w, res, y, dym, p1, s1, p2, s2):
+    from . import FsmnDropArgs
+
+    a = FsmnDropArgs()
+    a.x, a.w, a.res, a.y, a.dym = ptr(x, torch.float32), ptr(w, torch.float32), ptr(res, torch.float32), ptr(y), ptr(dym)
+    a.p1, a.p2, a.seed1, a.seed2 = float(p1), float(p2), int(s1), int(s2)
+    return a
+
+
+class _FsmnMemoryDrop2(torch.autograd.Function):
+    """_FsmnMemoryDrop for TWO memory blocks of one shape over the same lengths (the same layer of the pitch and of the
+    energy predictor): kantts_fsmn_memory_drop_fwd_pair / _bwd_pair, one launch each way for both.  Seeds are handed in
+    (drawn by the caller in the unpaired order); per problem the bits are those of its own _FsmnMemoryDrop node.  The
+    filter gradients stay one launch per problem on the weight-gradient stream."""
+
+    @staticmethod
+    def forward(ctx, lens, lp, cfgs, res_grads, ca, wa, ra, cb, wb, rb):
+        import ctypes
+
+        from . import rng_ptr
+
+        cs, ws = [_c(ca), _c(cb)], [_c(wa), _c(wb)]
+        rs = [None if r is None else _c(r) for r in (ra, rb)]
+        B, T, C = cs[0].shape
+        K = ws[0].shape[-1]
+        ys = [torch.empty_like(c) for c in cs]
+        a, b = (_fsmn_drop_args(c, w, r, y, None, *cfg) for c, w, r, y, cfg in zip(cs, ws, rs, ys, cfgs))
+        check(lib().kantts_fsmn_memory_drop_fwd_pair(ctypes.byref(a), ctypes.byref(b), ptr(lens), B, T, C, K, int(lp),
+                                                     rng_ptr(cs[0].device), stream()), "fsmn_memory_drop_fwd_pair")
+        ctx.save_for_backward(lens, *cs, *ws)
+        ctx.cfg = (B, T, C, K, int(lp), cfgs, [r is not None for r in rs])
+        ctx.res_grads = [tok if (r is not None and tok is not None and tok.armed) else None for r, tok in zip(rs, res_grads)]
+        return ys[0], ys[1]
+
+    @staticmethod
+    def backward(ctx, dya, dyb):
+        import ctypes
+
+        from . import rng_ptr
+
+        lens, ca, cb, wa, wb = ctx.saved_tensors
+        B, T, C, K, lp, cfgs, has_res = ctx.cfg
+        cs, ws, dys = [ca, cb], [wa, wb], [_c(dya), _c(dyb)]
+        dxs, dyms = [torch.empty_like(c) for c in cs], [torch.empty_like(c) for c in cs]
+        a, b = (_fsmn_drop_args(dy, w, None, dx, dym, *cfg) for dy, w, dx, dym, cfg in zip(dys, ws, dxs, dyms, cfgs))
+        check(lib().kantts_fsmn_memory_drop_bwd_pair(ctypes.byref(a), ctypes.byref(b), ptr(lens), B, T, C, K, lp,
+                                                     rng_ptr(dys[0].device), stream()), "fsmn_memory_drop_bwd_pair")
+        out = []
+        for i, (c, w, dy, dx, dym) in enumerate(zip(cs, ws, dys, dxs, dyms)):
+            dw = gzeros_like(w)  # (must NOT be in the keep-alive list: see _FsmnMemory.backward)
+            ws_n = int(lib().kantts_fsmn_dwconv_bwd_ws(B, T, C, K))
+            wsp = torch.empty(max(ws_n, 1), device=dy.device, dtype=torch.float32)
+            with wgrad_overlap.side(dym, c, wsp):
+                check(lib().kantts_fsmn_dwconv_bwd(ptr(dym), ptr(c), ptr(w), ptr(lens), None, ptr(dw), ptr(wsp), ws_n, B, T, C,
+                                                   K, lp, stream()), "fsmn_dwconv_bwd (dw)")
+            d_res = dy if has_res[i] and ctx.needs_input_grad[6 + 3 * i] else None  # the UNMASKED dy
+            if d_res is not None and ctx.res_grads[i] is not None:
+                ctx.res_grads[i].dres, d_res = d_res, None
+            out += [dx, dw, d_res]
+        return (None, None, None, None, *out)
+
+
+def fsmn_memory_drop2(xs, ws, lens_i64, left_pad, cfgs, ress=(None, None), res_grads=(None, None)):
+    """fsmn_memory_drop for two blocks of one shape at once (fp32, K = 41, equal shapes; the caller checked
+    predictor_pair_entry_points()).  cfgs: (p1, seed1, p2, seed2) per problem.  Returns (ya, yb)."""
+    return _FsmnMemoryDrop2.apply(lens_i64, int(left_pad), [tuple(c) for c in cfgs], list(res_grads), xs[0], ws[0], ress[0],
+                                  xs[1], ws[1], ress[1])
 
 
 # ================================================================================================
@@ -2610,13 +2805,16 @@ class _Dropout2Add(torch.autograd.Function):
     ``res_grad``: an armed ops_bf16.ResGradToken receives the residual's gradient instead of autograd."""
 
     @staticmethod
-    def forward(ctx, x, res, p1, p2, res_grad=None):
+    def forward(ctx, x, res, p1, p2, res_grad=None, seeds=None):
         from . import rng_ptr
 
         x = _c(x)
         y = torch.empty_like(x)
-        s1 = next_seed() if p1 > 0 else 0
-        s2 = next_seed() if p2 > 0 else 0
+        if seeds is None:
+            s1 = next_seed() if p1 > 0 else 0
+            s2 = next_seed() if p2 > 0 else 0
+        else:  # drawn by the caller (adaptors.paired_nar_predictors keeps each predictor's draw order)
+            s1, s2 = seeds
         r = None if res is None else _c(res)
         check(lib().kantts_dropout2_add(ptr(x, torch.float32), ptr(r, torch.float32), ptr(y), x.numel(), float(p1), s1,
                                         float(p2), s2, rng_ptr(x.device), stream()), "dropout2_add")
@@ -2639,11 +2837,12 @@ class _Dropout2Add(torch.autograd.Function):
         if d_res is not None and ctx.res_grad is not None:
             # the contraction that reads the same tensor adds it in its input-gradient launch (ResGradToken)
             ctx.res_grad.dres, d_res = d_res, None
-        return dx, d_res, None, None, None
+        return dx, d_res, None, None, None, None
 
 
-def dropout2_add(x, p1=0.0, p2=0.0, res=None, res_grad=None):
-    """dropout_{p2}(dropout_{p1}(x)) (+ res) in one pass (fp32, numel % 4 == 0); plain add / identity when both p are 0."""
+def dropout2_add(x, p1=0.0, p2=0.0, res=None, res_grad=None, seeds=None):
+    """dropout_{p2}(dropout_{p1}(x)) (+ res) in one pass (fp32, numel % 4 == 0); plain add / identity when both p are 0.
+    ``seeds``: (seed1, seed2) drawn by the caller instead of here (the fused kernel only)."""
     if p1 <= 0.0 and p2 <= 0.0:
         return x if res is None else x + res
     if x.dtype != torch.float32 or x.numel() % 4 or (res is not None and (res.shape != x.shape or res.dtype != x.dtype)):
@@ -2651,7 +2850,7 @@ def dropout2_add(x, p1=0.0, p2=0.0, res=None, res_grad=None):
 
         y = F.dropout(F.dropout(x, p1, True), p2, True)
         return y if res is None else y + res
-    return _Dropout2Add.apply(x, res, float(p1), float(p2), res_grad)
+    return _Dropout2Add.apply(x, res, float(p1), float(p2), res_grad, seeds)
 
 
 def sin_add(x, act_slope=None):

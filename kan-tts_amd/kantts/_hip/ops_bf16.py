@@ -16,13 +16,16 @@ import weakref
 
 import torch
 
-from . import bgemm_nt, bgemm_tn, check, ffn_pair, lib, pnca_block_bwd, pnca_block_fwd, ptr, rows_sum_accum, stream
+from . import (bgemm_nt, bgemm_nt_pair, bgemm_tn, check, ffn_pair, ffn_pair2, lib, pnca_block_bwd, pnca_block_fwd, ptr,
+               rows_sum_accum, stream)
 
 BF16 = torch.bfloat16
 _wcache = {}
 # the feed-forward pair as one launch (csrc/ffn_pair.hip); KANTTS_NO_FFN_PAIR=1 keeps the two-launch form (A/B runs)
 # ``fsmn``: the FSMN feed-forward nets (kantts/models/sambert/fsmn.py) through the same launch (tests, A/B runs)
-PAIR = {"on": os.environ.get("KANTTS_NO_FFN_PAIR", "") == "", "fsmn": True}
+# ``predictors``: the pitch and the energy predictor stage by stage in lockstep, one launch per stage for both
+# (kantts/models/sambert/adaptors.py paired_nar_predictors; tests, A/B runs)
+PAIR = {"on": os.environ.get("KANTTS_NO_FFN_PAIR", "") == "", "fsmn": True, "predictors": True}
 # (input width, output width, hidden width) of the FSMN feed-forward nets csrc/ffn_pair.hip is instantiated for: the
 # postnet's and the pitch / energy predictors' layers behind the first (k = 1 both ways)
 FSMN_PAIR_SHAPES = ((256, 256, 512), (128, 128, 256))
@@ -1226,3 +1229,113 @@ def fsmn_ffn(x, w1, b1, w2, *, p=0.0, res_grad=None):
     if pair:
         wf1, wf2, wt2, wt1 = ffn_frag_weights(w1, w2)
     return _FusedFsmnFFNB.apply(x, w1, b1, w2, bf16_weight(w1), bf16_weight(w2), wf1, wf2, wt2, wt1, cfg)
+
+
+class _FusedFsmnFFNB2(torch.autograd.Function):
+    """TWO feed-forward nets of one shape over the same number of rows -- the same layer of the pitch and of the energy
+    predictor -- as one node whose launches each serve both: kantts_ffn_pair2 at the shape csrc/ffn_pair.hip has, else
+    kantts_bgemm_nt_pair.  Per problem the arithmetic, the seed (handed in: see adaptors.paired_nar_predictors) and the
+    deferred weight gradients are those of its own _FusedFsmnFFNB node, so outputs and input gradients are the same bits.
+    Inputs: the ten tensors of _FusedFsmnFFNB.forward for the first problem, then for the second."""
+
+    @staticmethod
+    def forward(ctx, cfgs, *t):
+        probs = [t[:10], t[10:]]
+        xs = [_c(pr[0]).detach() for pr in probs]
+        lead, C = xs[0].shape[:-1], xs[0].shape[-1]
+        M = int(math.prod(lead))
+        F, N = probs[0][1].shape[0], probs[0][3].shape[0]
+        dev = xs[0].device
+        hids = [torch.empty((M, F), device=dev, dtype=BF16) for _ in probs]
+        outs = [torch.empty((M, N), device=dev, dtype=torch.float32) for _ in probs]
+        pair = cfgs[0]["pair"] and cfgs[1]["pair"]
+        fused = pair and ffn_pair2(*(((x.view(M, C), pr[6], pr[7], out),
+                                      dict(M=M, T=M, F=F, bias1=pr[2], relu=True, drop1_p=cfg["p"], drop1_seed=cfg["seed"],
+                                           t_out=hid))
+                                     for x, pr, out, hid, cfg in zip(xs, probs, outs, hids, cfgs)))
+        if not fused:
+            if not bgemm_nt_pair(*(([(x, C, pr[4], C, C, 0)], M, F, hid, F,
+                                    dict(bias=pr[2], relu=True, drop_p=cfg["p"], drop_seed=cfg["seed"]))
+                                   for x, pr, hid, cfg in zip(xs, probs, hids, cfgs))):
+                raise RuntimeError("bgemm_nt_pair declined the FSMN up-projections")
+            if not bgemm_nt_pair(*(([(hid, F, pr[5], F, F, 0)], M, N, out, N, {}) for pr, hid, out in zip(probs, hids, outs))):
+                raise RuntimeError("bgemm_nt_pair declined the FSMN down-projections")
+        ctx.cfgs, ctx.dims, ctx.lead, ctx.pair = cfgs, (M, F, C, N), lead, pair
+        saved = []
+        for x, pr, hid in zip(xs, probs, hids):
+            saved += [x, hid, pr[4], pr[5], pr[8], pr[9]]
+        ctx.has_t = [pr[8] is not None and pr[9] is not None for pr in probs]
+        ctx.save_for_backward(*saved)
+        return outs[0].view(*lead, N), outs[1].view(*lead, N)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        from .ops import gzeros, wgrad_overlap
+
+        sv = ctx.saved_tensors
+        probs = [sv[:6], sv[6:]]  # (x, hid, wb1, wb2, wt2, wt1) each
+        M, F, C, N = ctx.dims
+        dev = dys[0].device
+        dys = [_c(dy).view(M, N) for dy in dys]
+        need_dx = ctx.needs_input_grad[1] or ctx.needs_input_grad[11]
+        a1s, dress = [], []
+        for cfg in ctx.cfgs:
+            a1s.append(1.0 / (1.0 - cfg["p"]) if cfg["p"] > 0 else 1.0)
+            rg = cfg.get("res_grad")
+            if rg is not None and rg.dres is not None and not need_dx:
+                raise RuntimeError("a residual gradient was handed to this net's input-gradient launch (ResGradToken), "
+                                   "which does not run")
+            dres = None
+            if rg is not None and rg.dres is not None:
+                dres, rg.dres = _c(rg.dres).view(M, C), None
+            dress.append(dres)
+        dzs = [torch.empty((M, F), device=dev, dtype=BF16) for _ in probs]
+        dxs = [torch.empty((M, C), device=dev, dtype=torch.float32) if need_dx else None for _ in probs]
+        fused = (ctx.pair and need_dx and all(ctx.has_t) and all(dy.dtype == torch.float32 for dy in dys)
+                 and ffn_pair2(*(((dy, pr[4], pr[5], dx), dict(M=M, T=M, F=F, alpha1=a1, gate=pr[1], t_out=dz, res=dres))
+                                 for dy, pr, dx, a1, dz, dres in zip(dys, probs, dxs, a1s, dzs, dress))))
+        if not fused and not bgemm_nt_pair(*(([(dy, N, pr[3], F, N, 0)], M, F, dz, F,
+                                              dict(b_kn=True, a_drop_ld=N, gate=pr[1], ldg=F, alpha=a1))
+                                             for dy, pr, dz, a1 in zip(dys, probs, dzs, a1s))):
+            raise RuntimeError("bgemm_nt_pair declined the FSMN hidden gradients")
+        dw2s = []
+        for dy, pr in zip(dys, probs):
+            dw2 = gzeros((N, F, 1), dev)
+            with wgrad_overlap.side(dy, pr[1]):
+                if not bgemm_tn(dy, N, pr[1], F, M, N, F, dw2, F, 1):
+                    raise RuntimeError("bgemm_tn declined dW2")
+            dw2s.append(dw2)
+        if not fused and need_dx:
+            if not bgemm_nt_pair(*(([(dz, F, pr[2], C, F, 0)], M, C, dx, C,
+                                    dict(b_kn=True, a_drop_ld=F, **(dict(res=dres, ldr=C) if dres is not None else {})))
+                                   for dz, pr, dx, dres in zip(dzs, probs, dxs, dress))):
+                raise RuntimeError("bgemm_nt_pair declined the FSMN input gradients")
+        grads = [None]
+        for dz, pr, dx, dw2 in zip(dzs, probs, dxs, dw2s):
+            dw1 = gzeros((F, C, 1), dev)
+            db1 = gzeros((F,), dev)
+            with wgrad_overlap.side(dz, pr[0]):
+                if not bgemm_tn(dz, F, pr[0], C, M, F, C, dw1, C, 1, db=db1):
+                    raise RuntimeError("bgemm_tn declined dW1")
+            grads += [dx.view(*ctx.lead, C) if need_dx else None, dw1, db1, dw2] + [None] * 6
+        return tuple(grads)
+
+
+def fsmn_ffn2(xs, nets, *, ps, seeds, res_grads=(None, None)):
+    """fsmn_ffn for two nets of one shape at once: xs two (..., C) fp32 tensors of equal shape, nets two (w1, b1, w2),
+    ps / seeds the dropout probability and the seed of each (drawn by the caller in the unpaired order).  Returns (ya, yb)."""
+    F, C, _ = nets[0][0].shape
+    N = nets[0][2].shape[0]
+    pair = PAIR["on"] and (C, N, F) in FSMN_PAIR_SHAPES
+    args, cfgs = [], []
+    for x, (w1, b1, w2), p, seed, tok in zip(xs, nets, ps, seeds, res_grads):
+        cfg = dict(p=float(p), pair=pair, save=True, seed=int(seed))
+        if tok is not None and x.dtype == torch.float32 and x.requires_grad and C % 4 == 0:
+            tok.armed = True
+            cfg["res_grad"] = tok
+        wf1 = wf2 = wt2 = wt1 = None
+        if pair:
+            wf1, wf2, wt2, wt1 = ffn_frag_weights(w1, w2)
+        args += [x, w1, b1, w2, bf16_weight(w1), bf16_weight(w2), wf1, wf2, wt2, wt1]
+        cfgs.append(cfg)
+    return _FusedFsmnFFNB2.apply(cfgs, *args)

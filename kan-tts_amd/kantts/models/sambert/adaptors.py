@@ -141,3 +141,74 @@ class VarFsmnRnnNARPredictor(nn.Module):
         x = ops.lstm(x, params, None if info is None else info.lens32)
         x = ops.linear(x, self.fc.weight, self.fc.bias, rowmask=None if info is None else info.mask).squeeze(-1)
         return x
+
+    def blstm_params(self):
+        return [getattr(self.blstm, n + sfx) for sfx in ("", "_reverse")
+                for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
+
+
+def _predictors_pairable(a, b, inputs):
+    """Can the two predictors run in lockstep (paired_nar_predictors)?  bf16 mode, training with dropout on, equal
+    hyper-parameters, and every stage at a shape the library's two-problem launches take."""
+    import kantts._hip as hip
+    from kantts._hip import ops_bf16
+    from kantts.models.sambert import fsmn as fsmn_mod
+
+    fa, fb = a.fsmn, b.fsmn
+    if not (ops_bf16.PAIR["predictors"] and hip.get_precision() == "bf16" and a.training and b.training
+            and torch.is_grad_enabled() and torch.is_tensor(inputs) and inputs.dim() == 3 and inputs.dtype == torch.float32
+            and inputs.numel() > 0 and inputs.numel() % 4 == 0):
+        return False
+    hyper = lambda f: (f.filter_size, f.fsmn_num_layers, f.num_memory_units, f.ffn_inner_dim, float(f.dropout), tuple(f.shift),  # noqa: E731
+                       f.ffn_lst[0].w_1.in_channels, tuple(float(m.dropout.p) for m in f.ffn_lst),
+                       tuple((m.lp, float(m.dropout.p)) for m in f.memory_block_lst))
+    if hyper(fa) != hyper(fb) or a.blstm.hidden_size != b.blstm.hidden_size or a.fc.weight.shape != b.fc.weight.shape:
+        return False
+    if not (float(fa.dropout) > 0 and fa.filter_size == 41 and fa.num_memory_units % 8 == 0 and inputs.shape[-1] % 8 == 0
+            and fsmn_mod._RES_GRAD_PORT and ops.FSMN_MEMORY_DROP["on"] and hip.predictor_pair_entry_points()):
+        return False
+    x = inputs
+    for na, nb in zip(fa.ffn_lst, fb.ffn_lst):
+        if not all(ops_bf16.fsmn_ffn_eligible(x, n.w_1.weight, n.w_1.bias, n.w_2.weight) for n in (na, nb)):
+            return False
+        x = torch.empty((*inputs.shape[:2], fa.num_memory_units), device="meta")  # a layer's output: only its shape matters
+    return ops.bilstm2_eligible((x, x), a.blstm_params(), b.blstm_params())
+
+
+def paired_nar_predictors(pitch, energy, inputs, masks=None):
+    """pitch(inputs, masks), energy(inputs, masks) -- two VarFsmnRnnNARPredictor of one configuration -- stage by stage in
+    LOCKSTEP: every stage of both (feed-forward net, memory block, BiLSTM recurrence and its projections) is one launch,
+    and each two-output autograd node receives both output gradients in one backward call, so the backward pass stays in
+    lockstep too.  The two are independent chains of ~14 small launches and a recurrence; a replayed graph runs them one
+    after the other.  Each predictor's dropout seeds are drawn up front in ITS order -- all of pitch's, then all of
+    energy's -- which is the order of the two separate calls: same masks, same bits.  Anything the paired launches do not
+    take (fp32 mode, eval, no dropout, unequal modules, an older library, PAIR["predictors"] off) runs the two calls."""
+    from kantts._hip import ops_bf16
+
+    if not _predictors_pairable(pitch, energy, inputs):
+        return pitch(inputs, masks), energy(inputs, masks)
+    info = SeqInfo.of(masks)
+    mods = (pitch, energy)
+    p = float(pitch.fsmn.dropout)
+    seeds = []  # per predictor: the input dropout's, then per layer the net's and the memory block's two
+    for m in mods:
+        draw = lambda q: ops.next_seed() if q > 0 else 0  # noqa: E731
+        s = [draw(p)]
+        for ffn, mem in zip(m.fsmn.ffn_lst, m.fsmn.memory_block_lst):
+            s += [draw(float(ffn.dropout.p)), draw(float(mem.dropout.p)), draw(p)]
+        seeds.append(s)
+    xs = [ops.dropout2_add(inputs, p, seeds=(s[0], 0)) for s in seeds]
+    lens64 = None if info is None else info.lens64
+    for l in range(len(pitch.fsmn.ffn_lst)):
+        ffns = [m.fsmn.ffn_lst[l] for m in mods]
+        mems = [m.fsmn.memory_block_lst[l] for m in mods]
+        same = pitch.fsmn.num_memory_units == xs[0].size(-1)
+        toks = [ops_bf16.ResGradToken() if same else None for _ in mods]
+        cs = ops_bf16.fsmn_ffn2(xs, [(n.w_1.weight, n.w_1.bias, n.w_2.weight) for n in ffns],
+                                ps=[float(n.dropout.p) for n in ffns], seeds=[s[1 + 3 * l] for s in seeds], res_grads=toks)
+        xs = ops.fsmn_memory_drop2(cs, [mb.conv_dw.weight for mb in mems], lens64, mems[0].lp,
+                                   [(float(mb.dropout.p), s[2 + 3 * l], p, s[3 + 3 * l]) for mb, s in zip(mems, seeds)],
+                                   ress=[x if same else None for x in xs], res_grads=toks)
+    hs = ops.bilstm2(xs, pitch.blstm_params(), energy.blstm_params(), None if info is None else info.lens32)
+    rowmask = None if info is None else info.mask
+    return tuple(ops.linear(h, m.fc.weight, m.fc.bias, rowmask=rowmask).squeeze(-1) for h, m in zip(hs, mods))

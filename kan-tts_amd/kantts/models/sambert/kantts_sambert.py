@@ -24,7 +24,8 @@ from kantts._hip import ops
 from kantts.models.sambert import FFTBlock, PNCABlock, Prenet
 from kantts.models.sambert.alignment import b_mas
 from kantts.models.sambert.attention import ConvAttention
-from kantts.models.sambert.adaptors import LengthRegulator, VarFsmnRnnNARPredictor, VarRnnARPredictor
+from kantts.models.sambert.adaptors import (LengthRegulator, VarFsmnRnnNARPredictor, VarRnnARPredictor,
+                                            paired_nar_predictors)
 from kantts.models.sambert.fsmn import FsmnEncoderV2
 from kantts.models.sambert.positions import DurSinusoidalPositionEncoder, SinusoidalPositionEncoder
 from kantts.models.utils import SeqInfo, get_mask_from_lengths
@@ -294,8 +295,8 @@ class VarianceAdaptor(nn.Module):
         pitch_predictions = energy_predictions = None
         if not late:
             with ops.side_branch.fork(variance_predictor_inputs, *(lens_keep or ())) if teacher else contextlib.nullcontext():
-                pitch_predictions = self.pitch_predictor(variance_predictor_inputs, info)
-                energy_predictions = self.energy_predictor(variance_predictor_inputs, info)
+                pitch_predictions, energy_predictions = paired_nar_predictors(self.pitch_predictor, self.energy_predictor,
+                                                                              variance_predictor_inputs, info)
         pitch_src = pitch_targets if pitch_targets is not None else pitch_predictions
         energy_src = energy_targets if energy_targets is not None else energy_predictions
         # text + Conv1d(1->32,k=9)(pitch) + Conv1d(1->32,k=9)(energy): two 9-tap GEMMs chained through the
@@ -325,8 +326,7 @@ class VarianceAdaptor(nn.Module):
                         vpi = variance_predictor_inputs if variance_predictor_inputs is not None else vp_inputs()
                         cond = (duration_predictor_cond if duration_predictor_cond is not None
                                 else torch.cat([aug, inputs_spk_embedding, inputs_emo_embedding], dim=-1))
-                        p_ = self.pitch_predictor(vpi, info)
-                        e_ = self.energy_predictor(vpi, info)
+                        p_, e_ = paired_nar_predictors(self.pitch_predictor, self.energy_predictor, vpi, info)
                         d_, _ = self.duration_predictor(prev, cond, masks=info)
                     return d_, p_, e_
 
