@@ -130,6 +130,62 @@ class _SymLayer:
                 self.pos[1 - p, :, 0].cpu().clone())
 
 
+def _check_neutral(device, prec, slots, Tc, case):
+    """kantts_sconv_sym_rows_launch with neutral settings (lag = delay = res_lag = 0, sub = 1, every end open, pos = 0)
+    against kantts_sconv_rows_launch on the same buffers: the two kernels include ONE tile loop (csrc/sconv_body.inc) and
+    the two entry points ask ONE tile picker (csrc/sconv_common.inc), so the live rows of out and the state are the same
+    bits -- no tolerance."""
+    import kantts._hip as hip
+
+    Cin, N, K, d = case
+    Hn = (K - 1) * d
+    g = torch.Generator().manual_seed(11)
+    bf = prec == "bf16" and N > 1
+    w = (torch.randn(K, N, Cin, generator=g) / (Cin * K) ** 0.5).to(torch.bfloat16 if bf else torch.float32).to(device)
+    bias = torch.randn(N, generator=g).to(device)
+    x = torch.randn(slots, Tc, Cin, generator=g).to(device)
+    res = torch.randn(slots, Tc, N, generator=g).to(device)
+    hist = torch.randn(slots, Hn, Cin, generator=g).to(device)
+    counts = [[Tc, Tc // 2, 0][s % 3] for s in range(slots)]
+    rows = torch.tensor(counts, dtype=torch.int32).to(device)
+    end = torch.full((slots,), -1, dtype=torch.int32).to(device)
+    pos = torch.zeros(slots, dtype=torch.int32).to(device)
+    kw = dict(S=slots, Tc=Tc, Cin=Cin, N=N, K=K, step=d, hist_ss=Hn * Cin, precision=_prec(hip, prec), bias=bias, res=res,
+              in_leaky=SLOPE, out_leaky=SLOPE, rows=rows, row_mul=1, zero_tail=N == 1)
+    got = []
+    for sym in (False, True):
+        out = torch.full((slots, Tc, N), SENTINEL).to(device)
+        st = torch.full((slots, Hn, Cin), SENTINEL).to(device)
+        if sym:
+            assert hip.sconv_sym(x, hist, st, w, out, end=end, pos_in=pos, lag=0, delay=0, sub=1, res_lag=0, **kw)
+        else:
+            assert hip.sconv(x, hist, st, w, out, **kw)
+        got.append((out.cpu(), st.cpu()))
+    (out_c, st_c), (out_s, st_s) = got
+    what = (case, prec, slots, Tc)
+    for s, n in enumerate(counts):
+        assert not bool((out_c[s, :n] == SENTINEL).any()), ("live rows were not written", what, s)
+        assert torch.equal(out_s[s, :n], out_c[s, :n]), ("live rows of out", what, s)
+    assert torch.equal(st_s, st_c), ("hist_out", what)
+
+
+# (Cin, N, K, dilation): the smallest; a partial 32-channel chunk, a second fp32 slab and a partial column fragment; a second
+# bf16 slab and the longest tap count; N == 1 (with zero_tail)
+_NEUTRAL = [(16, 16, 3, 1), (72, 40, 3, 7), (136, 48, 11, 3), (32, 1, 7, 1)]
+# (S, Tc, (Cin, N, K, dilation)): the wider column tiles.  At Tc = 8 the four waves sit side by side (WN = 4), so the
+# picker's blocks(nfr) = S * ceil(N / (64 * nfr)): S = 96, N = 512 gives blocks(4) = 192 < 384 <= blocks(2) = 384 (NFR = 2),
+# and S = 96, N = 1024 gives blocks(4) = 384 (NFR = 4)
+_NEUTRAL_WIDE = [(96, 8, (16, 512, 3, 1)), (96, 8, (16, 1024, 3, 1))]
+
+
+@pytest.mark.parametrize("Tc", [8, 40, 130])  # the three row-tile classes of the dispatcher
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+@pytest.mark.parametrize("case", _NEUTRAL, ids=lambda c: "_".join(map(str, c)))
+def test_sconv_sym_neutral_is_sconv_rows(case, prec, Tc):
+    with kernel_source_on_cpu():
+        _check_neutral("cpu", prec, S, Tc, case)
+
+
 def _check_layer(case, prec, sched, device, lag=0, with_res=False, late_end=False, stage=False):
     L = _SymLayer(case, prec, device, lag=lag, with_res=with_res, stage=stage)
     xs = [torch.randn(T, L.Cin, generator=L.gen) for T in LENS]
@@ -380,6 +436,16 @@ def test_sconv_sym_layer_gpu(prec):
     for case in _STAGES:
         for sched in _SCHEDULES:
             _check_layer(case, prec, sched, "cuda", stage=True, late_end=sched == "mixed")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_sconv_sym_neutral_is_sconv_rows_gpu(prec):
+    for case in _NEUTRAL:
+        for Tc in (8, 40, 130):
+            _check_neutral("cuda", prec, S, Tc, case)
+    for slots, Tc, case in _NEUTRAL_WIDE:
+        _check_neutral("cuda", prec, slots, Tc, case)
 
 
 @pytest.mark.gpu
