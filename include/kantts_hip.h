@@ -1776,6 +1776,18 @@ int kantts_mb_tail_rows(const kantts_mb_tail_args* args, void* stream);
  *   The output of sequence b is the first T' rows of: for p = 0, 1, ...: [3 rows of filler label[b, p] if p < T and it is
  *   > 0], text_hid[b, p mod T] -- rows past the end wrap to the start of the sequence, as the reference's padding does.
  *
+ * kantts_fp_plan_given: the same map from GIVEN labels at a GIVEN width W, for teacher-forced steps that must not read the
+ *   device (a captured step): there the labels come from the batch and T' is the width of the duration targets.  It takes
+ *   no counts: fp_number[b] = nins[b] = #(1 <= label[b, p] <= 3) over all T slots, padding included (what kantts_fp_head
+ *   with given labels counts); inter_len[b] = lens[b] + 3 fp_number[b]; meta[0] = the T' of these labels and lengths.
+ *   src, emo_out, spk_out are (B, W): ALL of columns [0, W) is written, the first W entries of the stream below and
+ *   emo[b, q mod T] / spk[b, q mod T] (a W > T' continues the wrap), and nothing at or past column W.  pos (B, T) as above:
+ *   places >= W mean "not in the output", which kantts_fp_insert_bwd with Tp = cap = W skips, so that call stays in
+ *   bounds for any labels.  meta[1 + b]: 0, or the sum of 2 (lens[b] outside [0, T]; clamped), 4 (a label outside [0, 3];
+ *   taken as 0) and 8 (FP_ERR_WIDTH, in EVERY word: T' != W -- the batch is inconsistent and the step's result is to be
+ *   discarded).  One launch, a workgroup per sequence; every workgroup counts the labels of all B rows for T'.
+ *   B, T, W >= 1; T <= 2^24, W <= 2^26.
+ *
  * kantts_fp_insert_fwd: out (B, Tp, C)[b, q] = src[b, q] >= 0 ? text_hid (B, T, C)[b, src] : fill (9, C)[-src - 1]; an entry
  *   outside [-9, T) gives a zero row.  Tp <= cap, else KANTTS_E_BADARG.
  * kantts_fp_insert_bwd: d_text_hid (B, T, C)[b, j] = sum of the rows of d_out (B, Tp, C) that hold token j (its place, then
@@ -1793,6 +1805,9 @@ int kantts_fp_head_bwd(const float* rows, const float* weight, const float* prob
 int kantts_fp_plan(const int32_t* label, const int32_t* lens, const int32_t* fp_number, const int64_t* emo, const int64_t* spk,
                    int32_t* inter_len, int32_t* meta, int32_t* src, int32_t* pos, int32_t* nins, int64_t* emo_out,
                    int64_t* spk_out, int B, int T, int cap, void* stream);
+int kantts_fp_plan_given(const int32_t* label, const int32_t* lens, const int64_t* emo, const int64_t* spk, int32_t* inter_len,
+                         int32_t* meta, int32_t* src, int32_t* pos, int32_t* nins, int64_t* emo_out, int64_t* spk_out,
+                         int32_t* fp_number, int B, int T, int W, void* stream);
 int kantts_fp_insert_fwd(const float* text_hid, const float* fill, const int32_t* src, float* out, int B, int T, int Tp, int cap,
                          int C, void* stream);
 int kantts_fp_insert_bwd(const float* d_out, const int32_t* src, const int32_t* pos, const int32_t* nins, float* d_text_hid,

@@ -11,6 +11,8 @@
 //   filler row k of token p at q = p + 3 E(p) + k, token p at q = p + 3 I(p), and q >= T + 3 N holds token (q - 3 N) mod T.
 // kantts_fp_plan forms that map once (src, and its inverse pos / nins for the backward); insert_fwd / insert_bwd are
 // gathers through it, so no atomics and equal bits on every run.
+// kantts_fp_plan_given forms the same map from GIVEN labels at a GIVEN width (teacher forcing, where T' is the width of the
+// duration targets): no host read at all, so a training step with it can be captured.
 //
 // Everything is fp32 with plain vector loads and stores; C % 4 == 0 (one float4 per lane along the channels).
 #include "common.h"
@@ -184,6 +186,72 @@ __global__ __launch_bounds__(FP_THREADS) void fp_head_bwd_kernel(const float* __
 #define FP_ERR_CAP 1      // cap < T'
 #define FP_ERR_LENGTH 2   // a length outside [0, T] or a negative count
 #define FP_ERR_LABEL 4    // a label outside [0, 3] (taken as 0)
+#define FP_ERR_WIDTH 8    // kantts_fp_plan_given: the T' of the labels is not the width the caller planned at
+
+// The tile scan both plans share: the labels of one row, FP_THREADS tokens at a time, into the map (columns < Tw only) and
+// its inverse.  Returns N, the labels > 0 of the row, in every thread.  s_tot: FP_WAVES ints of LDS.
+__device__ __forceinline__ int fp_scan_row(const int* __restrict__ lrow, int T, int Tw, int* __restrict__ srow,
+                                           int* __restrict__ prow, int* s_tot, int* flags) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int carry = 0;
+  for (int base = 0; base < T; base += FP_THREADS) {
+    const int p = base + tid;
+    int lab = p < T ? lrow[p] : 0;
+    if (lab < 0 || lab > 3) *flags |= FP_ERR_LABEL, lab = 0;
+    const int f = lab > 0;
+    int inc = f;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int v = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += v;
+    }
+    __syncthreads();  // s_tot of the previous tile has been read by everyone
+    if (lane == 63) s_tot[wv] = inc;
+    __syncthreads();
+    int woff = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < FP_WAVES; ++i) {
+      woff += i < wv ? s_tot[i] : 0;
+      tot += s_tot[i];
+    }
+    const int incl = carry + woff + inc, excl = incl - f;
+    if (p < T) {
+      const int q0 = p + 3 * excl, qt = p + 3 * incl;
+      if (f) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          if (q0 + k < Tw) srow[q0 + k] = -(1 + 3 * (lab - 1) + k);
+      }
+      if (qt < Tw) srow[qt] = p;
+      prow[p] = qt;
+    }
+    carry += tot;
+  }
+  return carry;
+}
+
+// the wrapped tail of the map (columns [T + 3 N, Tw)) and the extended ids of columns [0, Tw); row b of (B, cap) tensors
+__device__ __forceinline__ void fp_tail_and_ids(int* __restrict__ srow, const long long* __restrict__ emo,
+                                                const long long* __restrict__ spk, long long* __restrict__ emo_out,
+                                                long long* __restrict__ spk_out, int b, int T, int N, int Tw, int cap) {
+  const int tid = threadIdx.x;
+  for (int q = T + 3 * N + tid; q < Tw; q += FP_THREADS) srow[q] = (q - 3 * N) % T;
+  for (int q = tid; q < Tw; q += FP_THREADS) {  // the ids are NOT shifted by the insertions (reference :805-828)
+    if (emo) emo_out[(long long)b * cap + q] = emo[(long long)b * T + q % T];
+    if (spk) spk_out[(long long)b * cap + q] = spk[(long long)b * T + q % T];
+  }
+}
+
+// OR of the threads' status bits; the result is valid in thread 0.  red: FP_WAVES ints of LDS
+__device__ __forceinline__ int fp_block_or_i(int flags, int* red) {
+  flags = fp_wave_or_i(flags);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = flags;
+  __syncthreads();
+  flags = 0;
+#pragma unroll
+  for (int i = 0; i < FP_WAVES; ++i) flags |= red[i];
+  return flags;
+}
 
 __global__ __launch_bounds__(FP_THREADS) void fp_plan_kernel(const int* __restrict__ label, const int* __restrict__ lens,
                                                              const int* __restrict__ fp_number,
@@ -218,54 +286,59 @@ __global__ __launch_bounds__(FP_THREADS) void fp_plan_kernel(const int* __restri
     if (tid == 0) inter_len[b] = min(max(l, 0), T) + 3 * min(max(f, 0), 3 * T);
   }
   int* srow = src + (long long)b * cap;
-  int carry = 0;
-  for (int base = 0; base < T; base += FP_THREADS) {
-    const int p = base + tid;
-    int lab = p < T ? label[(long long)b * T + p] : 0;
-    if (lab < 0 || lab > 3) flags |= FP_ERR_LABEL, lab = 0;
-    const int f = lab > 0;
-    int inc = f;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int v = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += v;
-    }
-    __syncthreads();  // s_tot of the previous tile has been read by everyone
-    if (lane == 63) s_tot[wv] = inc;
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < FP_WAVES; ++i) {
-      woff += i < wv ? s_tot[i] : 0;
-      tot += s_tot[i];
-    }
-    const int incl = carry + woff + inc, excl = incl - f;
-    if (p < T) {
-      const int q0 = p + 3 * excl, qt = p + 3 * incl;
-      if (f) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          if (q0 + k < Tw) srow[q0 + k] = -(1 + 3 * (lab - 1) + k);
-      }
-      if (qt < Tw) srow[qt] = p;
-      pos[(long long)b * T + p] = qt;
-    }
-    carry += tot;
-  }
-  const int N = carry;
-  for (int q = T + 3 * N + tid; q < Tw; q += FP_THREADS) srow[q] = (q - 3 * N) % T;
-  for (int q = tid; q < Tw; q += FP_THREADS) {  // the ids are NOT shifted by the insertions (reference :805-828)
-    if (emo) emo_out[(long long)b * cap + q] = emo[(long long)b * T + q % T];
-    if (spk) spk_out[(long long)b * cap + q] = spk[(long long)b * T + q % T];
-  }
-  flags = fp_wave_or_i(flags);
-  if (lane == 0) s_c[wv] = flags;
-  __syncthreads();
+  const int N = fp_scan_row(label + (long long)b * T, T, Tw, srow, pos + (long long)b * T, s_tot, &flags);
+  fp_tail_and_ids(srow, emo, spk, emo_out, spk_out, b, T, N, Tw, cap);
+  flags = fp_block_or_i(flags, s_c);
   if (tid == 0) {
-    flags = 0;
-#pragma unroll
-    for (int i = 0; i < FP_WAVES; ++i) flags |= s_c[i];
     nins[b] = N;
+    meta[1 + b] = flags;
+    if (b == 0) meta[0] = Tp;
+  }
+}
+
+// Plan from GIVEN labels at a GIVEN width W (teacher forcing: nothing of the insertion depends on the network, and the
+// caller knows T' = the width of its duration targets on the host).  Same map as above, but all of columns [0, W) of the
+// stream is written whatever T' is, nothing behind them, and the counts come from the labels: every workgroup counts the
+// labels > 0 of all B rows (a wave per row; B T ints), so T' needs no second launch.  T' != W sets FP_ERR_WIDTH.
+__global__ __launch_bounds__(FP_THREADS) void fp_plan_given_kernel(const int* __restrict__ label, const int* __restrict__ lens,
+                                                                   const long long* __restrict__ emo,
+                                                                   const long long* __restrict__ spk,
+                                                                   int* __restrict__ inter_len, int* __restrict__ meta,
+                                                                   int* __restrict__ src, int* __restrict__ pos,
+                                                                   int* __restrict__ nins, long long* __restrict__ emo_out,
+                                                                   long long* __restrict__ spk_out, int* __restrict__ fp_number,
+                                                                   int B, int T, int W) {
+  __shared__ int s_a[FP_WAVES], s_b[FP_WAVES], s_c[FP_WAVES], s_tot[FP_WAVES];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int flags = 0;
+  int mi = 0, ml = 0;
+  for (int i = wv; i < B; i += FP_WAVES) {
+    int c = 0;
+    for (int p = lane; p < T; p += 64) {
+      const int lab = label[(long long)i * T + p];
+      c += lab >= 1 && lab <= 3;
+    }
+    c = fp_wave_sum_i(c);
+    const int l = min(max(lens[i], 0), T);
+    mi = max(mi, l + 3 * c), ml = max(ml, l);
+  }
+  if (lane == 0) s_a[wv] = mi, s_b[wv] = ml;
+  __syncthreads();
+  mi = ml = 0;
+#pragma unroll
+  for (int i = 0; i < FP_WAVES; ++i) mi = max(mi, s_a[i]), ml = max(ml, s_b[i]);
+  const int Tp = T + mi - ml;
+  if (Tp != W) flags |= FP_ERR_WIDTH;
+  const int l = lens[b];
+  if (l < 0 || l > T) flags |= FP_ERR_LENGTH;
+  int* srow = src + (long long)b * W;
+  const int N = fp_scan_row(label + (long long)b * T, T, W, srow, pos + (long long)b * T, s_tot, &flags);
+  fp_tail_and_ids(srow, emo, spk, emo_out, spk_out, b, T, N, W, W);
+  flags = fp_block_or_i(flags, s_c);
+  if (tid == 0) {
+    nins[b] = N;
+    fp_number[b] = N;
+    inter_len[b] = min(max(l, 0), T) + 3 * N;
     meta[1 + b] = flags;
     if (b == 0) meta[0] = Tp;
   }
@@ -432,6 +505,22 @@ extern "C" int kantts_fp_plan(const int32_t* label, const int32_t* lens, const i
                      reinterpret_cast<int*>(inter_len), reinterpret_cast<int*>(meta), reinterpret_cast<int*>(src),
                      reinterpret_cast<int*>(pos), reinterpret_cast<int*>(nins), reinterpret_cast<long long*>(emo_out),
                      reinterpret_cast<long long*>(spk_out), B, T, cap);
+  KANTTS_CHECK_LAUNCH();
+}
+
+extern "C" int kantts_fp_plan_given(const int32_t* label, const int32_t* lens, const int64_t* emo, const int64_t* spk,
+                                    int32_t* inter_len, int32_t* meta, int32_t* src, int32_t* pos, int32_t* nins,
+                                    int64_t* emo_out, int64_t* spk_out, int32_t* fp_number, int B, int T, int W, void* stream) {
+  if (!label || !lens || !inter_len || !meta || !src || !pos || !nins || !fp_number || B < 1 || T < 1 || W < 1 ||
+      (emo && !emo_out) || (spk && !spk_out))
+    return KANTTS_E_BADARG;
+  if (B > 65535 || T > (1 << 24) || W > (1 << 26)) return KANTTS_E_UNSUPPORTED;
+  hipLaunchKernelGGL(fp_plan_given_kernel, dim3(B), dim3(FP_THREADS), 0, (hipStream_t)stream,
+                     reinterpret_cast<const int*>(label), reinterpret_cast<const int*>(lens),
+                     reinterpret_cast<const long long*>(emo), reinterpret_cast<const long long*>(spk),
+                     reinterpret_cast<int*>(inter_len), reinterpret_cast<int*>(meta), reinterpret_cast<int*>(src),
+                     reinterpret_cast<int*>(pos), reinterpret_cast<int*>(nins), reinterpret_cast<long long*>(emo_out),
+                     reinterpret_cast<long long*>(spk_out), reinterpret_cast<int*>(fp_number), B, T, W);
   KANTTS_CHECK_LAUNCH();
 }
 

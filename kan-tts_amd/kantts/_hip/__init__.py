@@ -573,6 +573,8 @@ def lib():
             L.kantts_fp_insert_fwd.argtypes = [p, p, p, p, i, i, i, i, i, p]
             L.kantts_fp_insert_bwd.argtypes = [p, p, p, p, p, p, i, i, i, i, i, p]
             L.kantts_fp_ce.argtypes = [p, p, p, p, p, p, i, i, p]
+        if hasattr(L, "kantts_fp_plan_given"):  # has_fp_given(): a library built before it still loads
+            L.kantts_fp_plan_given.argtypes = [p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, p]
         if all(hasattr(L, s) for s in SPK_SYMBOLS):  # has_spk_embed(): a library built before them still loads
             L.kantts_kaldi_fbank.argtypes = [p, p, p, p, p, p, p, p, i, i, i, i, i, i, p]
             L.kantts_spk_conv2d.argtypes = [p, ll, ll, ll, ll, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, p]
@@ -631,7 +633,7 @@ EXPORTED_SYMBOLS = [
     "kantts_nsf_source_rows", "kantts_nsf_downs_rows", "kantts_mel_handover_rows",
     "kantts_mb_tail_rows", "kantts_sconv_sym_rows_launch", "kantts_lr_memory_fwd", "kantts_lr_memory_bwd",
     "kantts_nsf_source_end_rows", "kantts_nsf_downs_sym_rows", "kantts_nsf_draw_states", "kantts_nsf_source_wgrad",
-    *FP_SYMBOLS,
+    *FP_SYMBOLS, "kantts_fp_plan_given",
     *SPK_SYMBOLS,
     "kantts_fsmn_memory_drop_fwd", "kantts_fsmn_memory_drop_bwd",
     *PREDICTOR_PAIR_SYMBOLS,
@@ -1814,6 +1816,12 @@ def has_fp():
 
 
 FP_ERR_CAP, FP_ERR_LENGTH, FP_ERR_LABEL = 1, 2, 4  # bits of kantts_fp_plan's per-sequence status words
+FP_ERR_WIDTH = 8  # kantts_fp_plan_given: the T' of the labels differs from the width the caller planned at
+
+
+def has_fp_given():
+    """True when the loaded library exports kantts_fp_plan_given (the plan a captured FP training step needs)."""
+    return hasattr(lib(), "kantts_fp_plan_given")
 
 
 def fp_head(rows, weight, bias, lens32, fp_label, probs, label, fp_number, *, B, T, C):
@@ -1839,6 +1847,15 @@ def fp_plan(label, lens32, fp_number, emo, spk, inter_len, meta, src, pos, nins,
                                 ptr(emo, torch.int64), ptr(spk, torch.int64), ptr(inter_len, torch.int32),
                                 ptr(meta, torch.int32), ptr(src, torch.int32), ptr(pos, torch.int32), ptr(nins, torch.int32),
                                 ptr(emo_out, torch.int64), ptr(spk_out, torch.int64), int(B), int(T), int(cap), stream())
+
+
+def fp_plan_given(label, lens32, emo, spk, inter_len, meta, src, pos, nins, emo_out, spk_out, fp_number, *, B, T, W):
+    """kantts_fp_plan_given; returns its code like fp_plan."""
+    return lib().kantts_fp_plan_given(ptr(label, torch.int32), ptr(lens32, torch.int32), ptr(emo, torch.int64),
+                                      ptr(spk, torch.int64), ptr(inter_len, torch.int32), ptr(meta, torch.int32),
+                                      ptr(src, torch.int32), ptr(pos, torch.int32), ptr(nins, torch.int32),
+                                      ptr(emo_out, torch.int64), ptr(spk_out, torch.int64), ptr(fp_number, torch.int32),
+                                      int(B), int(T), int(W), stream())
 
 
 def fp_insert_fwd(text_hid, fill, src, out, *, B, T, Tp, cap, C):

@@ -3062,7 +3062,7 @@ def fp_head(x, weight, bias, lens32, fp_label=None):
 class FpPlan:
     """What kantts_fp_plan wrote for one batch: ``Tp`` (the host integer T'), ``inter_len`` (B) int32, the source map
     ``src`` (B, cap), its inverse ``pos`` (B, T) / ``nins`` (B), and the extended ids (B, Tp) int64."""
-    __slots__ = ("B", "T", "Tp", "cap", "inter_len", "src", "pos", "nins", "emo", "spk")
+    __slots__ = ("B", "T", "Tp", "cap", "inter_len", "src", "pos", "nins", "emo", "spk", "fp_number")
 
 
 def fp_plan(label, lens32, fp_number, emo=None, spk=None, cap=None):
@@ -3107,6 +3107,54 @@ def fp_plan(label, lens32, fp_number, emo=None, spk=None, cap=None):
         pl.emo = None if e_out is None else e_out[:, :pl.Tp].contiguous()
         pl.spk = None if s_out is None else s_out[:, :pl.Tp].contiguous()
         return pl
+
+
+def fp_plan_given(label, lens32, emo=None, spk=None, width=None):
+    """The insertion map of GIVEN labels (teacher forcing) at a width the caller knows on the host -- the width of its
+    duration targets, which ``am_collate(fp=True)`` pads to T'.  One launch (kantts_fp_plan_given), no host read and no
+    synchronisation: it may be called during stream capture.  Returns ``(plan, meta)``: an ``FpPlan`` with
+    ``Tp = cap = width`` (and ``fp_number``, the per-row insertion counts (B) int32) and ``meta`` (1 + B) int32 LEFT ON THE
+    DEVICE -- ``meta[0]`` is the T' the device found, ``meta[1 + b]`` the status word (FP_ERR_LENGTH / FP_ERR_LABEL /
+    FP_ERR_WIDTH); the caller reads it where it synchronises anyway (``fp_status_error`` names the bits)."""
+    from . import fp_plan_given as k_plan
+    from . import has_fp_given
+
+    if not has_fp_given():
+        raise RuntimeError("the loaded library lacks kantts_fp_plan_given (rebuild kan-tts_amd/csrc); there is no stock "
+                           "fallback")
+    B, T = label.shape
+    W = int(width)
+    dev = label.device
+    emo = None if emo is None else _c(emo)
+    spk = None if spk is None else _c(spk)
+    pl = FpPlan()
+    pl.B, pl.T, pl.Tp, pl.cap = B, T, W, W
+    pl.inter_len = torch.empty((B,), device=dev, dtype=torch.int32)
+    meta = torch.empty((1 + B,), device=dev, dtype=torch.int32)
+    pl.src = torch.empty((B, W), device=dev, dtype=torch.int32)
+    pl.pos = torch.empty((B, T), device=dev, dtype=torch.int32)
+    pl.nins = torch.empty((B,), device=dev, dtype=torch.int32)
+    pl.fp_number = torch.empty((B,), device=dev, dtype=torch.int32)
+    pl.emo = None if emo is None else torch.empty((B, W), device=dev, dtype=torch.int64)
+    pl.spk = None if spk is None else torch.empty((B, W), device=dev, dtype=torch.int64)
+    check(k_plan(_c(label), lens32, emo, spk, pl.inter_len, meta, pl.src, pl.pos, pl.nins, pl.emo, pl.spk, pl.fp_number,
+                 B=B, T=T, W=W), "fp_plan_given")
+    return pl, meta
+
+
+def fp_status_error(word, where="fp_plan_given"):
+    """None for a zero status word (the OR of ``meta[1:]``), else the ValueError that names its bits."""
+    from . import FP_ERR_CAP, FP_ERR_LABEL, FP_ERR_LENGTH, FP_ERR_WIDTH
+
+    word = int(word)
+    if not word:
+        return None
+    names = [text for bit, text in ((FP_ERR_WIDTH, "width mismatch (the T' of the labels is not the width of the duration "
+                                                   "targets)"),
+                                    (FP_ERR_LENGTH, "a sequence length out of range"),
+                                    (FP_ERR_LABEL, "a filled-pause label out of range [0, 3]"),
+                                    (FP_ERR_CAP, "map narrower than the output")) if word & bit]
+    return ValueError("%s: status %d: %s" % (where, word, "; ".join(names) or "unknown bits"))
 
 
 class _FpInsert(torch.autograd.Function):

@@ -76,15 +76,18 @@ class DeviceVocSet:
 class DeviceAMSet:
     """Acoustic-model training set in HBM (duration-supervised items of AM_Dataset.__getitem__: (ling_data, mel, dur, f0,
     energy, attn_prior, fp_label, se) with ling_data = six integer streams incl. the trailing "~").  ``batch(indices)``
-    == ``am_collate([items[i] for i in indices], r, pad_ids)`` with device tensors."""
+    == ``am_collate([items[i] for i in indices], r, pad_ids)`` with device tensors.  ``fp``: filled-pause items -- the
+    batch carries ``fp_label`` (padded with 0 to the input width) and pitch / energy as wide as the durations, as
+    ``am_collate(..., fp=True)`` gives them, plus the host integers ``band_width`` (over the inter lengths) and
+    ``fp_width`` (T', which equals the width of the durations for items whose durations describe the inserted sequence)."""
 
     KEYS = ("input_lings", "input_emotions", "input_speakers", "valid_input_lengths", "valid_output_lengths",
             "mel_targets", "durations", "pitch_contours", "energy_contours", "attn_priors")
 
-    def __init__(self, items, r, pad_ids, device):
+    def __init__(self, items, r, pad_ids, device, fp=False):
         if any(it[2] is None for it in items):
             raise NotImplementedError("duration-free (MAS) items carry a per-batch prior: use the host collate")
-        self.r, self.device = int(r), torch.device(device)
+        self.r, self.device, self.fp = int(r), torch.device(device), bool(fp)
         self.n_sym = np.array([len(it[0][0]) for it in items], dtype=np.int64)
         self.n_mel = np.array([len(it[1]) for it in items], dtype=np.int64)
         self.n_dur = np.array([it[2].shape[0] for it in items], dtype=np.int64)
@@ -100,14 +103,33 @@ class DeviceAMSet:
         self.pad_ids = torch.as_tensor(list(pad_ids), dtype=torch.int64).to(self.device)
         # longest duration among an utterance's real symbols (the trailing "~" excluded), on the host: a batch's attention
         # band width (kantts_sambert.py:981-985) without reading the device batch back
-        self.max_dur = np.array([int(np.max(np.asarray(it[2])[: len(it[0][0]) - 1], initial=0)) for it in items], dtype=np.int64)
+        # (FP: the model masks the duration targets with the INTER lengths, len - 1 + 3 n_fp, which may reach past an item's
+        # own durations into the slot that takes the batch's pad frames: ``band_width`` adds that slot per batch)
+        self.n_fp = np.zeros(len(items), dtype=np.int64)
+        if self.fp:
+            if any(it[6] is None or len(it[6]) != len(it[0][0]) for it in items):
+                raise ValueError("filled-pause items carry one fp_label per symbol slot")
+            self.n_fp = np.array([int(np.sum(np.asarray(it[6]) > 0)) for it in items], dtype=np.int64)
+            self.fp_label, self.fp_off = _flat([np.asarray(it[6]).reshape(-1, 1) for it in items], np.int64, self.device)
+        self.max_dur = np.array([int(np.max(np.asarray(it[2])[: len(it[0][0]) - 1 + 3 * int(n)], initial=0))
+                                 for it, n in zip(items, self.n_fp)], dtype=np.int64)
 
     def __len__(self):
         return len(self.n_sym)
 
     def band_width(self, indices):
-        """x_band_width of the batch ``indices`` as the model computes it from the duration targets (host integer)."""
-        return int(float(self.max_dur[np.asarray(indices, dtype=np.int64)].max()) / self.r + 0.5)
+        """x_band_width of the batch ``indices`` as the model computes it from the duration targets (host integer).  FP: over
+        the inter lengths, ``band_width_of(durations, valid_input_lengths + 3 #(fp_label > 0), r)``."""
+        idx = np.asarray(indices, dtype=np.int64)
+        longest = int(self.max_dur[idx].max())
+        if self.fp:
+            # a row whose inter length reaches past its own durations also shows the slot behind them, where the frames
+            # that pad the mel to the batch's width go (Padder._pad_durations)
+            max_out = Padder()._round_up(int(self.n_mel[idx].max()), self.r)
+            extra = np.where(self.frames[idx] < max_out, max_out - self.frames[idx], 0)
+            seen = self.n_sym[idx] - 1 + 3 * self.n_fp[idx] > self.n_dur[idx]
+            longest = max(longest, int(np.max(extra * seen, initial=0)))
+        return int(float(longest) / self.r + 0.5)
 
     def batch(self, indices):
         idx = np.asarray(indices, dtype=np.int64)
@@ -129,10 +151,16 @@ class DeviceAMSet:
         extra = np.where(self.frames[idx] < max_out, max_out - self.frames[idx], 0)
         dur.scatter_add_(1, i64(self.n_dur[idx]).view(-1, 1), i64(extra).view(-1, 1))
         out["durations"] = dur
-        out["pitch_contours"] = hip.ragged_rows(self.f0, i64(self.f0_off[idx]), i32(self.n_f0[idx]), max_in).view(len(idx), max_in)
-        out["energy_contours"] = hip.ragged_rows(self.energy, i64(self.en_off[idx]), i32(self.n_en[idx]), max_in).view(len(idx), max_in)
+        feat = max_dur if self.fp else max_in  # FP: pitch / energy describe the sequence after the insertion
+        out["pitch_contours"] = hip.ragged_rows(self.f0, i64(self.f0_off[idx]), i32(self.n_f0[idx]), feat).view(len(idx), feat)
+        out["energy_contours"] = hip.ragged_rows(self.energy, i64(self.en_off[idx]), i32(self.n_en[idx]), feat).view(len(idx), feat)
         out["attn_priors"] = None
         out["band_width"] = self.band_width(idx)  # host integer (Sambert_Trainer: captured-step class of the batch)
+        if self.fp:
+            out["fp_label"] = hip.ragged_rows(self.fp_label, i64(self.fp_off[idx]), i32(self.n_sym[idx]),
+                                              max_in).view(len(idx), max_in)
+            lens = self.n_sym[idx] - 1
+            out["fp_width"] = int(max_in + (lens + 3 * self.n_fp[idx]).max() - lens.max())  # T' (host integer)
         return out
 
 
@@ -171,6 +199,10 @@ class PinnedPrefetcher:
             if (self.r and not path and "band_width" not in batch and torch.is_tensor(batch.get("durations"))
                     and torch.is_tensor(batch.get("valid_input_lengths")) and not batch["durations"].is_cuda):
                 d, n = batch["durations"], batch["valid_input_lengths"]
+                if torch.is_tensor(batch.get("fp_label")):  # FP: over the inter lengths (kantts_sambert.fp_inter_lengths)
+                    n = n + 3 * (batch["fp_label"] > 0).sum(1)
+                    lens = batch["valid_input_lengths"]
+                    out["fp_width"] = int(batch["fp_label"].size(1) + n.max() - lens.max())  # T' (fp_width_of)
                 valid = torch.arange(d.size(1))[None, :] < n[:, None]
                 out["band_width"] = int(float((d * valid).max()) / self.r + 0.5)  # == kantts_sambert.band_width_of
             return out
@@ -276,9 +308,11 @@ def make_train_loader(kind, dataset, host_loader, device, batch_size, sampler=No
     device = torch.device(device)
     if mode == "off":
         return host_loader
-    if kind == "am" and getattr(dataset, "fp_enable", False):
-        raise NotImplementedError("--device_corpus with a filled-pause (FP) model: the device-side batch assembly has no "
-                                  "fp_label stream and pads pitch / energy to the input width; use --device_corpus off")
+    fp = kind == "am" and bool(getattr(dataset, "fp_enable", False))
+    if fp and device.type != "cuda":
+        raise NotImplementedError("--device_corpus with a filled-pause (FP) model on device '%s': the device-side batch "
+                                  "assembly (fp_label stream, pitch / energy at the width of the durations) runs on a HIP "
+                                  "device only; use --device_corpus off" % device.type)
     if device.type != "cuda":
         return host_loader
     r = getattr(dataset, "r", None) if kind == "am" else None
@@ -296,7 +330,7 @@ def make_train_loader(kind, dataset, host_loader, device, batch_size, sampler=No
         items = [dataset[i] for i in range(len(dataset))]
         if kind == "am":
             pad_ids = [dataset.ling_unit._sub_unit_pad[t] for t in dataset.ling_unit._lfeat_type_list]
-            dset = DeviceAMSet(items, dataset.r, pad_ids, device)
+            dset = DeviceAMSet(items, dataset.r, pad_ids, device, fp=fp)
         else:
             dset = DeviceVocSet(items, dataset.hop_length, dataset.batch_max_steps, device)
         return DeviceCorpusLoader(dset, batch_size, sampler=sampler, shuffle=sampler is None,

@@ -491,6 +491,23 @@ def band_width_of(duration_targets, input_lengths, r):
     return int(float((duration_targets * valid).max()) / r + 0.5)
 
 
+def fp_inter_lengths(fp_label, input_lengths):
+    """Lengths of a filled-pause batch AFTER the insertion: every label > 0 of a row, padded slots included, adds three
+    rows.  The band width of an FP batch is taken over THESE lengths (``band_width_of(durations, fp_inter_lengths(...),
+    r)``): the model masks the duration targets with the inter info, so the tail of each row counts."""
+    return input_lengths + 3 * (fp_label > 0).sum(1).to(input_lengths.dtype)
+
+
+def fp_width_of(fp_label, input_lengths):
+    """T' of a filled-pause batch, the width its duration / pitch / energy targets must have, as a host integer:
+    T + max(inter lengths) - max(lengths) (kantts_fp_plan_given computes the same on the device).  On host tensors this
+    costs no device synchronisation."""
+    T = fp_label.size(1)
+    lens = input_lengths.clamp(0, T)
+    inter = lens + 3 * ((fp_label >= 1) & (fp_label <= 3)).sum(1).to(lens.dtype)
+    return T + int(inter.max()) - int(lens.max())
+
+
 def average_frame_feat(pitch, durs):
     """Frame-level contour (B, F, T_mel) -> per-phoneme mean over each phoneme's NON-ZERO frames (B, F, N), 0 where a
     phoneme has none (reference :652-674).  Prefix sums + two gathers; durations are whole numbers stored as float."""
@@ -581,6 +598,14 @@ class KanTtsSAMBERT(nn.Module):
             # {1, 2, 3: (1, 3, 4) int64}: the linguistic ids of the "en" / "a" / "e" fillers; attached by
             # sambert_model_builder from kantts.utils.ling_unit.get_fpdict, as the reference does
             self.fp_dict = None
+        # True (opt-in; the captured step sets it as it sets ``device_band_width``): a teacher-forced step of an FP model
+        # plans the insertion from the GIVEN labels at the width of the duration targets (ops.fp_plan_given) -- no host
+        # read of T', and the plan, the target-only plan and the embeddings of the extended ids run beside the encoder.
+        # The status words of the step are left on the device in ``fp_status`` / res["fp_status"] for the caller to check
+        # where it synchronises anyway.  Inference never takes this path: its labels are predictions.
+        self.fp_static_width = False
+        self.fp_status = None
+        self._fp_ids = None
         # the reference always returns 8 + 24 dense attention maps; here opt-in
         self.return_attns = False
         # True: the band width stays in device memory (no host sync) so that a whole training step can be
@@ -660,7 +685,14 @@ class KanTtsSAMBERT(nn.Module):
             raise RuntimeError("FP model without fp_dict: attach {1, 2, 3: (1, 3, 4) ids} (sambert_model_builder does, "
                                "from kantts.utils.ling_unit.get_fpdict)")
         dev = self.text_encoder.ling_proj.weight.device
-        ids = torch.cat([self.fp_dict[c].reshape(1, 3, -1)[:, :, :4] for c in (1, 2, 3)], dim=0).to(dev)
+        if self.fp_static_width:
+            # the ids are constants of the voice: uploaded once, because a host-to-device copy cannot be captured
+            if self._fp_ids is None or self._fp_ids[0] is not self.fp_dict or self._fp_ids[1].device != dev:
+                self._fp_ids = (self.fp_dict, torch.cat([self.fp_dict[c].reshape(1, 3, -1)[:, :, :4] for c in (1, 2, 3)],
+                                                        dim=0).to(dev))
+            ids = self._fp_ids[1]
+        else:
+            ids = torch.cat([self.fp_dict[c].reshape(1, 3, -1)[:, :, :4] for c in (1, 2, 3)], dim=0).to(dev)
         return self.text_encoder(ids, None, False)[0]
 
     def insert_fp(self, text_hid, label, fp_number, inputs_emotion, inputs_speaker, lens32, fillers=None):
@@ -670,6 +702,30 @@ class KanTtsSAMBERT(nn.Module):
         plan = ops.fp_plan(label, lens32, fp_number, inputs_emotion, inputs_speaker)
         out = ops.fp_insert(text_hid, self.fp_fillers() if fillers is None else fillers, plan)
         return out, plan.emo, plan.spk, plan.inter_len
+
+    def _beside_encoder_fp(self, label32, lens32, output_lengths, mel_targets, duration_targets, inputs_emotion,
+                           inputs_speaker, pitch_targets, energy_targets, fused):
+        """``_beside_encoder`` of an FP model on the static path: the insertion plan from the given labels at the width of
+        the duration targets (one launch, no host read), then the target-only plan over the INTER lengths that launch just
+        wrote on the device, then the embeddings of the extended ids.  Returns the plan with "fp_plan", "fp_meta",
+        "inter_info" and "inter_lengths" added."""
+        W = duration_targets.size(1)
+        fp_plan, meta = ops.fp_plan_given(label32, lens32, inputs_emotion, inputs_speaker, width=W)
+        inter_lengths = fp_plan.inter_len.to(output_lengths.dtype)
+        if fused:
+            inter_info, base_plan = self.teacher_forced_plan_fused(inter_lengths, W, output_lengths, mel_targets,
+                                                                   duration_targets)
+            # the position term from the stock operators, as the default FP path forms it: the launch's sinusoids equal
+            # them to fp32 rounding only (tests/test_teacher_plan.py), and this path is to give the default path's numbers
+            # bit for bit on equal arithmetic -- a handful of small launches, here beside the encoder
+            with torch.no_grad():
+                base_plan["pos_enc"] = self.variance_adaptor.position_term(base_plan["lr_plan"], base_plan["out_info"])
+        else:
+            inter_info, base_plan = SeqInfo(inter_lengths, W), None
+        plan = self._beside_encoder(inter_info, output_lengths, mel_targets, duration_targets, fp_plan.emo, fp_plan.spk,
+                                    pitch_targets, energy_targets, base_plan=base_plan)
+        plan.update(fp_plan=fp_plan, fp_meta=meta, inter_info=inter_info, inter_lengths=inter_lengths)
+        return plan
 
     def _embed_emo_spk(self, inputs_emotion, inputs_speaker):
         (emo_hid, _) = ops.embed_sum(inputs_emotion, [self.emo_tokenizer.weight])
@@ -704,7 +760,7 @@ class KanTtsSAMBERT(nn.Module):
                           "lfr_info", "out_info", "enc_sla_attn_lst", "LR_length_rounded", "log_duration_predictions",
                           "pitch_predictions", "energy_predictions", "duration_targets", "pitch_targets", "energy_targets",
                           "inter_lengths", "LR_text_outputs", "LR_emo_outputs", "LR_spk_outputs", "ling_embedding",
-                          "attn_soft", "attn_hard", "attn_logprob", "fp_predictions", "fp_decisions")
+                          "attn_soft", "attn_hard", "attn_logprob", "fp_predictions", "fp_decisions", "fp_status")
 
     def _token_side(self, inputs_ling, inputs_emotion, inputs_speaker, input_lengths, output_lengths=None,
                     mel_targets=None, duration_targets=None, pitch_targets=None, energy_targets=None, attn_priors=None,
@@ -718,12 +774,17 @@ class KanTtsSAMBERT(nn.Module):
         is_training = mel_targets is not None
         tplan = base_plan = in_info = None
         # FP: the targets are as wide as the sequences AFTER the insertion (T', known once the plan is read back), so the
-        # target-only plan cannot be formed beside the encoder from T_in: FP models take the inline (unfused) plan
-        teacher = (is_training and not self.MAS and not getattr(self, "inline_teacher_plan", False) and not self.fp_enable
+        # target-only plan cannot be formed beside the encoder from T_in: FP models take the inline (unfused) plan -- unless
+        # ``fp_static_width`` is on and the labels are given: then T' is the width of the duration targets (fp_static)
+        fp_static = (self.fp_enable and self.fp_static_width and is_training and fp_label is not None)
+        teacher = (is_training and not self.MAS and not getattr(self, "inline_teacher_plan", False)
+                   and (not self.fp_enable or fp_static)
                    and output_lengths is not None and duration_targets is not None and pitch_targets is not None
                    and energy_targets is not None)
-        if (teacher and _PLAN_KERNEL and duration_targets.dtype == torch.int64 and mel_targets.dtype == torch.float32
-                and mel_targets.dim() == 3 and inputs_ling.numel() > 0):
+        fp_static = fp_static and teacher
+        fused = (teacher and _PLAN_KERNEL and duration_targets.dtype == torch.int64 and mel_targets.dtype == torch.float32
+                 and mel_targets.dim() == 3 and inputs_ling.numel() > 0)
+        if fused and not fp_static:
             in_info, base_plan = self.teacher_forced_plan_fused(input_lengths, T_in, output_lengths, mel_targets,
                                                                 duration_targets)
         if in_info is None:
@@ -734,7 +795,18 @@ class KanTtsSAMBERT(nn.Module):
         # of the durations = 3 of 32 utterance lengths.  It is T_in <= ~80 tokens: a few % of an utterance's time.
         front = hip_rt.precision_scope("fp32" if (not is_training and self.infer_front_fp32) else None)
         with front:
-            if teacher:
+            if fp_static:
+                if inputs_speaker.dim() != 2:
+                    raise ValueError("FP models take integer speaker ids (B, T)")
+                label32 = fp_label.to(torch.int32).contiguous()
+                enc_info = in_info
+                (text_hid, enc_sla_attn_lst, ling_embedding), tplan = ops.run_beside(
+                    lambda: self.text_encoder(inputs_ling, enc_info, self.return_attns),
+                    lambda: self._beside_encoder_fp(label32, enc_info.lens32, output_lengths, mel_targets, duration_targets,
+                                                    inputs_emotion, inputs_speaker, pitch_targets, energy_targets, fused),
+                    side_inputs=(output_lengths, mel_targets, duration_targets, label32, enc_info.lens32, inputs_emotion,
+                                 inputs_speaker, pitch_targets, energy_targets))
+            elif teacher:
                 (text_hid, enc_sla_attn_lst, ling_embedding), tplan = ops.run_beside(
                     lambda: self.text_encoder(inputs_ling, in_info, self.return_attns),
                     lambda: self._beside_encoder(in_info, output_lengths, mel_targets, duration_targets, inputs_emotion,
@@ -747,8 +819,17 @@ class KanTtsSAMBERT(nn.Module):
             # the side stream, beside the encoder's own backward (no-op unless weight gradients are deferred)
             text_hid = ops.wgrad_flush_point(text_hid)
             inter_lengths = input_lengths
-            fp_predictions = fp_decisions = None
-            if self.fp_enable:
+            fp_predictions = fp_decisions = fp_status = None
+            if fp_static:
+                # only the head (for fp_predictions) and the gather stay behind the encoder; the plan ran beside it
+                fp_predictions, label, fp_number = self.FP_predictor.decide(text_hid, in_info.lens32, label32)
+                text_hid = ops.fp_insert(text_hid, self.fp_fillers(), tplan["fp_plan"])
+                inputs_emotion, inputs_speaker = tplan["fp_plan"].emo, tplan["fp_plan"].spk
+                inter_lengths = tplan["inter_lengths"]
+                fp_decisions = (label, fp_number)
+                in_info = tplan["inter_info"]
+                self.fp_status = fp_status = tplan["fp_meta"]
+            elif self.fp_enable:
                 # predictor -> decision -> plan (the one host read: T') -> gather; everything downstream sees the extended
                 # sequences, lengths and ids (reference :885-899).  Inference: fp32 whatever the precision mode (this block
                 # sits inside ``front``) -- the decisions are index tensors
@@ -896,6 +977,8 @@ class KanTtsSAMBERT(nn.Module):
             res["attn_soft"] = ts.attn_soft
             res["attn_hard"] = ts.attn_hard
             res["attn_logprob"] = ts.attn_logprob
+        if ts.fp_status is not None:
+            res["fp_status"] = ts.fp_status  # (1 + B) int32 on the device: [T', status words]; 0 words = a consistent batch
         return res
 
 

@@ -25,7 +25,8 @@ from kantts._hip import ops, rng_state as _rng_state
 
 class GraphedSambertStep:
     def __init__(self, net, optimizer, scheduler, mel_criterion, prosody_criterion, batch, warmup=3,
-                 overlap_wgrad=True, group_wgrads=True, band_width=None, force_wide=False, mas_criteria=None):
+                 overlap_wgrad=True, group_wgrads=True, band_width=None, force_wide=False, mas_criteria=None,
+                 fp_criterion=None, fp_width=None):
         """``band_width``: x_band_width of ``batch`` when the caller already knows it on the host (band_width_of on the
         batch before its upload); None: read from the device batch here, once.  ``force_wide``: capture the wide-band form
         (the five-launch decoder chain, any band width) whatever this batch's band is -- data parallel: the form must be
@@ -40,6 +41,17 @@ class GraphedSambertStep:
         self.mas_criteria = mas_criteria
         if mas_criteria is not None:
             self._force_wide = True
+        # Filled-pause step (FP: True): ``fp_criterion`` (FpCELoss, one launch) joins the objective and ``batch`` carries
+        # ``fp_label``.  The model takes its static path (``fp_static_width``): the insertion is planned from the labels at
+        # the width of the duration targets, so nothing is read back.  A batch whose T' is not that width is refused on the
+        # host (``_check_fp_width``; ``fp_width``: the T' of ``batch`` if the caller knows it from a host copy); what the
+        # device finds is ORed, replay after replay, into ``fp_status`` (a device word; ``check_fp_status`` reads it).
+        self.fp_criterion = fp_criterion
+        self.fp_status = None
+        if fp_criterion is not None and mas_criteria is not None:
+            raise NotImplementedError("FP together with MAS is not a shipped configuration")
+        if fp_criterion is not None:
+            self._check_fp_width(batch, fp_width)
         # weight gradients leave the critical path: fp32-mode ones as parallel branches of the captured graph
         # (ops._WgradOverlap), bf16-mode ones recorded and issued grouped by shape before the optimizer
         # (kantts._hip.deferred_tn); the variance predictors run as a side branch (ops.side_branch).  These switches only
@@ -54,6 +66,12 @@ class GraphedSambertStep:
         names = [n for n, _ in net.named_parameters(remove_duplicate=False)]
         if len(names) != len(list(net.parameters())):
             raise NotImplementedError("GraphedSambertStep defers weight gradients; tied parameters are not supported")
+        if fp_criterion is not None:
+            # An FP forward runs the text encoder TWICE (the batch and the three filler sequences), so each of its
+            # parameters receives two gradients per backward and autograd adds the second into the first on the main
+            # stream -- at a time when a deferred / side-stream weight gradient has not been written yet (the hazard
+            # described above for tied parameters).  The FP step is therefore captured with every weight gradient in line.
+            overlap_wgrad = group_wgrads = False
         ops.wgrad_overlap.enable(overlap_wgrad, group_wgrads=group_wgrads)
         try:
             self._build(net, optimizer, scheduler, mel_criterion, prosody_criterion, batch, warmup)
@@ -67,6 +85,11 @@ class GraphedSambertStep:
         self.batch = {k: v.clone() for k, v in batch.items()}
         self.device = next(net.parameters()).device
         net.device_band_width = True
+        if self.fp_criterion is not None:
+            net.fp_static_width = True
+            self.fp_criterion.to(self.device)  # (a class weight left on the host would be uploaded inside the capture)
+            self.fp_status = torch.zeros(1, device=self.device, dtype=torch.int32)
+            self._fp_bits = torch.tensor([1, 2, 4, 8], device=self.device, dtype=torch.int32)
         # The band width itself stays in device memory, but the SHAPE of the captured step depends on it: up to 16 the
         # decoder blocks are one launch each (csrc/pnca_block.hip), above that the five-launch chain.  The capture is made
         # for the class this batch is in; load_batch() refuses a batch of the other class (the trainer keys its graph cache
@@ -81,7 +104,7 @@ class GraphedSambertStep:
             self.kl_ratio = torch.zeros((), device=self.device, dtype=torch.float32)
             self.set_epoch(0)
         elif bw is None:
-            bw = band_width_of(self.batch["duration_targets"], self.batch["input_lengths"], self._r)
+            bw = band_width_of(self.batch["duration_targets"], self._band_lengths(self.batch), self._r)
         self.narrow_band = bw <= ops_bf16.PB_MAX_BAND and not self._force_wide
         self._bound = ops_bf16.PB_MAX_BAND if self.narrow_band else None
         self.distributed = optimizer.arena.world_size > 1 or getattr(optimizer.arena, "force_exchange", False)
@@ -112,6 +135,8 @@ class GraphedSambertStep:
         torch.cuda.current_stream().wait_stream(self._cap_stream)
         torch.cuda.synchronize()
         self.loss = None
+        if self.fp_status is not None:
+            self.fp_status.zero_()  # the warm-up steps are not steps of the run
         optimizer.restore(snap)
         if rng_snap is not None:
             _rng_state(self.device).copy_(rng_snap)
@@ -184,7 +209,16 @@ class GraphedSambertStep:
             self.net.band_width_bound = None
         from kantts.train.loss import sambert_loss_sum
 
-        if self.mas_criteria is None:
+        if self.fp_criterion is not None:
+            total, terms = sambert_loss_sum(self.mel_criterion, self.prosody_criterion, b, res,
+                                            prosody_lengths=res["valid_inter_lengths"])
+            fp = self.fp_criterion(b["input_lengths"], res["fp_predictions"], b["fp_label"])
+            self.loss = total + fp
+            self.loss_terms = dict(terms, fp_loss=fp.detach())
+            # OR of the B status words (each bit's maximum over the rows, summed) into the word this step owns
+            words = res["fp_status"][1:]
+            self.fp_status.bitwise_or_((words.unsqueeze(1) & self._fp_bits).amax(0).sum().to(torch.int32))
+        elif self.mas_criteria is None:
             self.loss, self.loss_terms = sambert_loss_sum(self.mel_criterion, self.prosody_criterion, b, res)
         else:
             total, terms = sambert_loss_sum(self.mel_criterion, self.prosody_criterion, b, res,
@@ -211,16 +245,53 @@ class GraphedSambertStep:
         ratio = 0.0 if epoch < c.start_epoch else min(1.0, (epoch - c.start_epoch) / c.warmup_epoch)
         self.kl_ratio.fill_(float(ratio))
 
-    def load_batch(self, batch, band_width=None):
+    def _band_lengths(self, batch):
+        """The lengths the model masks the duration targets with: the inter lengths for a filled-pause batch."""
+        if self.fp_criterion is None:
+            return batch["input_lengths"]
+        from kantts.models.sambert.kantts_sambert import fp_inter_lengths
+
+        return fp_inter_lengths(batch["fp_label"], batch["input_lengths"])
+
+    def _check_fp_width(self, batch, fp_width=None):
+        """A filled-pause batch whose duration targets are not T' columns wide is refused BEFORE it runs.  ``fp_width``: the
+        T' of its labels and lengths when the caller has it from a host copy; None: computed from ``batch`` (a device
+        synchronisation when the batch is on the device)."""
+        from kantts.models.sambert.kantts_sambert import fp_width_of
+
+        if "fp_label" not in batch:
+            raise ValueError("a filled-pause step needs fp_label in the batch")
+        if fp_width is None:
+            fp_width = fp_width_of(batch["fp_label"], batch["input_lengths"])
+        have = batch["duration_targets"].size(1)
+        if int(fp_width) != have:
+            raise ValueError("filled-pause batch: the duration targets are %d columns wide, the labels and lengths give "
+                             "T' = %d (width mismatch)" % (have, int(fp_width)))
+
+    def check_fp_status(self):
+        """Read and clear the status word (a device synchronisation); a non-zero word raises the ValueError that names its
+        bits: width mismatch, length out of range, label out of range."""
+        if self.fp_status is None:
+            return
+        word = int(self.fp_status.item())
+        self.fp_status.zero_()
+        err = ops.fp_status_error(word, "captured filled-pause step")
+        if err is not None:
+            raise err
+
+    def load_batch(self, batch, band_width=None, fp_width=None):
         """Copy a new batch of the captured shape into the static buffers.  ``band_width``: its x_band_width if the caller
-        knows it on the host; else it is read from ``batch`` (a device synchronisation when the batch is on the device)."""
+        knows it on the host; else it is read from ``batch`` (a device synchronisation when the batch is on the device).
+        ``fp_width``: likewise the T' of a filled-pause batch (``_check_fp_width``)."""
         from kantts._hip import ops_bf16
         from kantts.models.sambert.kantts_sambert import band_width_of
 
+        if self.fp_criterion is not None:
+            self._check_fp_width(batch, fp_width)
         if band_width is None and not self.narrow_band:
             band_width = 0  # the wide form serves every band width: nothing to check (MAS batches carry no durations)
         if band_width is None:
-            band_width = band_width_of(batch["duration_targets"], batch["input_lengths"], self._r)
+            band_width = band_width_of(batch["duration_targets"], self._band_lengths(batch), self._r)
         if self.narrow_band and band_width > ops_bf16.PB_MAX_BAND:  # (the wide form serves every band width)
             raise ValueError("this step was captured for band widths <= %d, the batch has %d: capture another step for it"
                              % (ops_bf16.PB_MAX_BAND, band_width))

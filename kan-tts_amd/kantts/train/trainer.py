@@ -187,15 +187,24 @@ class Sambert_Trainer(Trainer):
     into one hipGraph the first time a batch shape is seen and replays it for every later batch of that shape."""
 
     KEY = "KanTtsSAMBERT"
+    fp_enable = False  # set per instance from the configuration (FP: True)
+    _fp_evicted = None  # FP: status word of the captured steps the LRU dropped since the last check
 
     def __init__(self, *args, graph=False, **kwargs):
         super().__init__(*args, **kwargs)
         params = self.config["Model"][self.KEY]["params"]
         self.with_MAS, self.fp_enable = params.get("MAS", False), params.get("FP", False)
         if self.fp_enable and graph:
-            raise NotImplementedError("graph=True with FP: the width T' of the sequences after the filled-pause insertion is "
-                                      "read back from the device for every batch, so the step cannot be captured; "
-                                      "train FP voices with the eager step")
+            # the captured FP step plans the insertion from the batch's labels at the width of its duration targets
+            # (kantts_fp_plan_given): that needs a device that captures and a library with the entry point
+            from kantts import _hip as hip_rt
+
+            if self.device.type != "cuda" or not hip_rt.has_fp_given():
+                raise NotImplementedError(
+                    "graph=True with FP on %s: without kantts_fp_plan_given on a capturing device the width T' of the "
+                    "sequences after the filled-pause insertion is read back from the device for every batch, so the step "
+                    "cannot be captured; train FP voices with the eager step" % (
+                        "device '%s'" % self.device.type if self.device.type != "cuda" else "this library"))
         if self.fp_enable and "FpCELoss" not in self.criterion:
             raise ValueError("FP: True needs Loss.FpCELoss enabled in the configuration")
         # graph=True serves the MAS step too since round 6 (the CTC criterion is a device-side launch: csrc/ctc.hip)
@@ -248,9 +257,23 @@ class Sambert_Trainer(Trainer):
                 from kantts._hip import ops_bf16
 
                 bw = ops_bf16.PB_MAX_BAND + 1  # the durations are aligned on the device: the wide-band form (graph_step.py)
+            elif bw is None and self.fp_enable:
+                # FP: over the INTER lengths -- the model masks the duration targets with the info after the insertion
+                from kantts.models.sambert.kantts_sambert import fp_inter_lengths
+
+                bw = band_width_of(batch["durations"], fp_inter_lengths(batch["fp_label"], batch["valid_input_lengths"]),
+                                   net.mel_decoder.r)
             elif bw is None:
                 bw = band_width_of(batch["durations"], batch["valid_input_lengths"], net.mel_decoder.r)
-            return self._graph_step(b, bw)
+            fp_width = None
+            if self.fp_enable:
+                # T' of the labels, from the HOST copy when there is one (a device-assembled batch brings it along)
+                from kantts.models.sambert.kantts_sambert import fp_width_of
+
+                fp_width = batch.get("fp_width")
+                if fp_width is None and not batch["fp_label"].is_cuda:
+                    fp_width = fp_width_of(batch["fp_label"], batch["valid_input_lengths"])
+            return self._graph_step(b, bw, fp_width)
         from kantts._hip import ops
 
         if b["mel_targets"].is_cuda:
@@ -286,7 +309,30 @@ class Sambert_Trainer(Trainer):
             wide, missing_narrow, missing_wide = (bool(int(v)) for v in flags)
         return wide, (missing_wide if wide else missing_narrow)
 
-    def _graph_step(self, b, band_width):
+    def _flush_losses(self, into, prefix):
+        super()._flush_losses(into, prefix)
+        if prefix == "train":
+            self._check_fp_status()
+
+    def _check_fp_status(self):
+        """FP, captured steps: the status words the replays since the last flush ORed together, read where the losses were
+        just read (the trainer synchronises there anyway).  Non-zero: ValueError naming the bits."""
+        words = [g.fp_status for g in self._graphs.values() if getattr(g, "fp_status", None) is not None]
+        if self._fp_evicted is not None:
+            words.append(self._fp_evicted)
+        if not words:
+            return
+        from kantts._hip import ops
+
+        word = 0
+        for w in torch.cat(words).cpu().tolist():
+            word |= w
+        if word:
+            for w in words:
+                w.zero_()
+            raise ops.fp_status_error(word, "Sambert_Trainer: a filled-pause batch since the last log interval")
+
+    def _graph_step(self, b, band_width, fp_width=None):
         from kantts._hip import ops_bf16
         from kantts.train.graph_step import GraphedSambertStep
 
@@ -294,28 +340,45 @@ class Sambert_Trainer(Trainer):
         wide, build = self._agree_on_graph(shape_key, band_width > ops_bf16.PB_MAX_BAND)
         key = shape_key + (not wide,)
         g = self._graphs.pop(key, None)
+        # FP: the criterion that joins the captured objective and the T' of this batch (nothing is passed without FP)
+        fp = {"fp_criterion": self.criterion["FpCELoss"], "fp_width": fp_width} if self.fp_enable else {}
         if build:
             g = None  # (data parallel: another rank has to build, so this one builds with it)
             if len(self._graphs) >= self.max_graphs:  # least recently used shape goes (dicts keep insertion order)
-                self._graphs.pop(next(iter(self._graphs)))
+                old = self._graphs.pop(next(iter(self._graphs)))
+                if getattr(old, "fp_status", None) is not None:  # its unread status word outlives it
+                    self._fp_evicted = old.fp_status if self._fp_evicted is None else self._fp_evicted | old.fp_status
             mas = ({k: self.criterion[k] for k in ("AttentionCTCLoss", "AttentionBinarizationLoss")} if self.with_MAS
                    else None)
             g = GraphedSambertStep(self.model[self.KEY], self.optimizer[self.KEY], self.scheduler[self.KEY],
                                    self.criterion["MelReconLoss"], self.criterion["ProsodyReconLoss"],
                                    {k: v for k, v in b.items() if v is not None}, band_width=band_width, force_wide=wide,
-                                   mas_criteria=mas)
+                                   mas_criteria=mas, **fp)
         else:
-            g.load_batch({k: v for k, v in b.items() if v is not None}, band_width=band_width)
+            g.load_batch({k: v for k, v in b.items() if v is not None}, band_width=band_width,
+                         **({"fp_width": fp_width} if fp else {}))
         self._graphs[key] = g  # most recently used last
         g.set_epoch(self.epoch)
         g()
         self._accumulate("train", {"TotalLoss": g.loss})
+        if self.fp_enable:
+            self._accumulate("train", {"fp_loss": g.loss_terms["fp_loss"]})
         return g.loss
 
     @torch.no_grad()
     def eval_step(self, batch):
         b = self._to_device(batch)
-        res = self.model[self.KEY](**b)
+        net = self.model[self.KEY]
+        # evaluation stays eager, and FP models take their default path there (T' read back, errors raised at once), also
+        # after a captured step has switched the static path on
+        static = getattr(net, "fp_static_width", False)
+        if static:
+            net.fp_static_width = False
+        try:
+            res = net(**b)
+        finally:
+            if static:
+                net.fp_static_width = True
         _, losses = self._losses(b, res)
         self._accumulate("eval", losses)
 

@@ -13,6 +13,13 @@ Two points, each in a child process of its own under ``timeout`` (the children a
           predictor, the three-filler encoder pass, head / plan / insert, FpCELoss and the host read of T' -- minus the
           baseline's encoder running T' instead of T tokens wide.
 
+  captured  the CAPTURED step of the same FP model (GraphedSambertStep with ``fp_criterion``: the insertion planned from the
+          given labels at the width of the duration targets, kantts_fp_plan_given, no host read) against the eager FP step
+          above -- both on this commit, the eager leg being the path every FP step took before -- and the same pair for the
+          ``FP: False`` twin on the shapes downstream of the insertion, so that what FP still costs inside a captured step
+          can be read off.  Device launches per step of all four legs, and the number of distinct captured shapes a pass
+          over ``--shape_batches`` seeded batches of this geometry builds (FP adds T' to the key beside the mel length).
+
 Timing: host clock around work that ends in a device synchronise; the two legs of a point interleaved, ``--reps`` windows
 each after a warm-up of both; median, minimum and maximum of the windows are recorded.
 
@@ -61,8 +68,13 @@ def _window(torch, fn, iters):
     return (time.perf_counter() - t0) / iters * 1e3  # ms per call
 
 
-def _launches(torch, fn):
-    """Device kernels and copies of one call, from the profiler (untimed pass)."""
+_LAUNCH_CALLS = ("hipLaunch", "hipExtLaunch", "hipExtModuleLaunch", "hipModuleLaunch", "hipMemcpy", "hipMemset")
+
+
+def _launches(torch, fn, host_side=False):
+    """Device kernels and copies of one call, from the profiler (untimed pass).  ``host_side``: count the runtime's launch /
+    copy / fill CALLS instead of the device records -- work issued on several streams at once came back with device records
+    missing (the count changed from run to run), the calls are all there."""
     from torch.profiler import ProfilerActivity, profile
 
     fn()
@@ -70,6 +82,9 @@ def _launches(torch, fn):
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
         fn()
         torch.cuda.synchronize()
+    if host_side:
+        return sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CPU
+                   and e.name.startswith(_LAUNCH_CALLS))
     return sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
 
 
@@ -155,18 +170,18 @@ def point_insert(reps):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def _fp_batch(torch, fp):
+def _fp_batch(torch, fp, seed=3, cuda=True):
     """FP: tokens (B, T) + labels, targets as wide as the sequences after the insertion (T').  Not FP: tokens (B, T') of
     the inter lengths, the same targets."""
-    label, lens = _labels(torch)
+    label, lens = _labels(torch, seed)
     inter = lens + 3 * (label > 0).sum(1)
     Tp = T + int(inter.max()) - int(lens.max())
-    g = torch.Generator().manual_seed(5)
+    g = torch.Generator().manual_seed(seed + 2)
     vocab = (147, 10, 8, 8)
     Tw = T if fp else Tp
     ling = torch.stack([torch.randint(0, vocab[k] - 3, (B, Tw), generator=g) for k in range(4)], -1)
     emo, spk = torch.randint(0, 33, (B, Tw), generator=g), torch.zeros(B, Tw, dtype=torch.long)
-    g = torch.Generator().manual_seed(6)
+    g = torch.Generator().manual_seed(seed + 3)
     dur = torch.randint(2, 17, (B, Tp), generator=g) * (torch.arange(Tp)[None, :] < inter[:, None])
     out_lens = dur.sum(1)
     T_mel = -(-int(out_lens.max()) // 3) * 3
@@ -182,23 +197,19 @@ def _fp_batch(torch, fp):
                  energy_targets=torch.randn(B, Tp, generator=g))
     if fp:
         batch["fp_label"] = label
-    return {k: v.cuda() for k, v in batch.items()}
+    return {k: v.cuda() for k, v in batch.items()} if cuda else batch
 
 
-def point_step(reps):
-    import torch
-
-    import kantts._hip as hip
+def _step_legs(torch, fps=(True, False)):
+    """{fp: (net, opt, batch, eager step)}: the full 16k model, bf16 mode, arena Adam, one batch of the bench geometry."""
     import torch_oracle as O
     from kantts._hip import ops
     from kantts.models.sambert.kantts_sambert import KanTtsSAMBERT
     from kantts.train.loss import FpCELoss, MelReconLoss, ProsodyReconLoss, sambert_loss_sum
     from kantts.train.optim import ArenaAdam, ParamArena
 
-    assert torch.cuda.is_available(), "needs the GPU"
-    hip.set_precision("bf16")
     legs = {}
-    for fp in (True, False):
+    for fp in fps:
         cfg = dict(O.sambert_config(), FP=fp)
         torch.manual_seed(0)
         net = KanTtsSAMBERT(cfg).cuda().train()
@@ -220,7 +231,111 @@ def point_step(reps):
             opt.step()
             return total
 
-        legs[fp] = step
+        legs[fp] = (net, opt, batch, step)
+    return legs
+
+
+def _schedule_launches(torch, step, overlap):
+    """Device kernels and copies of the schedule ``step`` (a GraphedSambertStep) captured, from one uncaptured run of it
+    with the switches the capture had (``overlap``: weight gradients beside the chain / grouped)."""
+    from kantts._hip import deferred_tn, ops
+
+    prev = (ops.wgrad_overlap.enabled, deferred_tn.enabled, ops.side_branch.enabled)
+    ops.wgrad_overlap.enable(overlap, group_wgrads=overlap)
+
+    def run():
+        with torch.cuda.stream(step._cap_stream):
+            step._eager_step()
+
+    try:
+        step._cap_stream.wait_stream(torch.cuda.current_stream())
+        n = _launches(torch, run, host_side=True)
+    finally:
+        ops.wgrad_overlap.join()
+        ops.wgrad_overlap.enabled, deferred_tn.enabled, ops.side_branch.enabled = prev
+    return n
+
+
+def point_captured(reps, shape_batches=64):
+    import torch
+
+    import kantts._hip as hip
+    from kantts.models.sambert.kantts_sambert import fp_width_of
+    from kantts.train.graph_step import GraphedSambertStep
+    from kantts.train.loss import FpCELoss, MelReconLoss, ProsodyReconLoss
+    from kantts.train.scheduler import NoamLR
+
+    assert torch.cuda.is_available(), "needs the GPU"
+    hip.set_precision("bf16")
+    # the eager legs on models of their own, the captured legs on twins from the same seed (a captured step switches its
+    # model to the static path and its optimizer to device-side state)
+    eager, cap = _step_legs(torch), _step_legs(torch)
+    steps = {}
+    for fp in (True, False):
+        steps[("eager", fp)] = eager[fp][3]
+        net, opt, batch, _ = cap[fp]
+        kw = {}
+        if fp:
+            kw = dict(fp_criterion=FpCELoss(), fp_width=fp_width_of(batch["fp_label"].cpu(), batch["input_lengths"].cpu()))
+        steps[("captured", fp)] = GraphedSambertStep(net, opt, NoamLR(opt, warmup_steps=4000), MelReconLoss(),
+                                                     ProsodyReconLoss(), batch, **kw)
+    # a third captured leg: the twin with every weight gradient in line, as the FP step is captured (its text encoder runs
+    # twice per forward, so its parameters receive two gradients per backward: graph_step.py) -- what that form costs
+    net, opt, batch, _ = _step_legs(torch, fps=(False,))[False]
+    steps[("captured_inline_wgrad", False)] = GraphedSambertStep(net, opt, NoamLR(opt, warmup_steps=4000), MelReconLoss(),
+                                                                 ProsodyReconLoss(), batch, overlap_wgrad=False,
+                                                                 group_wgrads=False)
+    order = [("eager", True), ("captured", True), ("eager", False), ("captured", False), ("captured_inline_wgrad", False)]
+    for _ in range(5):
+        last = {k: steps[k]() for k in order}
+    torch.cuda.synchronize()
+    assert all(bool(torch.isfinite(v)) for v in last.values()), last
+    steps[("captured", True)].check_fp_status()
+    t = {k: [] for k in order}
+    for _ in range(reps):
+        for k in order:
+            t[k].append(_window(torch, steps[k], 10))
+    # launches per step: the eager legs from the profiler's device records; a captured step is one graph launch, so its
+    # NODES are counted by running the schedule it captured once more uncaptured (the same host code on the capture
+    # stream) and counting the runtime's launch / copy / fill calls
+    launches = {}
+    for k in order:
+        name = "%s_fp_%s" % (k[0], str(k[1]).lower())
+        if k[0] == "eager":
+            launches[name] = _launches(torch, steps[k])
+            launches[name + "_calls"] = _launches(torch, steps[k], host_side=True)  # the same number: the two counts agree
+        else:
+            launches[name] = _schedule_launches(torch, steps[k], k[0] == "captured" and not k[1])
+    steps[("captured", True)].check_fp_status()
+    # distinct captured shapes over a pass of seeded batches of this geometry (host only): the trainer keys its graphs on
+    # the shapes of the batch's tensors, to which FP adds T' (durations, pitch, energy) beside T and the mel length
+    keys_fp, keys_plain = set(), set()
+    for seed in range(100, 100 + shape_batches):
+        b = _fp_batch(torch, True, seed=seed, cuda=False)
+        keys_fp.add((b["inputs_ling"].size(1), b["duration_targets"].size(1), b["mel_targets"].size(1)))
+        keys_plain.add((b["duration_targets"].size(1), b["mel_targets"].size(1)))
+    med = {k: statistics.median(v) for k, v in t.items()}
+    return {"model": "full 16k SAM-BERT, bf16 mode, arena Adam",
+            "geometry": dict(B=B, T=T, T_out=eager[True][2]["duration_targets"].size(1)),
+            "fp_true_eager_ms": _stats(t[("eager", True)]), "fp_true_captured_ms": _stats(t[("captured", True)]),
+            "fp_false_eager_ms": _stats(t[("eager", False)]), "fp_false_captured_ms": _stats(t[("captured", False)]),
+            "fp_false_captured_inline_wgrad_ms": _stats(t[("captured_inline_wgrad", False)]),
+            "fp_cost_against_the_inline_wgrad_twin_ms": med[("captured", True)] - med[("captured_inline_wgrad", False)],
+            "eager_over_captured_fp_true": med[("eager", True)] / med[("captured", True)],
+            "fp_cost_inside_a_captured_step_ms": med[("captured", True)] - med[("captured", False)],
+            "device_launches_per_step": launches,
+            "captured_shapes": {"batches": shape_batches, "distinct_with_fp": len(keys_fp),
+                                "distinct_fp_false_twin": len(keys_plain), "lru": 16}}
+
+
+def point_step(reps):
+    import torch
+
+    import kantts._hip as hip
+
+    assert torch.cuda.is_available(), "needs the GPU"
+    hip.set_precision("bf16")
+    legs = {fp: leg[3] for fp, leg in _step_legs(torch).items()}
     for _ in range(5):
         a, b_ = legs[True](), legs[False]()
     assert bool(torch.isfinite(a)) and bool(torch.isfinite(b_))
@@ -264,7 +379,9 @@ def resources():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--point", choices=["insert", "step"])
+    ap.add_argument("--point", choices=["insert", "step", "captured"])
+    ap.add_argument("--only", choices=["insert", "step", "captured"], help="run this point alone and merge it into --out")
+    ap.add_argument("--shape_batches", type=int, default=64)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--resources", action="store_true")
     ap.add_argument("--out", default=OUT)
@@ -272,10 +389,17 @@ def main():
     if a.resources:
         return resources()
     if a.point:
-        print("RESULT " + json.dumps({"insert": point_insert, "step": point_step}[a.point](a.reps)))
+        fn = {"insert": point_insert, "step": point_step,
+              "captured": lambda reps: point_captured(reps, a.shape_batches)}[a.point]
+        print("RESULT " + json.dumps(fn(a.reps)))
         return
     result = {}
-    for point, limit in (("insert", 240), ("step", 300)):
+    if a.only and os.path.exists(a.out):
+        with open(a.out) as f:
+            result = json.load(f)
+    for point, limit in (("insert", 240), ("step", 300), ("captured", 420)):
+        if a.only and point != a.only:
+            continue
         r = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--point", point,
                             "--reps", str(a.reps)], capture_output=True, text=True)
         sys.stderr.write(r.stderr[-3000:])
