@@ -1872,6 +1872,36 @@ int kantts_spk_cam_gate_conv(const float* h, const int32_t* lens, const float* p
 int kantts_spk_tail(const float* x, const int32_t* lens, const float* scale, const float* shift, const float* w,
                     const float* oscale, const float* oshift, float* out, int B, int C, int CX, int TX, int E, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Device-resident corpus of duration-free (MAS) and speaker-embedding (SE) voices (csrc/attn_prior.hip): the two batch
+ * fields the collate of kantts/datasets/dataset.py builds per utterance on the host (:20-31 the beta-binomial alignment
+ * prior, :757-762 the utterance's speaker embedding repeated over its symbols, :798-827 their padding).
+ *
+ * kantts_attn_prior_rows: the padded prior of a whole batch in one launch; every cell of out (B, Tout, Tin) fp32 is
+ *   written (no memset in front).  With P = min(n_sym[b], Tin) -- the symbol count INCLUDING the trailing "~" -- and
+ *   M = min(n_mel[b], Tout):
+ *     out[b][i][k] = pmf of Beta-Binomial(P, i + 1, M - i) at k         for i < M and k < P
+ *                  = 0                                                  elsewhere
+ *   (the support point k = P is left out as in the reference, so a row does not sum to 1).  All gamma arguments are
+ *   positive integers; with lfact[n] = log n! (fp64, n < n_lfact) the cell is
+ *     exp(  lfact[P] - lfact[k] - lfact[P - k]
+ *         + lfact[k + i] + lfact[P - k + M - i - 1] - lfact[P + M]
+ *         - lfact[i] - lfact[M - i - 1] + lfact[M] )
+ *   summed and exponentiated in fp64 and rounded once to fp32.  An item with P < 1 or M < 1 is all zeros.  An item with
+ *   P + M >= n_lfact (the table does not reach it) gets NaN in its live cells and zeros elsewhere, and the table is not
+ *   read for it.  Nothing outside out (B, Tout, Tin) is written and nothing of lfact at or past n_lfact is read, whatever
+ *   n_sym / n_mel hold.  16-byte stores when out is 16-byte aligned.
+ *   BADARG: a NULL pointer, B / Tout / Tin < 1, n_lfact < 2.  UNSUPPORTED: B > 65535 or Tout * Tin >= 2^31.
+ *
+ * kantts_broadcast_rows_f32: out (B, Tmax, D)[b][t][:] = table (n, D)[item[b]][:] for t < min(len[b], Tmax), zeros
+ *   beyond; every cell of out is written, bit-exact copies.  item (B) int64, len (B) int32.  An item index outside [0, n)
+ *   gives a row of zeros (nothing is read for it).  16-byte stores when out is 16-byte aligned.
+ *   BADARG: a NULL pointer, B / Tmax / D / n < 1.  UNSUPPORTED: B > 65535 or Tmax * D >= 2^31. */
+int kantts_attn_prior_rows(const double* lfact, int n_lfact, const int32_t* n_sym, const int32_t* n_mel, float* out, int B,
+                           int Tout, int Tin, void* stream);
+int kantts_broadcast_rows_f32(const float* table, int n, const int64_t* item, const int32_t* len, float* out, int B, int Tmax,
+                              int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

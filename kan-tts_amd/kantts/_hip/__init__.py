@@ -588,6 +588,9 @@ def lib():
             L.kantts_fsmn_memory_drop_bwd_pair.argtypes = [POINTER(FsmnDropArgs), POINTER(FsmnDropArgs), p, i, i, i, i, i, p, p]
             L.kantts_bilstm_pair_fwd.argtypes = [POINTER(BiLstmArgs), POINTER(BiLstmArgs), p, i, i, i, i, p]
             L.kantts_bilstm_pair_bwd.argtypes = [POINTER(BiLstmArgs), POINTER(BiLstmArgs), p, i, i, i, i, p]
+        if all(hasattr(L, s) for s in CORPUS_PRIOR_SYMBOLS):  # has_corpus_prior(): a library built before them still loads
+            L.kantts_attn_prior_rows.argtypes = [p, i, p, p, p, i, i, i, p]
+            L.kantts_broadcast_rows_f32.argtypes = [p, i, p, p, p, i, i, i, p]
         _lib = L
     return _lib
 
@@ -601,6 +604,9 @@ SPK_SYMBOLS = ("kantts_kaldi_fbank", "kantts_spk_conv2d", "kantts_spk_conv1d", "
 PREDICTOR_PAIR_SYMBOLS = ("kantts_bgemm_nt_pair", "kantts_ffn_pair2", "kantts_fsmn_memory_drop_fwd_pair",
                           "kantts_fsmn_memory_drop_bwd_pair", "kantts_bilstm_pair_fwd",
                           "kantts_bilstm_pair_bwd")  # two problems of one shape per launch (the pitch / energy predictors)
+
+
+CORPUS_PRIOR_SYMBOLS = ("kantts_attn_prior_rows", "kantts_broadcast_rows_f32")  # MAS / SE batch fields (csrc/attn_prior.hip)
 
 
 def predictor_pair_entry_points():
@@ -637,6 +643,7 @@ EXPORTED_SYMBOLS = [
     *SPK_SYMBOLS,
     "kantts_fsmn_memory_drop_fwd", "kantts_fsmn_memory_drop_bwd",
     *PREDICTOR_PAIR_SYMBOLS,
+    *CORPUS_PRIOR_SYMBOLS,
 ]
 
 
@@ -1986,6 +1993,76 @@ def ragged_rows(src, row_off, lens, Tmax, *, start=None, pad=None, transpose=Fal
     fn = {torch.float32: "kantts_ragged_rows_f32", torch.int64: "kantts_ragged_rows_i64"}[src.dtype]
     check(getattr(lib(), fn)(ptr(src), ptr(row_off, torch.int64), ptr(start, torch.int32), ptr(lens, torch.int32),
                              ptr(pad, src.dtype), ptr(out), B, int(Tmax), C, int(bool(transpose)), stream()), fn)
+    return out
+
+
+def has_corpus_prior():
+    """True when the loaded library exports the batch fields of a device-resident MAS / SE corpus (csrc/attn_prior.hip:
+    the alignment prior and the broadcast speaker embedding)."""
+    return all(hasattr(lib(), s) for s in CORPUS_PRIOR_SYMBOLS)
+
+
+def log_factorials(n, device):
+    """lfact[k] = log k! for k = 0 .. n as an fp64 tensor on ``device``: the table kantts_attn_prior_rows evaluates the
+    beta-binomial prior from (every gamma argument of the prior is a positive integer)."""
+    import numpy as np
+    from scipy.special import gammaln
+
+    return torch.from_numpy(gammaln(np.arange(int(n) + 1, dtype=np.float64) + 1.0)).to(device)
+
+
+def attn_prior_rows_raw(lfact, n_lfact, n_sym, n_mel, out, *, B, Tout, Tin):
+    """kantts_attn_prior_rows as it is: n_sym / n_mel int32 DEVICE tensors, nothing checked; returns its code."""
+    return lib().kantts_attn_prior_rows(ptr(lfact, torch.float64), int(n_lfact), ptr(n_sym, torch.int32),
+                                        ptr(n_mel, torch.int32), ptr(out, torch.float32), int(B), int(Tout), int(Tin),
+                                        stream())
+
+
+def attn_prior_rows(lfact, n_sym, n_mel, Tout, Tin, *, n_sym_dev=None, n_mel_dev=None):
+    """The zero-padded beta-binomial alignment prior of a batch in one launch (csrc/attn_prior.hip): out (B, Tout, Tin) fp32
+    with out[b, :n_mel[b], :n_sym[b]] = ``beta_binomial_prior_distribution(n_sym[b], n_mel[b])`` (fp64 arithmetic, rounded
+    once) and zeros elsewhere.  ``lfact``: the device table of ``log_factorials``; ``n_sym`` (symbols INCLUDING the
+    trailing "~") / ``n_mel``: HOST integers, one per item.  A batch the table or the output does not cover is refused
+    here, before any launch.  ``n_sym_dev`` / ``n_mel_dev``: the same lengths as (B) int32 device tensors where the caller
+    has uploaded them already (they are uploaded here otherwise)."""
+    import numpy as np
+
+    n_sym, n_mel = np.asarray(n_sym, dtype=np.int64).reshape(-1), np.asarray(n_mel, dtype=np.int64).reshape(-1)
+    B, n = int(n_sym.shape[0]), int(lfact.numel())
+    if B < 1 or n_mel.shape[0] != B:
+        raise ValueError("attn_prior_rows: n_sym / n_mel must name the same items, at least one")
+    if int(n_sym.min()) < 1 or int(n_mel.min()) < 1 or int(n_sym.max()) > int(Tin) or int(n_mel.max()) > int(Tout):
+        raise ValueError("attn_prior_rows: lengths must lie in [1, Tin = %d] / [1, Tout = %d]" % (int(Tin), int(Tout)))
+    if int((n_sym + n_mel).max()) >= n:
+        raise ValueError("attn_prior_rows: the log-factorial table has %d entries, an item of this batch needs %d "
+                         "(n_sym + n_mel + 1)" % (n, int((n_sym + n_mel).max()) + 1))
+    dev = lfact.device
+    out = torch.empty((B, int(Tout), int(Tin)), device=dev, dtype=torch.float32)
+    for t in (n_sym_dev, n_mel_dev):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != B or t.device != dev):
+            raise ValueError("attn_prior_rows: n_sym_dev / n_mel_dev must be (B = %d) int32 tensors on %s" % (B, dev))
+    if n_sym_dev is None:
+        n_sym_dev = torch.as_tensor(n_sym, dtype=torch.int32).to(dev)
+    if n_mel_dev is None:
+        n_mel_dev = torch.as_tensor(n_mel, dtype=torch.int32).to(dev)
+    check(attn_prior_rows_raw(lfact, n, n_sym_dev, n_mel_dev, out, B=B, Tout=Tout, Tin=Tin), "attn_prior_rows")
+    return out
+
+
+def broadcast_rows_raw(table, item, lens, out, *, n, B, Tmax, D):
+    """kantts_broadcast_rows_f32 as it is; returns its code."""
+    return lib().kantts_broadcast_rows_f32(ptr(table, torch.float32), int(n), ptr(item, torch.int64), ptr(lens, torch.int32),
+                                           ptr(out, torch.float32), int(B), int(Tmax), int(D), stream())
+
+
+def broadcast_rows(table, item, lens, Tmax):
+    """out (B, Tmax, D) fp32 with out[b, t] = table[item[b]] for t < lens[b] and zeros beyond (csrc/attn_prior.hip): an
+    utterance's speaker embedding repeated over its symbols.  table (n, D) fp32, item (B) int64, lens (B) int32 device
+    tensors."""
+    n, D = int(table.shape[0]), int(table.shape[1])
+    B = int(item.shape[0])
+    out = torch.empty((B, int(Tmax), D), device=table.device, dtype=torch.float32)
+    check(broadcast_rows_raw(table, item, lens, out, n=n, B=B, Tmax=Tmax, D=D), "broadcast_rows")
     return out
 
 

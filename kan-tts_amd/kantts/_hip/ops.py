@@ -27,11 +27,30 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def distinct_stream(priority=None):
+    """A stream from torch's pool that is neither the current stream nor one of this module's helper streams
+    (``helper_streams()``).  The pool hands out 32 streams per priority round-robin, so the n-th and the (n + 32)-th
+    ``torch.cuda.Stream()`` of a process are the SAME HIP stream, and which one a role gets depends on everything the
+    process did before.  Two roles of one captured step on one stream (say the attention side stream and the
+    weight-gradient stream, created a multiple of 32 allocations apart) break ``hipStreamEndCapture``.  So every helper
+    role and every capture stream asks here: the helper roles are pairwise distinct, and a capture stream is distinct from
+    all of them.  Capture streams themselves are not remembered: a helper role created while a step is being built sees
+    that step's capture stream as the current stream; one created later in eager code may share a pool stream with the
+    capture stream of an earlier step, which forks nothing onto it.  Raises when two rounds of the pool offer no free
+    stream (more roles than the pool has streams) rather than handing out a taken one."""
+    taken = {st.cuda_stream for st in helper_streams()} | {torch.cuda.current_stream().cuda_stream}
+    for _ in range(64):
+        st = torch.cuda.Stream() if priority is None else torch.cuda.Stream(priority=int(priority))
+        if st.cuda_stream not in taken:
+            return st
+    raise RuntimeError("no free stream in torch's pool: %d streams are the current stream or helper streams of kantts._hip.ops"
+                       % len(taken))
+
+
 def _new_side_stream():
     """Streams of work that runs BESIDE the step's critical path (deferred weight gradients, the variance-predictor branch).
     KANTTS_SIDE_PRIORITY (experiment switch): HIP stream priority, larger = lower; default: the device default."""
-    pr = os.environ.get("KANTTS_SIDE_PRIORITY")
-    return torch.cuda.Stream(priority=int(pr)) if pr else torch.cuda.Stream()
+    return distinct_stream(os.environ.get("KANTTS_SIDE_PRIORITY") or None)
 
 
 class _ZeroPool:
@@ -789,7 +808,7 @@ def _pair_on_two_streams(fn_main, fn_side, side_inputs=()):
             or not any(torch.is_tensor(t) and t.is_cuda for t in side_inputs)):
         return fn_main(), fn_side()
     if not _attn_side_stream:
-        _attn_side_stream.append(torch.cuda.Stream())
+        _attn_side_stream.append(distinct_stream())
     side, main = _attn_side_stream[0], torch.cuda.current_stream()
     side.wait_stream(main)
     for t in side_inputs:
@@ -833,7 +852,7 @@ def run_beside(fn_main, fn_side, side_inputs=()):
         rs = fn_side()  # same host order as below: dropout seeds are drawn in issue order
         return fn_main(), rs
     if not _attn_side_stream:
-        _attn_side_stream.append(torch.cuda.Stream())
+        _attn_side_stream.append(distinct_stream())
     side, main = _attn_side_stream[0], torch.cuda.current_stream()
     side.wait_stream(main)
     for t in side_inputs:

@@ -242,6 +242,10 @@ class AM_Dataset(torch.utils.data.Dataset):
         self.padder = Padder()
         self.allow_cache = allow_cache
         self.caches = {}
+        # duration-free items carry the beta-binomial prior (slot 5) unless this is switched off: a consumer that evaluates
+        # the prior itself (the device-resident corpus, device_batching.make_train_loader) then gets ``None`` there and no
+        # M x P matrix is computed per utterance; such items are not cached
+        self.attach_prior = True
 
     def __len__(self):
         return len(self.meta)
@@ -280,7 +284,8 @@ class AM_Dataset(torch.utils.data.Dataset):
 
     def __getitem__(self, idx):
         if self.allow_cache and idx in self.caches:
-            return self.caches[idx]
+            item = self.caches[idx]
+            return item if self.attach_prior else item[:5] + (None,) + item[6:]
         ling_txt, mel_file, dur_file, f0_file, energy_file, frame_f0_file, frame_uv_file, aug_txt, se_path = self.meta[idx]
         ling_data = self.ling_unit.encode_symbol_sequence(ling_txt)
         mel_data = np.load(mel_file)
@@ -288,7 +293,9 @@ class AM_Dataset(torch.utils.data.Dataset):
         f0_data = np.load(f0_file)
         energy_data = np.load(energy_file)
         se_data = np.load(se_path) if self.se_enable else None
-        attn_prior = None if self.with_duration else beta_binomial_prior_distribution(len(ling_data[0]), mel_data.shape[0])
+        attn_prior = None
+        if not self.with_duration and self.attach_prior:
+            attn_prior = beta_binomial_prior_distribution(len(ling_data[0]), mel_data.shape[0])
         if self.nsf_enable:
             frame_f0 = np.load(frame_f0_file).reshape(-1, 1)  # stored mean / std normalised
             if self.nsf_norm_type == "global":
@@ -299,7 +306,7 @@ class AM_Dataset(torch.utils.data.Dataset):
             mel_data = np.concatenate([mel_data, frame_f0, np.load(frame_uv_file).reshape(-1, 1)], axis=1)
         fp_label = get_fp_label(aug_txt) if (self.fp_enable and aug_txt is not None) else None
         item = (ling_data, mel_data, dur_data, f0_data, energy_data, attn_prior, fp_label, se_data)
-        if self.allow_cache:
+        if self.allow_cache and (self.with_duration or self.attach_prior):
             self.caches[idx] = item
         return item
 

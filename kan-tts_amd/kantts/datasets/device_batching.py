@@ -14,7 +14,13 @@ corpus (10 h of 22.05 kHz audio and its 80-bin mels is ~4 GB) fits next to the m
 ``PinnedPrefetcher`` is the other half of the row for corpora that stay on the host: it stages the NEXT host batch in
 pinned memory and copies it on a side stream while the current step runs (double-buffered; what
 ``GraphedSambertStep.load_batch`` / ``GraphedGanStep.load_batch`` consume).
+
+Every shipped SAM-BERT training configuration except the byte-input one can train from a resident corpus: duration-
+supervised voices, filled-pause voices, duration-free (MAS) voices -- whose alignment prior is evaluated on the device per
+batch instead of per utterance on the host -- and speaker-embedding (SE) voices (csrc/attn_prior.hip).
 """
+import logging
+
 import numpy as np
 import torch
 
@@ -74,33 +80,71 @@ class DeviceVocSet:
 
 
 class DeviceAMSet:
-    """Acoustic-model training set in HBM (duration-supervised items of AM_Dataset.__getitem__: (ling_data, mel, dur, f0,
-    energy, attn_prior, fp_label, se) with ling_data = six integer streams incl. the trailing "~").  ``batch(indices)``
-    == ``am_collate([items[i] for i in indices], r, pad_ids)`` with device tensors.  ``fp``: filled-pause items -- the
-    batch carries ``fp_label`` (padded with 0 to the input width) and pitch / energy as wide as the durations, as
+    """Acoustic-model training set in HBM (items of AM_Dataset.__getitem__: (ling_data, mel, dur, f0, energy, attn_prior,
+    fp_label, se) with ling_data = six integer streams incl. the trailing "~").  ``batch(indices)``
+    == ``am_collate([items[i] for i in indices], r, pad_ids, se=se, fp=fp)`` with device tensors.
+
+    Duration-supervised items carry the host integer ``band_width`` along.  ``fp``: filled-pause items -- the batch carries
+    ``fp_label`` (padded with 0 to the input width) and pitch / energy as wide as the durations, as
     ``am_collate(..., fp=True)`` gives them, plus the host integers ``band_width`` (over the inter lengths) and
-    ``fp_width`` (T', which equals the width of the durations for items whose durations describe the inserted sequence)."""
+    ``fp_width`` (T', which equals the width of the durations for items whose durations describe the inserted sequence).
+
+    Duration-free (MAS) items -- slot 2 ``None`` for EVERY item -- give ``durations = None``, FRAME-level pitch / energy at
+    the width of the mel, and ``attn_priors`` (B, max_out, max_in): the beta-binomial prior is a function of two integers
+    per utterance, so it is evaluated on the device per batch (``kantts._hip.attn_prior_rows``, one launch, from a table of
+    log-factorials that is uploaded once) and slot 5, the host prior, is never looked at (it may be ``None``:
+    ``AM_Dataset.attach_prior``).  No ``band_width``: the trainer uses the wide-band form for MAS.
+
+    ``se``: speaker-embedding voices -- ``input_speakers`` is the float (B, max_in, D) tensor of ``am_collate(..., se=True)``:
+    slot 7 of every item ((1, D) or (D,)) is uploaded once as an (n_items, D) table and broadcast over the item's symbols
+    per batch (``kantts._hip.broadcast_rows``)."""
 
     KEYS = ("input_lings", "input_emotions", "input_speakers", "valid_input_lengths", "valid_output_lengths",
             "mel_targets", "durations", "pitch_contours", "energy_contours", "attn_priors")
 
-    def __init__(self, items, r, pad_ids, device, fp=False):
-        if any(it[2] is None for it in items):
-            raise NotImplementedError("duration-free (MAS) items carry a per-batch prior: use the host collate")
-        self.r, self.device, self.fp = int(r), torch.device(device), bool(fp)
+    def __init__(self, items, r, pad_ids, device, fp=False, se=False):
+        free = [it[2] is None for it in items]
+        self.mas = bool(items) and all(free)
+        if any(free) and not self.mas:
+            # the host collate would treat a batch with ONE such item as duration-free and drop the others' durations
+            raise ValueError("duration-supervised and duration-free (MAS) items in one set: %d of %d items have no "
+                             "durations" % (sum(free), len(items)))
+        if self.mas and fp:
+            raise NotImplementedError("FP together with MAS is not a shipped configuration")
+        if (self.mas or se) and not hip.has_corpus_prior():
+            raise RuntimeError("libkantts_hip.so does not export %s: rebuild it (a device-resident MAS / SE corpus needs "
+                               "them)" % ", ".join(hip.CORPUS_PRIOR_SYMBOLS))
+        self.r, self.device, self.fp, self.se = int(r), torch.device(device), bool(fp), bool(se)
         self.n_sym = np.array([len(it[0][0]) for it in items], dtype=np.int64)
         self.n_mel = np.array([len(it[1]) for it in items], dtype=np.int64)
-        self.n_dur = np.array([it[2].shape[0] for it in items], dtype=np.int64)
-        self.frames = np.array([int(np.sum(it[2])) for it in items], dtype=np.int64)
         self.ling, self.sym_off = _flat([np.stack([np.asarray(s) for s in it[0]], axis=1) for it in items], np.int64,
                                         self.device)
         self.mel, self.mel_off = _flat([it[1] for it in items], np.float32, self.device)
-        self.dur, self.dur_off = _flat([np.asarray(it[2]).reshape(-1, 1) for it in items], np.int64, self.device)
         self.f0, self.f0_off = _flat([np.asarray(it[3]).reshape(-1, 1) for it in items], np.float32, self.device)
         self.energy, self.en_off = _flat([np.asarray(it[4]).reshape(-1, 1) for it in items], np.float32, self.device)
         self.n_f0 = np.array([len(it[3]) for it in items], dtype=np.int64)
         self.n_en = np.array([len(it[4]) for it in items], dtype=np.int64)
         self.pad_ids = torch.as_tensor(list(pad_ids), dtype=torch.int64).to(self.device)
+        if self.se:
+            emb = [None if it[7] is None else np.asarray(it[7], dtype=np.float32).reshape(-1) for it in items]
+            if any(e is None for e in emb):
+                raise ValueError("se=True: item %d carries no speaker embedding (slot 7)" % [e is None for e in emb].index(True))
+            if len({e.shape[0] for e in emb}) != 1 or emb[0].shape[0] < 1:
+                raise ValueError("se=True: the speaker embeddings differ in size: %s" % sorted({e.shape[0] for e in emb}))
+            self.emb = torch.from_numpy(np.stack(emb)).to(self.device)  # (n_items, D)
+        if self.mas:
+            # the host collate pads pitch / energy to the width of the mel: np.pad raises on a longer one
+            width = np.array([Padder()._round_up(int(n), self.r) for n in self.n_mel], dtype=np.int64)
+            for name, n in (("pitch", self.n_f0), ("energy", self.n_en)):
+                if np.any(n > width):
+                    i = int(np.argmax(n > width))
+                    raise ValueError("item %d: %d frames of %s for a mel of %d frames (%d at r = %d)" % (
+                        i, int(n[i]), name, int(self.n_mel[i]), int(width[i]), self.r))
+            self.lfact = hip.log_factorials(int((self.n_sym + self.n_mel).max()), self.device)
+            return
+        self.n_dur = np.array([it[2].shape[0] for it in items], dtype=np.int64)
+        self.frames = np.array([int(np.sum(it[2])) for it in items], dtype=np.int64)
+        self.dur, self.dur_off = _flat([np.asarray(it[2]).reshape(-1, 1) for it in items], np.int64, self.device)
         # longest duration among an utterance's real symbols (the trailing "~" excluded), on the host: a batch's attention
         # band width (kantts_sambert.py:981-985) without reading the device batch back
         # (FP: the model masks the duration targets with the INTER lengths, len - 1 + 3 n_fp, which may reach past an item's
@@ -134,31 +178,43 @@ class DeviceAMSet:
     def batch(self, indices):
         idx = np.asarray(indices, dtype=np.int64)
         d = self.device
+        B = len(idx)
         max_in = int(self.n_sym[idx].max())
-        max_dur = int(self.n_dur[idx].max()) + 1
         max_out = Padder()._round_up(int(self.n_mel[idx].max()), self.r)
         i32 = lambda a: _dev(a, torch.int32, d)  # noqa: E731
         i64 = lambda a: _dev(a, torch.int64, d)  # noqa: E731
-        ling = hip.ragged_rows(self.ling, i64(self.sym_off[idx]), i32(self.n_sym[idx]), max_in, pad=self.pad_ids)
+        n_sym32 = i32(self.n_sym[idx])
+        ling = hip.ragged_rows(self.ling, i64(self.sym_off[idx]), n_sym32, max_in, pad=self.pad_ids)
         out = {"input_lings": ling[:, :, :4].contiguous(), "input_emotions": ling[:, :, 4].contiguous(),
                "input_speakers": ling[:, :, 5].contiguous()}
+        if self.se:  # the utterance's embedding over its symbols ("~" included), zeros behind them
+            out["input_speakers"] = hip.broadcast_rows(self.emb, i64(idx), n_sym32, max_in)
         out["valid_input_lengths"] = i64(self.n_sym[idx] - 1)  # minus "~"
         out["valid_output_lengths"] = i64(self.n_mel[idx])
-        out["mel_targets"] = hip.ragged_rows(self.mel, i64(self.mel_off[idx]), i32(self.n_mel[idx]), max_out)
-        dur = hip.ragged_rows(self.dur, i64(self.dur_off[idx]), i32(self.n_dur[idx]), max_dur).view(len(idx), max_dur)
-        # Padder._pad_durations (:47-64): the frames that pad the mel to a multiple of r belong to the slot after the last
-        # symbol -- B values, computed on the host from the cached frame counts
-        extra = np.where(self.frames[idx] < max_out, max_out - self.frames[idx], 0)
-        dur.scatter_add_(1, i64(self.n_dur[idx]).view(-1, 1), i64(extra).view(-1, 1))
-        out["durations"] = dur
-        feat = max_dur if self.fp else max_in  # FP: pitch / energy describe the sequence after the insertion
-        out["pitch_contours"] = hip.ragged_rows(self.f0, i64(self.f0_off[idx]), i32(self.n_f0[idx]), feat).view(len(idx), feat)
-        out["energy_contours"] = hip.ragged_rows(self.energy, i64(self.en_off[idx]), i32(self.n_en[idx]), feat).view(len(idx), feat)
+        n_mel32 = i32(self.n_mel[idx])
+        out["mel_targets"] = hip.ragged_rows(self.mel, i64(self.mel_off[idx]), n_mel32, max_out)
+        if self.mas:
+            out["durations"] = None
+            feat = max_out  # frame-level pitch / energy (averaged per phoneme inside the model)
+        else:
+            max_dur = int(self.n_dur[idx].max()) + 1
+            dur = hip.ragged_rows(self.dur, i64(self.dur_off[idx]), i32(self.n_dur[idx]), max_dur).view(B, max_dur)
+            # Padder._pad_durations (:47-64): the frames that pad the mel to a multiple of r belong to the slot after the
+            # last symbol -- B values, computed on the host from the cached frame counts
+            extra = np.where(self.frames[idx] < max_out, max_out - self.frames[idx], 0)
+            dur.scatter_add_(1, i64(self.n_dur[idx]).view(-1, 1), i64(extra).view(-1, 1))
+            out["durations"] = dur
+            feat = max_dur if self.fp else max_in  # FP: pitch / energy describe the sequence after the insertion
+        out["pitch_contours"] = hip.ragged_rows(self.f0, i64(self.f0_off[idx]), i32(self.n_f0[idx]), feat).view(B, feat)
+        out["energy_contours"] = hip.ragged_rows(self.energy, i64(self.en_off[idx]), i32(self.n_en[idx]), feat).view(B, feat)
         out["attn_priors"] = None
+        if self.mas:
+            out["attn_priors"] = hip.attn_prior_rows(self.lfact, self.n_sym[idx], self.n_mel[idx], max_out, max_in,
+                                                     n_sym_dev=n_sym32, n_mel_dev=n_mel32)
+            return out
         out["band_width"] = self.band_width(idx)  # host integer (Sambert_Trainer: captured-step class of the batch)
         if self.fp:
-            out["fp_label"] = hip.ragged_rows(self.fp_label, i64(self.fp_off[idx]), i32(self.n_sym[idx]),
-                                              max_in).view(len(idx), max_in)
+            out["fp_label"] = hip.ragged_rows(self.fp_label, i64(self.fp_off[idx]), n_sym32, max_in).view(B, max_in)
             lens = self.n_sym[idx] - 1
             out["fp_width"] = int(max_in + (lens + 3 * self.n_fp[idx]).max() - lens.max())  # T' (host integer)
         return out
@@ -303,8 +359,10 @@ def make_train_loader(kind, dataset, host_loader, device, batch_size, sampler=No
     """``--device_corpus`` of the training entry points.  ``mode``: "hbm" = upload ``dataset`` once and assemble batches on
     the device (DeviceCorpusLoader); "pinned" = keep the host DataLoader and stage / copy its batches one step ahead
     (PinnedPrefetcher); "auto" = "hbm" when the payload takes less than half of the free device memory, else "pinned";
-    "off" = ``host_loader`` as the reference builds it.  ``kind``: "am" (dataset items of AM_Dataset, duration-supervised)
-    or "voc" (Voc_Dataset)."""
+    "off" = ``host_loader`` as the reference builds it.  ``kind``: "am" (AM_Dataset: duration-supervised, filled-pause,
+    duration-free (MAS) and speaker-embedding (SE) voices) or "voc" (Voc_Dataset).  A MAS dataset is materialised with
+    ``attach_prior`` off (restored afterwards): its prior is evaluated on the device.  With a library built before the MAS /
+    SE entry points, "auto" / "hbm" log why and stage host batches ("pinned") for those voices."""
     device = torch.device(device)
     if mode == "off":
         return host_loader
@@ -316,21 +374,37 @@ def make_train_loader(kind, dataset, host_loader, device, batch_size, sampler=No
     if device.type != "cuda":
         return host_loader
     r = getattr(dataset, "r", None) if kind == "am" else None
-    if kind == "am" and getattr(dataset, "mas_enable", False):
-        return PinnedPrefetcher(host_loader, device)  # MAS items carry a per-batch prior: host collate
+    mas = kind == "am" and bool(getattr(dataset, "mas_enable", False))
+    se = kind == "am" and bool(getattr(dataset, "se_enable", False))
+    if mas:
+        r = None  # no durations in a MAS batch: nothing to take a band width from
+    if mode in ("auto", "hbm") and (mas or se) and not hip.has_corpus_prior():
+        logging.warning("--device_corpus %s: this libkantts_hip.so does not export %s, which a device-resident %s corpus "
+                        "needs; staging host batches instead (pinned)", mode, ", ".join(hip.CORPUS_PRIOR_SYMBOLS),
+                        "MAS" if mas else "SE")
+        mode = "pinned"
     if mode in ("auto", "hbm"):
-        if mode == "auto":
-            # decide from a SAMPLE before materialising the corpus: loading every item only to fall back to the prefetcher
-            # paid the whole load time and held the corpus in host memory
-            n = len(dataset)
-            probe = [dataset[i] for i in sorted({int(j * (n - 1) / 15) for j in range(16)})] if n else []
-            free, _ = torch.cuda.mem_get_info(device)
-            if probe and corpus_bytes(probe) / len(probe) * n > free // 2:
-                return PinnedPrefetcher(host_loader, device, r=r)
-        items = [dataset[i] for i in range(len(dataset))]
+        # a MAS item's host prior (an M x P fp64 matrix per utterance) is never uploaded: do not compute it for the items
+        # that only pass through here (AM_Dataset.attach_prior; the host loader of "pinned" / "off" keeps it)
+        attach = getattr(dataset, "attach_prior", None)
+        if mas and attach is not None:
+            dataset.attach_prior = False
+        try:
+            if mode == "auto":
+                # decide from a SAMPLE before materialising the corpus: loading every item only to fall back to the
+                # prefetcher paid the whole load time and held the corpus in host memory
+                n = len(dataset)
+                probe = [dataset[i] for i in sorted({int(j * (n - 1) / 15) for j in range(16)})] if n else []
+                free, _ = torch.cuda.mem_get_info(device)
+                if probe and corpus_bytes(probe) / len(probe) * n > free // 2:
+                    return PinnedPrefetcher(host_loader, device, r=r)
+            items = [dataset[i] for i in range(len(dataset))]
+        finally:
+            if mas and attach is not None:
+                dataset.attach_prior = attach
         if kind == "am":
             pad_ids = [dataset.ling_unit._sub_unit_pad[t] for t in dataset.ling_unit._lfeat_type_list]
-            dset = DeviceAMSet(items, dataset.r, pad_ids, device, fp=fp)
+            dset = DeviceAMSet(items, dataset.r, pad_ids, device, fp=fp, se=se)
         else:
             dset = DeviceVocSet(items, dataset.hop_length, dataset.batch_max_steps, device)
         return DeviceCorpusLoader(dset, batch_size, sampler=sampler, shuffle=sampler is None,

@@ -100,7 +100,9 @@ class GraphedGanStep:
         buf_snap = [b.clone() for b in bufs]  # e.g. the spectral_norm power-iteration vectors of follow_official_norm
         draws = None if self._source is None else self._source._draw_words[1:].clone()  # int64: not among the buffers above
         # one stream for warm-up and capture (AccumulateGrad nodes replay on the stream they were created on)
-        self._cap_stream = torch.cuda.Stream()
+        from kantts._hip import ops
+
+        self._cap_stream = ops.distinct_stream()  # not one of the branch streams the step forks
         self._cap_stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self._cap_stream):
             for _ in range(warmup):

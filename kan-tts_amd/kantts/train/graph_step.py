@@ -127,7 +127,7 @@ class GraphedSambertStep:
         # captured step sat on a foreign stream, forked from and joined back into the capture (autograd's "AccumulateGrad
         # node's stream does not match" warning) -- and a capture cut in the middle of backward could not end.
         pr = os.environ.get("KANTTS_MAIN_PRIORITY")  # experiment switch: priority of the capture (critical-path) stream
-        self._cap_stream = torch.cuda.Stream(priority=int(pr)) if pr else torch.cuda.Stream()
+        self._cap_stream = ops.distinct_stream(pr or None)  # not one of the helper streams the step forks
         self._cap_stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self._cap_stream):
             for _ in range(warmup):
