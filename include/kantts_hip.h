@@ -149,14 +149,28 @@ int kantts_layernorm_bwd(const float* dy, const float* x, const float* gamma, co
 /* ------------------------------------------------------------------------------------------
  * Range-limited multi-head attention, d_head = 16.  Replaces ScaledDotProductAttention and the mask
  * tensors (kantts/models/sambert/__init__.py:17-29,85-100; kantts_sambert.py:135-166).
- * q/k/v/o/d*: element (b,t,h,d) at ptr[(b*L+t)*ld + h*16 + d].  mode 0: key padding (encoder),
- * 1: PNCA x (causal band [i-bw, i]), 2: PNCA h (look-ahead band [i, i+bw]); lens (B) int32 = valid
- * positions per sequence (NULL: all); bw_dev: optional device scalar overriding bw.
- * lse: (B,H,L) saved; probs: optional (H*B, L, L) post-dropout probabilities (reference layout).
- * Band modes: rows of padded queries (t >= lens[b]) are un-masked in the reference but zeroed by every
- * caller; they are computed only when probs is requested, otherwise their context is 0, and they never
- * receive / produce gradients.
- * Backward writes dq (or adds to it when accumulate_dq), dk, dv; dvec (B,H,L) is scratch. */
+ * q/k/v/o/d*: element (b,t,h,d) at ptr[(b*L+t)*ld + h*16 + d]; every ld is a multiple of 4 and every base pointer
+ * 16-byte aligned (KANTTS_E_BADARG for an ld that is not; d_head != 16: KANTTS_E_UNSUPPORTED); nothing else of a row is
+ * read or written.  lens (B) int32 = valid positions per sequence, 0 <= len <= L (NULL: len = L); bw_dev: optional device
+ * scalar overriding bw.  bw >= 0; a host bw of L or more means the whole sequence (any int), a width read from device
+ * memory (bw_dev, bw_seq of kantts_attn_decode) must be below 2^30.
+ * Query i of sequence b attends to the keys j of the interval [lo, hi]:
+ *   mode 0 (key padding, encoder):   [0, len-1] for EVERY i, padded query rows (i >= len) included
+ *   mode 1 (PNCA x, causal band):    [max(0, i-bw), i]              if i < len, else [0, L-1]
+ *   mode 2 (PNCA h, look-ahead band): [i, min(i+bw, L-1, len-1)]     if i < len, else [0, L-1]
+ * s_j = 0.25 * q_i . k_j (= 1/sqrt(d_head)), p_j = softmax of s over [lo, hi], lse_i = log sum_j exp(s_j),
+ * o_i = sum_j p_j * m_j * v_j with the dropout scale m_j = rng(seed + *seed_dev, ((h*B+b)*L+i)*L+j) in {0, 1/(1-drop_p)}
+ * (1 when drop_p = 0; seed_dev: optional device word).  An empty interval (mode 0, len = 0): o_i = 0, lse_i = 0.
+ * lse: (B,H,L) saved; probs: optional (H*B, L, L) post-dropout probabilities p_j * m_j (reference layout), 0 outside
+ * [lo, hi].
+ * Band modes: rows of padded queries (i >= len) are un-masked in the reference ([0, L-1] above) but zeroed by every
+ * caller; they are computed only when probs is requested, otherwise their context and lse are 0, and they never
+ * receive / produce gradients in the backward.  Mode 0 computes padded query rows like any other row, forward and backward.
+ * Backward, from d_o and the o / lse of the forward: D_i = d_o_i . o_i, dp_j = m_j * (d_o_i . v_j),
+ * ds_j = 0.25 * p_j * (dp_j - D_i); dq_i = sum_j ds_j k_j, dk_j = sum_i ds_j q_i, dv_j = sum_i p_j m_j d_o_i, the sums over i
+ * running over the queries whose interval holds j (band modes: i < len only).  Writes dq (or adds to it when
+ * accumulate_dq), dk, dv -- every row of all three, zeros where nothing contributes (dq of a padded query row in the
+ * band modes: 0, or unchanged under accumulate_dq); dvec (B,H,L) is scratch. */
 int kantts_attn_fwd(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, float* o, int ldo,
                     float* lse, float* probs, const int32_t* lens, const int32_t* bw_dev, int bw, int B, int H,
                     int L, int d_head, int mode, float drop_p, uint64_t seed, const uint64_t* seed_dev,
@@ -184,6 +198,26 @@ int kantts_pnca_attn_bwd(const float* qkv, const float* hkv, int ldh, const floa
                          const float* d_oh, const float* lse_x, const float* lse_h, float* dqkv, float* dqh, float* dhkv,
                          const int32_t* lens, const int32_t* bw_dev, int bw_x, int bw_h, int B, int H, int L, int d_head,
                          float drop_p, uint64_t seed_x, uint64_t seed_h, const uint64_t* seed_dev, void* stream);
+
+/* Which kernels the four entry points above use for sequences of L positions, without launching (host only; the launchers
+ * take their choice from the same function, the per-process switches KANTTS_ATTN_NO_QUAD / KANTTS_ATTN_NO_DQ2 included).
+ * pass: KANTTS_ATTN_PASS_*; mode as above (ignored for the PNCA passes).  Returns a KANTTS_ATTN_* path,
+ * KANTTS_E_UNSUPPORTED where the entry point refuses (PNCA forward L >= 410, PNCA backward L >= 391), KANTTS_E_BADARG for
+ * an unknown pass / mode or L < 0.  A head is LDS-staged while its row images fit 64 KB. */
+#define KANTTS_ATTN_PASS_FWD 0
+#define KANTTS_ATTN_PASS_BWD 1
+#define KANTTS_ATTN_PASS_PNCA_FWD 2
+#define KANTTS_ATTN_PASS_PNCA_BWD 3
+#define KANTTS_ATTN_FWD_LDS_QUAD 1   /* mode 0, L <= 409: four lanes per query */
+#define KANTTS_ATTN_FWD_LDS 2        /* band modes (mode 0 under KANTTS_ATTN_NO_QUAD), L <= 409 */
+#define KANTTS_ATTN_FWD_DIRECT 3     /* L >= 410: keys and values from global memory */
+#define KANTTS_ATTN_BWD_LDS_QUAD 4   /* mode 0, L <= 390 */
+#define KANTTS_ATTN_BWD_LDS 5        /* band modes (mode 0 under KANTTS_ATTN_NO_QUAD), L <= 390 */
+#define KANTTS_ATTN_BWD_DIRECT 6     /* L >= 391 */
+#define KANTTS_ATTN_PNCA_FWD_LDS 7   /* L <= 409 */
+#define KANTTS_ATTN_PNCA_BWD_DQ2 8   /* L <= 256: both bands' query gradients summed in one pass, returns 0 */
+#define KANTTS_ATTN_PNCA_BWD_SPLIT 9 /* 257 <= L <= 390 (L <= 390 under KANTTS_ATTN_NO_DQ2): dqh written, returns 1 */
+int kantts_attn_plan(int L, int mode, int pass);
 
 /* ------------------------------------------------------------------------------------------
  * LSTM recurrence, H = 128 (time loop of torch.nn.LSTM: kantts/models/sambert/adaptors.py:44-57,
@@ -657,7 +691,10 @@ int kantts_conv_n1_launch(const kantts_conv_n1_args* args, int mode, void* strea
 /* Free-running inference steps.
  * kantts_attn_decode: one query per sequence (decoder position `step`) against rows [lo, hi] of a (B, L, .) K/V
  *   buffer; the interval is the training kernels' function of (mode, step, len, bw) (HybridAttentionDecoder.infer,
- *   kantts/models/sambert/kantts_sambert.py:208-253; K/V state sambert/__init__.py:212-258).  q / o hold B rows.
+ *   kantts/models/sambert/kantts_sambert.py:208-253; K/V state sambert/__init__.py:212-258).  q / o hold B rows
+ *   (row b at ptr[b*ld + h*16 + d]); no dropout, no lse.  Band modes: a sequence with step >= len gets context 0.
+ *   0 <= step < L, else KANTTS_E_BADARG; an ld that is not a multiple of 4: KANTTS_E_BADARG; d_head != 16:
+ *   KANTTS_E_UNSUPPORTED (the codes of the training entry points).
  *   bw_seq (optional, B entries) gives every sequence its own band width: the reference infers one utterance at a
  *   time with the band of THAT utterance, which a batch can only reproduce per sequence.
  * kantts_lstm_cell: gates (B, 4H) in PyTorch order [i|f|g|o] -> h, c (VarRnnARPredictor.infer, adaptors.py:67-83). */

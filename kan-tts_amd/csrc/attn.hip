@@ -258,8 +258,8 @@ __global__ __launch_bounds__(128) void attn_bwd_dkv_kernel(const AttnArgs a) {
 
 // ---------------------------------------------------------------------------------------------
 // LDS-staged versions: one workgroup per (batch, head) stages the K/V (or Q/dO) rows of that head
-// once (coalesced float4 rows, 17-float LDS row stride => conflict-free when neighbouring lanes read
-// neighbouring rows, broadcast when all lanes read one row) and every thread then walks its interval
+// once (coalesced float4 rows, AT_LD = 20-float LDS row stride => 16-byte accesses, conflict-free when neighbouring lanes
+// read neighbouring rows, broadcast when all lanes read one row) and every thread then walks its interval
 // out of LDS.  The direct-from-global kernels above are latency-bound (two dependent L2 round trips
 // per key); these are the ones used whenever the head fits in 64 KB of LDS (L <= ~390).
 #define AT_LD 20  // 80-byte rows: 16-byte LDS accesses, conflict-free for neighbouring rows in neighbouring lanes
@@ -419,14 +419,8 @@ __device__ __forceinline__ void attn_bwd_dq_lds_body(const AttnArgs& a, const in
   }
 }
 
-__global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_lds_kernel(const AttnArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  attn_bwd_dq_lds_body(a, AT_H(a), AT_B(a), sm);
-}
-
-// D_i = dO_i . O_i: read from dvec (written by the dq pass, which then has to run first) or, with RECOMPUTE_D, formed
-// here from the O rows -- the two passes of a backward then are independent and run as roles of ONE launch
-template <bool RECOMPUTE_D>
+// D_i = dO_i . O_i is formed here from the O rows, not read from dvec (which the dq pass writes): the two passes of a
+// backward then are independent and run as roles of ONE launch
 __device__ __forceinline__ void attn_bwd_dkv_lds_body(const AttnArgs& a, const int h, const int b, float* sm) {
   float* Qs = sm;
   float* Gs = sm + a.L * AT_LD;
@@ -443,15 +437,11 @@ __device__ __forceinline__ void attn_bwd_dkv_lds_body(const AttnArgs& a, const i
   const long long sbase = ((long long)b * a.H + h) * a.L;
   for (int i = threadIdx.x; i < a.L; i += AT_THREADS) {
     Ls[i] = a.lse[sbase + i];
-    if (RECOMPUTE_D) {
-      const long long row = (long long)b * a.L + i;
-      float go[DH], oo[DH];
-      load16(a.d_o + row * a.lddo + h * DH, go);
-      load16(a.o + row * a.ldo + h * DH, oo);
-      Ds[i] = dot16(go, oo);
-    } else {
-      Ds[i] = a.dvec[sbase + i];
-    }
+    const long long row = (long long)b * a.L + i;
+    float go[DH], oo[DH];
+    load16(a.d_o + row * a.lddo + h * DH, go);
+    load16(a.o + row * a.ldo + h * DH, oo);
+    Ds[i] = dot16(go, oo);
   }
   __syncthreads();
   const int len = a.lens ? a.lens[b] : a.L;
@@ -510,12 +500,6 @@ __device__ __forceinline__ void attn_bwd_dkv_lds_body(const AttnArgs& a, const i
     store16(a.dk + krow * a.lddk + h * DH, dk);
     store16(a.dv + krow * a.lddv + h * DH, dv);
   }
-}
-
-// must run after attn_bwd_dq_* (needs dvec)
-__global__ __launch_bounds__(AT_THREADS) void attn_bwd_dkv_lds_kernel(const AttnArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  attn_bwd_dkv_lds_body<false>(a, AT_H(a), AT_B(a), sm);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -866,7 +850,7 @@ __global__ __launch_bounds__(AT_THREADS) void attn_multi_lds_kernel(const AttnMu
     else if (role == AT_ROLE_DQ)
       attn_bwd_dq_lds_body(a, AT_H(a), AT_B(a), sm);
     else
-      attn_bwd_dkv_lds_body<true>(a, AT_H(a), AT_B(a), sm);
+      attn_bwd_dkv_lds_body(a, AT_H(a), AT_B(a), sm);
   }
 }
 
@@ -883,6 +867,34 @@ static inline dim3 at_grid(int H, int B, int Z) { return at_b_first() ? dim3(B, 
 
 static inline size_t attn_lds_bytes(int L, bool dkv) {
   return (size_t)(2 * L * AT_LD + (dkv ? 2 * L : 0)) * sizeof(float);
+}
+
+// A band of L or more positions is the whole sequence: the host band width is clamped so that i + bw cannot overflow
+// (a width read from device memory, bw_dev / bw_seq, is the caller's to keep below 2^30: see the header)
+static inline int at_clamp_bw(int bw, int L) { return bw < L ? bw : L; }
+
+// The one statement of which path a problem takes (include/kantts_hip.h, kantts_attn_plan); the four launchers switch
+// on its result.  A head fits the LDS-staged kernels while its two row images (plus lse and D for a backward) fit 64 KB:
+// L <= 409 forward, L <= 390 backward.  The environment switches are read once per process.
+extern "C" int kantts_attn_plan(int L, int mode, int pass) {
+  static const bool no_quad = getenv("KANTTS_ATTN_NO_QUAD") != nullptr;
+  static const bool no_dq2 = getenv("KANTTS_ATTN_NO_DQ2") != nullptr;
+  if (L < 0 || pass < KANTTS_ATTN_PASS_FWD || pass > KANTTS_ATTN_PASS_PNCA_BWD) return KANTTS_E_BADARG;
+  const bool pnca = pass == KANTTS_ATTN_PASS_PNCA_FWD || pass == KANTTS_ATTN_PASS_PNCA_BWD;
+  if (!pnca && (mode < 0 || mode > 2)) return KANTTS_E_BADARG;
+  const bool bwd = pass == KANTTS_ATTN_PASS_BWD || pass == KANTTS_ATTN_PASS_PNCA_BWD;
+  const bool fits = attn_lds_bytes(L, bwd) <= 64 * 1024;
+  const bool quad = mode == 0 && !no_quad;
+  switch (pass) {
+    case KANTTS_ATTN_PASS_FWD:
+      return !fits ? KANTTS_ATTN_FWD_DIRECT : quad ? KANTTS_ATTN_FWD_LDS_QUAD : KANTTS_ATTN_FWD_LDS;
+    case KANTTS_ATTN_PASS_BWD:
+      return !fits ? KANTTS_ATTN_BWD_DIRECT : quad ? KANTTS_ATTN_BWD_LDS_QUAD : KANTTS_ATTN_BWD_LDS;
+    case KANTTS_ATTN_PASS_PNCA_FWD:
+      return fits ? KANTTS_ATTN_PNCA_FWD_LDS : KANTTS_E_UNSUPPORTED;
+    default:  // one query per thread, held in registers across the two bands: at most AT_THREADS queries
+      return !fits ? KANTTS_E_UNSUPPORTED : (L <= AT_THREADS && !no_dq2) ? KANTTS_ATTN_PNCA_BWD_DQ2 : KANTTS_ATTN_PNCA_BWD_SPLIT;
+  }
 }
 
 static int attn_check(AttnArgs& a) {
@@ -906,14 +918,19 @@ extern "C" int kantts_attn_fwd(const float* q, const float* k, const float* v, i
   int rc = attn_check(a);
   if (rc) return rc;
   if (B == 0 || L == 0) return KANTTS_OK;
-  static const bool no_quad = getenv("KANTTS_ATTN_NO_QUAD") != nullptr;
-  if (attn_lds_bytes(L, false) <= 64 * 1024 && mode == 0 && !no_quad)
-    hipLaunchKernelGGL(attn_fwd_lds_quad_kernel, at_grid(H, B, 1), dim3(AT_THREADS), attn_lds_bytes(L, false),
-                       (hipStream_t)stream, a);
-  else if (attn_lds_bytes(L, false) <= 64 * 1024)
-    hipLaunchKernelGGL(attn_fwd_lds_kernel, at_grid(H, B, 1), dim3(AT_THREADS), attn_lds_bytes(L, false), (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3(kantts_cdiv(L, 128), H, B), dim3(128), 0, (hipStream_t)stream, a);
+  a.bw = at_clamp_bw(bw, L);
+  switch (kantts_attn_plan(L, mode, KANTTS_ATTN_PASS_FWD)) {
+    case KANTTS_ATTN_FWD_LDS_QUAD:
+      hipLaunchKernelGGL(attn_fwd_lds_quad_kernel, at_grid(H, B, 1), dim3(AT_THREADS), attn_lds_bytes(L, false),
+                         (hipStream_t)stream, a);
+      break;
+    case KANTTS_ATTN_FWD_LDS:
+      hipLaunchKernelGGL(attn_fwd_lds_kernel, at_grid(H, B, 1), dim3(AT_THREADS), attn_lds_bytes(L, false),
+                         (hipStream_t)stream, a);
+      break;
+    default:
+      hipLaunchKernelGGL(attn_fwd_kernel, dim3(kantts_cdiv(L, 128), H, B), dim3(128), 0, (hipStream_t)stream, a);
+  }
   KANTTS_CHECK_LAUNCH();
 }
 
@@ -933,21 +950,22 @@ extern "C" int kantts_attn_bwd(const float* q, const float* k, const float* v, i
   if (rc) return rc;
   if (!d_o || !dq || !dk || !dv || !dvec || ((lddo | lddq | lddk | lddv) & 3)) return KANTTS_E_BADARG;
   if (B == 0 || L == 0) return KANTTS_OK;
-  if (attn_lds_bytes(L, true) <= 64 * 1024) {
+  a.bw = at_clamp_bw(bw, L);
+  const int plan = kantts_attn_plan(L, mode, KANTTS_ATTN_PASS_BWD);
+  if (plan == KANTTS_ATTN_BWD_DIRECT) {
+    dim3 grid(kantts_cdiv(L, 128), H, B), block(128);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, block, 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid, block, 0, (hipStream_t)stream, a);
+  } else {
     AttnMulti m = {};
     m.p[0] = a; m.role[0] = AT_ROLE_DQ;
     m.p[1] = a; m.role[1] = AT_ROLE_DKV;
-    static const bool no_quad = getenv("KANTTS_ATTN_NO_QUAD") != nullptr;
-    if (mode == 0 && !no_quad)
+    if (plan == KANTTS_ATTN_BWD_LDS_QUAD)
       hipLaunchKernelGGL(attn_multi_lds_kernel<true>, at_grid(H, B, 2), dim3(AT_THREADS), attn_lds_bytes(L, true),
                          (hipStream_t)stream, m);
     else
       hipLaunchKernelGGL(attn_multi_lds_kernel<false>, at_grid(H, B, 2), dim3(AT_THREADS), attn_lds_bytes(L, true),
                          (hipStream_t)stream, m);
-  } else {
-    dim3 grid(kantts_cdiv(L, 128), H, B), block(128);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, block, 0, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid, block, 0, (hipStream_t)stream, a);
   }
   KANTTS_CHECK_LAUNCH();
 }
@@ -978,7 +996,9 @@ extern "C" int kantts_pnca_attn_fwd(const float* qkv, const float* hkv, int ldh,
   if (!qkv || !hkv || !ox || !oh || !lse_x || !lse_h || B < 0 || H < 1 || L < 0 || ldh < 2 * H * DH || (ldh & 3))
     return KANTTS_E_BADARG;
   if (B == 0 || L == 0) return KANTTS_OK;
-  if (attn_lds_bytes(L, false) > 64 * 1024) return KANTTS_E_UNSUPPORTED;
+  if (kantts_attn_plan(L, 1, KANTTS_ATTN_PASS_PNCA_FWD) != KANTTS_ATTN_PNCA_FWD_LDS) return KANTTS_E_UNSUPPORTED;
+  bw_x = at_clamp_bw(bw_x, L);
+  bw_h = at_clamp_bw(bw_h, L);
   const int D = H * DH;
   AttnMulti m = {};
   pnca_fill(m.p[0], qkv, qkv, 3 * D, D, ox, lse_x, lens, bw_dev, bw_x, B, H, L, 1, drop_p, seed_x, seed_dev);
@@ -1003,7 +1023,10 @@ extern "C" int kantts_pnca_attn_bwd(const float* qkv, const float* hkv, int ldh,
       ldh < 2 * H * DH || (ldh & 3))
     return KANTTS_E_BADARG;
   if (B == 0 || L == 0) return KANTTS_OK;
-  if (attn_lds_bytes(L, true) > 64 * 1024) return KANTTS_E_UNSUPPORTED;
+  const int plan = kantts_attn_plan(L, 1, KANTTS_ATTN_PASS_PNCA_BWD);
+  if (plan != KANTTS_ATTN_PNCA_BWD_DQ2 && plan != KANTTS_ATTN_PNCA_BWD_SPLIT) return KANTTS_E_UNSUPPORTED;
+  bw_x = at_clamp_bw(bw_x, L);
+  bw_h = at_clamp_bw(bw_h, L);
   const int D = H * DH;
   AttnMulti m = {};
   AttnArgs x, hh;
@@ -1013,8 +1036,7 @@ extern "C" int kantts_pnca_attn_bwd(const float* qkv, const float* hkv, int ldh,
   pnca_fill(hh, qkv, hkv, ldh, 0, const_cast<float*>(oh), const_cast<float*>(lse_h), lens, bw_dev, bw_h, B, H, L, 2, drop_p,
             seed_h, seed_dev);
   hh.d_o = d_oh; hh.lddo = D; hh.dq = dqh; hh.lddq = D; hh.dk = dhkv; hh.dv = dhkv + D; hh.lddk = hh.lddv = 2 * D;
-  static const bool no_dq2 = getenv("KANTTS_ATTN_NO_DQ2") != nullptr;
-  const bool dq2 = L <= AT_THREADS && !no_dq2;  // one query per thread, held in registers across the two bands
+  const bool dq2 = plan == KANTTS_ATTN_PNCA_BWD_DQ2;
   if (!dqh && !dq2) return KANTTS_E_BADARG;
   if (dq2) {
     // three roles: the query gradient of both bands summed in one pass (dqh is not written), dk/dv per band
@@ -1086,11 +1108,11 @@ extern "C" int kantts_attn_decode(const float* q, const float* k, const float* v
   if (!q || !k || !v || !o || B < 0 || H < 1 || L < 1 || mode < 0 || mode > 2 || step < 0 || step >= L)
     return KANTTS_E_BADARG;
   if (d_head != DH) return KANTTS_E_UNSUPPORTED;
-  if ((ldq | ldk | ldv | ldo) & 3) return KANTTS_E_UNSUPPORTED;
+  if ((ldq | ldk | ldv | ldo) & 3) return KANTTS_E_BADARG;  // float4 row access, as in attn_check
   if (B == 0) return KANTTS_OK;
   AttnArgs a = {};
   a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.o = o; a.ldo = ldo;
-  a.lens = lens; a.B = B; a.H = H; a.L = L; a.mode = mode; a.bw = bw; a.scale = 0.25f;
+  a.lens = lens; a.B = B; a.H = H; a.L = L; a.mode = mode; a.bw = at_clamp_bw(bw, L); a.scale = 0.25f;
   hipLaunchKernelGGL(attn_decode_kernel, dim3(kantts_cdiv((long long)B * H, 128)), dim3(128), 0, (hipStream_t)stream, a,
                      step, bw_seq);
   KANTTS_CHECK_LAUNCH();

@@ -454,6 +454,7 @@ def lib():
                                       i, f, u64, p, p]
         L.kantts_pnca_attn_fwd.argtypes = [p, p, i, p, p, p, p, p, p, i, i, i, i, i, i, f, u64, u64, p, p]
         L.kantts_pnca_attn_bwd.argtypes = [p, p, i, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, f, u64, u64, p, p]
+        L.kantts_attn_plan.argtypes = [i, i, i]
         L.kantts_lstm_fwd.argtypes = [p, p, p, p, p, p, p, i, i, i, i, i, i, p]
         L.kantts_attn_decode.argtypes = [p, p, p, i, i, i, p, i, p, p, i, i, i, i, i, i, i, p]
         L.kantts_lstm_cell.argtypes = [p, p, p, p, i, i, p]
@@ -616,7 +617,7 @@ def predictor_pair_entry_points():
 
 EXPORTED_SYMBOLS = [
     "kantts_abi_version", "kantts_target_arch", "kantts_gemm_seg_launch", "kantts_gemm_plan", "kantts_layernorm_fwd",
-    "kantts_layernorm_bwd", "kantts_attn_fwd", "kantts_attn_bwd", "kantts_pnca_attn_fwd", "kantts_pnca_attn_bwd", "kantts_lstm_fwd", "kantts_lstm_bwd",
+    "kantts_layernorm_bwd", "kantts_attn_fwd", "kantts_attn_bwd", "kantts_attn_plan", "kantts_pnca_attn_fwd", "kantts_pnca_attn_bwd", "kantts_lstm_fwd", "kantts_lstm_bwd",
     "kantts_embed_sum_fwd", "kantts_embed_sum_bwd", "kantts_lr_index", "kantts_lr_gather_fwd",
     "kantts_lr_gather_bwd", "kantts_fsmn_dwconv_fwd", "kantts_fsmn_dwconv_bwd", "kantts_fsmn_dwconv_bwd_ws", "kantts_masked_l1",
     "kantts_sumsq", "kantts_elem_loss", "kantts_adam_step", "kantts_melspec_fwd", "kantts_melspec_norm_fwd", "kantts_melspec_bwd", "kantts_melspec_norm_fwd_fm", "kantts_melspec_bwd_fm", "kantts_weight_norm_fwd", "kantts_weight_norm_bwd", "kantts_weight_norm_strided_fwd", "kantts_weight_norm_strided_bwd",
@@ -833,6 +834,20 @@ def gemm_plan(g):
     out = (c_int32 * 8)()
     check(lib().kantts_gemm_plan(ctypes.byref(g), ctypes.byref(out)), "gemm_plan")
     return list(out)
+
+
+ATTN_PASSES = {"fwd": 0, "bwd": 1, "pnca_fwd": 2, "pnca_bwd": 3}  # KANTTS_ATTN_PASS_*
+ATTN_PATHS = {1: "fwd_lds_quad", 2: "fwd_lds", 3: "fwd_direct", 4: "bwd_lds_quad", 5: "bwd_lds", 6: "bwd_direct",
+              7: "pnca_fwd_lds", 8: "pnca_bwd_dq2", 9: "pnca_bwd_split", -2: "unsupported"}  # KANTTS_ATTN_* / E_UNSUPPORTED
+
+
+def attn_plan(L, mode, which):
+    """kantts_attn_plan (include/kantts_hip.h): the name of the path ``which`` ("fwd", "bwd", "pnca_fwd", "pnca_bwd") takes at
+    L positions in ``mode`` -- an ATTN_PATHS value, "unsupported" where the entry point refuses."""
+    rc = lib().kantts_attn_plan(int(L), int(mode), ATTN_PASSES[which])
+    if rc not in ATTN_PATHS:
+        raise RuntimeError("libkantts_hip: attn_plan failed with code %d" % rc)
+    return ATTN_PATHS[rc]
 
 
 E_UNSUPPORTED = -2

@@ -1889,7 +1889,7 @@ class EmulatedLib:
             bw_b = int(_arr(bw_seq, B, np.int32)[b]) if bw_seq else bw
             lo, hi = self._ranges(mode, L, ln_b, bw_b)
             lo, hi = int(lo[step]), int(hi[step])
-            if mode != 0 and step >= ln_b:
+            if (mode != 0 and step >= ln_b) or hi < lo:  # padded query of a band mode / no key at all (mode 0, len = 0)
                 continue
             for h in range(H):
                 sc = (K[b, lo:hi + 1, h].astype(np.float64) @ Q[b, h].astype(np.float64)) * 0.25
