@@ -1939,6 +1939,80 @@ int kantts_attn_prior_rows(const double* lfact, int n_lfact, const int32_t* n_sy
 int kantts_broadcast_rows_f32(const float* table, int n, const int64_t* item, const int32_t* len, float* out, int B, int Tmax,
                               int D, void* stream);
 
+/* ---- sy-BERT pre-training (csrc/sybert.hip): the BERT masking of a padded batch on the device, and the masked-LM head
+ * (Linear(d_model -> |sy|) + SeqCELoss) fused.  Reference: kantts/datasets/dataset.py:873-925,1023-1042 (BERT_Text_Dataset
+ * .bert_masking, MaskingActor), kantts/models/sambert/kantts_sambert.py (KanTtsTextsyBERT.fc), kantts/train/loss.py:444-460.
+ *
+ * kantts_bert_mask_rows: the device twin of kantts.datasets.bert_masking.draw.  seed_counter: two 64-bit words
+ * {seed, counter} in DEVICE memory, the convention of kantts_nsf_draw_states.  With mix = kantts_rng_mix of csrc/common.h,
+ * L = clamp(lens[b], 0, T) (the length INCLUDING the closing "~") and, for sequence b of draw number `counter`,
+ *   key_b     = mix(mix(seed, 0x53594245), (counter << 20) | b)
+ *   masked(j) = j < L - 1  and  (mix(key_b, j) >> 40) < thr              thr = floor(mask_ratio * 2^24), in [0, 2^24]
+ *   n         = the number of masked positions,  n2 = 4 n / 5,  n3 = n / 10     (integer divisions)
+ *   rank(j)   = the place of (mix(key_b, 2^32 + j), j) among the masked positions in ascending order
+ *   rnd_b     = (hi32(mix(key_b, 2^33)) * nsym) >> 32                    ONE random symbol per sequence, as in the reference
+ *   id(j)     = mask_id   for masked j with rank < n2
+ *             = rnd_b     for masked j with n2 <= rank < n2 + n3
+ *             = t(b, j)   otherwise (masked or not),   t(b, j) = targets[(b * T + j) * tgt_ts], the unmasked id
+ * the launch writes, for every b < B and j < T,
+ *   input_lings[(b * T + j) * ling_ts] = id(j)        (int64; ling_ts = 4 and the base of column 0 for a (B, T, 4) tensor)
+ *   bert_masks[b * T + j]              = masked(j) ? 1.0f : 0.0f
+ *   targets_out[b * T + j]             = t(b, j)      (targets_out == NULL: not written)
+ * and nothing else: `targets` may be column 0 of input_lings ITSELF (tgt_ts == ling_ts, the same base: a thread reads its
+ * cell before it writes it, and no other thread reads that cell) -- a batch gathered as (B, T, 4) rows is then masked in
+ * place and its dense targets come out of the same launch; the cells between two positions (ling_ts > 1) and `seed` are not written.  Position L - 1 and the
+ * padding at or past L are never masked.  Behind a barrier the launch stores counter + 1: consecutive launches (and replays
+ * of one captured launch) draw different numbers, and a counter set back replays them.  ONE workgroup, a wave per sequence
+ * (wave w takes sequences w, w + 16, ...): the counter is read and advanced by the same launch, and only inside one
+ * workgroup does a barrier stand between every read and the store -- with a workgroup per sequence a workgroup that starts
+ * late would read the advanced counter.  T may exceed the thread count: a wave walks its sequence 64 positions at a time.
+ * Plain vector stores only, no atomics.
+ * KANTTS_E_BADARG: a NULL pointer, seed_counter / targets / input_lings not 8-byte aligned, lens / bert_masks not 4-byte
+ * aligned, targets_out not 8-byte aligned, B < 1, T < 1, ling_ts < 1, tgt_ts < 1, thr outside [0, 2^24].
+ * KANTTS_E_UNSUPPORTED: T > 4096, B >= 2^20 (the key holds the item in 20 bits), nsym < 1.  Nothing is written when a call is
+ * refused. */
+int kantts_bert_mask_rows(uint64_t* seed_counter, const int64_t* targets, long long tgt_ts, const int32_t* lens,
+                          int64_t* input_lings, long long ling_ts, float* bert_masks, int64_t* targets_out, int B, int T,
+                          int thr, int mask_id, int nsym, void* stream);
+
+/* kantts_mlm_head_fwd: logits[r][v] = bias[v] + sum_c hid[r][c] * W[v][c] are formed 16 rows at a time on
+ * v_mfma_f32_16x16x4_f32 and never stored; per row an online softmax keeps the maximum, the sum of exponentials, the
+ * arg-max (the LOWEST index among equal maxima, torch.argmax on the CPU) and the target's logit:
+ *   lse[r]  = log sum_v exp(logits[r][v])                                  written for every r < M
+ *   ce[r]   = lse[r] - logits[r][targets[r]]
+ *   out[0]  = sum_r mask[r] * ce[r] / sum_r mask[r]                         the loss of SeqCELoss
+ *   out[1]  = sum_r mask[r] * [argmax_v logits[r][v] != targets[r]] / sum_r mask[r]      its error rate
+ *   out[2]  = sum_r mask[r]                                                 (the backward reads it)
+ * A row with mask[r] == 0 adds exactly 0 to the three sums whatever its logits and its target are: a non-finite logit on
+ * an unmasked row does NOT poison the loss as it would in the reference (0 * NaN there).  sum(mask) == 0 gives NaN in out[0]
+ * and out[1], as the reference does.  A target outside [0, V) on a row with mask != 0 gives NaN in out[0].
+ * fp32 operands and fp32 accumulation in every precision mode.  No atomics; equal inputs give equal bits: workgroup g (rows
+ * 16 g ...) leaves its three sums in ws[3 g ..], a second launch behind it on the stream adds them in a fixed order.
+ *   hid (M, C), W (V, C), bias (V) or NULL, targets (M) int64, mask (M), out (3), lse (M): dense; ws: 3 * ceil(M / 16) floats
+ *   the call may overwrite, ws_floats says how many there are.
+ *
+ * kantts_mlm_head_bwd: for the forward that wrote `lse` and `out`, with g[r] = gscale * dloss[0] * mask[r] / out[2]
+ * (dloss: the upstream gradient of out[0], ONE float in device memory; gscale: a host scalar, the trainer's 1 / V):
+ *   dlogits[r][v] = g[r] * (exp(logits[r][v] - lse[r]) - [v == targets[r]])      mask[r] != 0;   exactly 0 otherwise
+ *   d_hid[r][c]   = sum_v dlogits[r][v] * W[v][c]            exactly 0 on rows with mask[r] == 0
+ *   d_W[v][c]     = sum_r dlogits[r][v] * hid[r][c]
+ *   d_bias[v]     = sum_r dlogits[r][v]                      (d_bias == NULL: not written)
+ * All three are WRITTEN, not accumulated into.  out[2] == 0, or a target outside [0, V) on a row with mask != 0, gives NaN
+ * gradients.  Two launches: the first recomputes the logits as the forward did and leaves dlogits, zero-padded to
+ * (16 ceil(M / 16), 16 ceil(V / 16)), in ws; the second holds one workgroup per 16 x 16 tile of d_W (its 8 waves take
+ * interleaved 16-row blocks, the partial tiles are added in wave order through LDS; the tiles of the first 16 channels also
+ * sum d_bias) and one workgroup per 16 rows of d_hid.  No atomics; equal inputs give equal bits.
+ *   d_hid (M, C), d_W (V, C), d_bias (V); ws: 16 ceil(M / 16) * 16 ceil(V / 16) floats, 16-byte aligned.
+ *
+ * Both: KANTTS_E_BADARG: a NULL required pointer, M < 1, hid / W / d_hid / d_W / ws (backward) not 16-byte aligned.
+ * KANTTS_E_UNSUPPORTED: C not a multiple of 16 or outside [16, 512], V outside [1, 4096], M > 2^24.  KANTTS_E_WORKSPACE:
+ * ws_floats too small.  Nothing is written when a call is refused. */
+int kantts_mlm_head_fwd(const float* hid, const float* W, const float* bias, const int64_t* targets, const float* mask,
+                        float* out, float* lse, float* ws, long long ws_floats, int M, int C, int V, void* stream);
+int kantts_mlm_head_bwd(const float* hid, const float* W, const float* bias, const int64_t* targets, const float* mask,
+                        const float* lse, const float* out, const float* dloss, float gscale, float* d_hid, float* d_W,
+                        float* d_bias, float* ws, long long ws_floats, int M, int C, int V, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -592,6 +592,10 @@ def lib():
         if all(hasattr(L, s) for s in CORPUS_PRIOR_SYMBOLS):  # has_corpus_prior(): a library built before them still loads
             L.kantts_attn_prior_rows.argtypes = [p, i, p, p, p, i, i, i, p]
             L.kantts_broadcast_rows_f32.argtypes = [p, i, p, p, p, i, i, i, p]
+        if all(hasattr(L, s) for s in SYBERT_SYMBOLS):  # has_sybert(): a library built before them still loads
+            L.kantts_bert_mask_rows.argtypes = [p, p, ll, p, p, ll, p, p, i, i, i, i, i, p]
+            L.kantts_mlm_head_fwd.argtypes = [p, p, p, p, p, p, p, p, ll, i, i, i, p]
+            L.kantts_mlm_head_bwd.argtypes = [p, p, p, p, p, p, p, p, f, p, p, p, p, ll, i, i, i, p]
         _lib = L
     return _lib
 
@@ -608,6 +612,8 @@ PREDICTOR_PAIR_SYMBOLS = ("kantts_bgemm_nt_pair", "kantts_ffn_pair2", "kantts_fs
 
 
 CORPUS_PRIOR_SYMBOLS = ("kantts_attn_prior_rows", "kantts_broadcast_rows_f32")  # MAS / SE batch fields (csrc/attn_prior.hip)
+
+SYBERT_SYMBOLS = ("kantts_bert_mask_rows", "kantts_mlm_head_fwd", "kantts_mlm_head_bwd")  # sy-BERT pre-training (csrc/sybert.hip)
 
 
 def predictor_pair_entry_points():
@@ -645,6 +651,7 @@ EXPORTED_SYMBOLS = [
     "kantts_fsmn_memory_drop_fwd", "kantts_fsmn_memory_drop_bwd",
     *PREDICTOR_PAIR_SYMBOLS,
     *CORPUS_PRIOR_SYMBOLS,
+    *SYBERT_SYMBOLS,
 ]
 
 
@@ -2301,3 +2308,51 @@ def _tag_flops(tag):
     kern, s, _ = tag
     f = 2.0 * s["B"] * s["Tdst"] * s["inner"] * s["Cout"] * (s["Cin"] // s["groups"]) * s["K"]
     return f / max(1, s.get("in_div", 1)) if kern in ("conv_win", "cconv") else f
+
+
+# ----------------------------------------------------------------------------------------------
+# sy-BERT pre-training (csrc/sybert.hip)
+E_WORKSPACE = -3
+SYBERT_MAX_T, SYBERT_MAX_B = 4096, 1 << 20
+
+
+def has_sybert():
+    """True when the loaded library exports the sy-BERT entry points (csrc/sybert.hip: the device-side BERT masking and the
+    fused masked-LM head)."""
+    return all(hasattr(lib(), s) for s in SYBERT_SYMBOLS)
+
+
+def require_sybert():
+    missing = [s for s in SYBERT_SYMBOLS if not hasattr(lib(), s)]
+    if missing:
+        raise RuntimeError("libkantts_hip.so at %s has no %s: rebuild the library (make -C kan-tts_amd/csrc)"
+                           % (LIB_PATH, ", ".join(missing)))
+
+
+def bert_mask_rows_raw(words, targets, lens, lings, masks, *, B, T, thr, mask_id, nsym, ling_ts=4, tgt_ts=1,
+                       targets_out=None):
+    """kantts_bert_mask_rows as it is: ``lings`` is the int64 tensor whose FIRST element is column 0 of sequence 0,
+    ``ling_ts`` elements from one position to the next (``targets`` / ``tgt_ts`` likewise); returns its code."""
+    return lib().kantts_bert_mask_rows(ptr(words, torch.int64), ptr(targets, torch.int64), int(tgt_ts),
+                                       ptr(lens, torch.int32), ptr(lings, torch.int64), int(ling_ts),
+                                       ptr(masks, torch.float32), ptr(targets_out, torch.int64), int(B), int(T), int(thr),
+                                       int(mask_id), int(nsym), stream())
+
+
+def mlm_head_fwd_raw(hid, weight, bias, targets, mask, out, lse, ws, *, M, C, V, ws_floats=None):
+    """kantts_mlm_head_fwd as it is; returns its code."""
+    n = ws.numel() if ws_floats is None and ws is not None else (ws_floats or 0)
+    return lib().kantts_mlm_head_fwd(ptr(hid, torch.float32), ptr(weight, torch.float32), ptr(bias, torch.float32),
+                                     ptr(targets, torch.int64), ptr(mask, torch.float32), ptr(out, torch.float32),
+                                     ptr(lse, torch.float32), ptr(ws, torch.float32), int(n), int(M), int(C), int(V), stream())
+
+
+def mlm_head_bwd_raw(hid, weight, bias, targets, mask, lse, out, dloss, gscale, d_hid, d_weight, d_bias, ws, *, M, C, V,
+                     ws_floats=None):
+    """kantts_mlm_head_bwd as it is; returns its code."""
+    n = ws.numel() if ws_floats is None and ws is not None else (ws_floats or 0)
+    return lib().kantts_mlm_head_bwd(ptr(hid, torch.float32), ptr(weight, torch.float32), ptr(bias, torch.float32),
+                                     ptr(targets, torch.int64), ptr(mask, torch.float32), ptr(lse, torch.float32),
+                                     ptr(out, torch.float32), ptr(dloss, torch.float32), float(gscale),
+                                     ptr(d_hid, torch.float32), ptr(d_weight, torch.float32), ptr(d_bias, torch.float32),
+                                     ptr(ws, torch.float32), int(n), int(M), int(C), int(V), stream())

@@ -3362,3 +3362,87 @@ def spk_tail(x, lens, bn, w, obn):
     out = torch.empty((B, E), device=x.device, dtype=torch.float32)
     k_tail(x, lens, bn[0], bn[1], w, obn[0], obn[1], out, B=B, C=C2 // 2, CX=CX, TX=TX, E=E)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# sy-BERT pre-training (csrc/sybert.hip): the masked-LM head and the device-side BERT masking
+class _MlmHeadCE(torch.autograd.Function):
+    """Linear(C -> V) + SeqCELoss in two launches each way (kantts_mlm_head_fwd / _bwd); the logits are never stored."""
+
+    @staticmethod
+    def forward(ctx, hid, weight, bias, targets, masks, gscale):
+        from . import mlm_head_fwd_raw, require_sybert
+
+        require_sybert()
+        M, C = hid.shape
+        V = weight.shape[0]
+        out = torch.empty((3,), device=hid.device, dtype=torch.float32)
+        lse = torch.empty((M,), device=hid.device, dtype=torch.float32)
+        ws = torch.empty((3 * ((M + 15) // 16),), device=hid.device, dtype=torch.float32)
+        check(mlm_head_fwd_raw(hid, weight, bias, targets, masks, out, lse, ws, M=M, C=C, V=V), "mlm_head_fwd")
+        ctx.save_for_backward(hid, weight, bias, targets, masks, lse, out)
+        ctx.gscale = gscale
+        loss, err = out[0], out[1]
+        ctx.mark_non_differentiable(err)
+        return loss, err
+
+    @staticmethod
+    def backward(ctx, g_loss, g_err):
+        from . import mlm_head_bwd_raw
+
+        hid, weight, bias, targets, masks, lse, out = ctx.saved_tensors
+        M, C = hid.shape
+        V = weight.shape[0]
+        d_hid, d_w = torch.empty_like(hid), torch.empty_like(weight)
+        d_b = None if bias is None else torch.empty_like(bias)
+        ws = torch.empty((((M + 15) // 16) * 16 * ((V + 15) // 16) * 16,), device=hid.device, dtype=torch.float32)
+        g = _c(g_loss).reshape(1).to(torch.float32)
+        check(mlm_head_bwd_raw(hid, weight, bias, targets, masks, lse, out, g, ctx.gscale, d_hid, d_w, d_b, ws, M=M, C=C,
+                               V=V), "mlm_head_bwd")
+        return d_hid, d_w, d_b, None, None, None
+
+
+def mlm_head_ce(hid, weight, bias, targets, masks, gscale=1.0):
+    """SeqCELoss of ``hid @ weight.T + bias`` without the logits: hid (..., C) fp32, weight (V, C), bias (V) or None,
+    targets (...) int64, masks (...) fp32 -> (loss, err), the two scalars SeqCELoss.forward returns: the masked mean of the
+    cross entropy and of [arg-max != target].  ``gscale`` multiplies the GRADIENT only (a factor the caller applies to the
+    loss behind this op, e.g. the trainer's 1 / V, can be folded in here instead; the returned loss is undivided).  fp32 in
+    every precision mode.  C a multiple of 16 up to 512 and V <= 4096, or the call fails: there is no stock fallback."""
+    C = hid.shape[-1]
+    if weight.dim() != 2 or weight.shape[1] != C or targets.numel() * C != hid.numel() or masks.numel() != targets.numel():
+        raise ValueError("mlm_head_ce: hid %s, weight %s, targets %s, masks %s"
+                         % (tuple(hid.shape), tuple(weight.shape), tuple(targets.shape), tuple(masks.shape)))
+    if targets.dtype != torch.int64 or masks.dtype != torch.float32:
+        raise TypeError("mlm_head_ce: targets int64 and masks float32, got %s and %s" % (targets.dtype, masks.dtype))
+    return _MlmHeadCE.apply(_c(hid).reshape(-1, C), _c(weight), None if bias is None else _c(bias),
+                            _c(targets).reshape(-1), _c(masks).reshape(-1), float(gscale))
+
+
+def bert_mask_thr(mask_ratio):
+    """floor(mask_ratio * 2^24) in fp64: the integer threshold kantts_bert_mask_rows compares its 24-bit draws with."""
+    if not 0.0 <= float(mask_ratio) <= 1.0:
+        raise ValueError("mask_ratio %r is outside [0, 1]" % (mask_ratio,))
+    return int(math.floor(float(mask_ratio) * 16777216.0))
+
+
+def bert_mask_rows(words, targets, lens32, input_lings, bert_masks, *, mask_ratio, mask_id, nsym, targets_out=None):
+    """The BERT masking of a padded batch in one launch (kantts_bert_mask_rows, the device twin of
+    kantts.datasets.bert_masking.draw): ``words`` an int64 device tensor {seed, counter} (the counter is left one higher),
+    targets (B, T) int64 -- the unmasked sy ids --, lens32 (B) int32 -- the lengths INCLUDING the closing "~" --; writes the
+    masked ids into column 0 of input_lings (B, T, 4) int64 and bert_masks (B, T) fp32.  ``targets=None``: the unmasked ids
+    ARE column 0 of input_lings (a batch gathered as rows of four streams), masked in place; ``targets_out`` (B, T) int64
+    then receives them.  No host read."""
+    from . import bert_mask_rows_raw, require_sybert
+
+    require_sybert()
+    B, T = bert_masks.shape
+    if (input_lings.dim() != 3 or tuple(input_lings.shape[:2]) != (B, T) or not input_lings.is_contiguous()
+            or not bert_masks.is_contiguous()):
+        raise ValueError("bert_mask_rows: input_lings %s, bert_masks %s" % (tuple(input_lings.shape), tuple(bert_masks.shape)))
+    for t in (targets, targets_out):
+        if t is not None and (tuple(t.shape) != (B, T) or not t.is_contiguous()):
+            raise ValueError("bert_mask_rows: targets / targets_out %s for a batch of %s" % (tuple(t.shape), (B, T)))
+    ts = input_lings.shape[2]
+    check(bert_mask_rows_raw(words, input_lings if targets is None else targets, lens32, input_lings, bert_masks, B=B, T=T,
+                             thr=bert_mask_thr(mask_ratio), mask_id=mask_id, nsym=nsym, ling_ts=ts,
+                             tgt_ts=ts if targets is None else 1, targets_out=targets_out), "bert_mask_rows")

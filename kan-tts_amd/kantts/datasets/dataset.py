@@ -362,4 +362,179 @@ def get_am_datasets(metafile, root_dir, config, allow_cache, split_ratio=0.98, s
     return AM_Dataset(config, train_lst, root_dir, allow_cache), AM_Dataset(config, valid_lst, root_dir, allow_cache)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# sy-BERT pre-training (reference :873-1130): unlabelled symbol sequences, BERT masking of the sy stream.  This is the HOST
+# path -- the validation loader, and the training loader with ``--device_corpus host``; a resident corpus draws its masks on
+# the device instead (kantts.datasets.bert_masking / device_batching.DeviceTextSet).  Under equal ``np.random`` / ``random``
+# seeds the arrays are the reference's (tests/golden/sybert_tiny.pt): the generators are consumed in its order.
+class MaskingActor(object):
+    def __init__(self, mask_ratio=0.15):
+        self.mask_ratio = mask_ratio
+
+    def _get_random_mask(self, length, p1=0.15):
+        """0. / 1. per position: one ``np.random.uniform`` draw of ``length`` values, 1 where it is below ``p1``."""
+        draws = np.random.uniform(0, 1, length)
+        return (draws < p1).astype(draws.dtype)
+
+    def _input_bert_masking(self, sequence_array, nb_symbol_category, mask_symbol_id, mask, p2=0.8, p3=0.1, p4=0.1):
+        """Of the n masked positions, in the order of one ``np.random.shuffle``: the first floor(n p2) read [MASK], the
+        next floor(n p3) read ONE ``random.randint`` symbol (drawn only when there is such a position), the rest stay."""
+        import math
+
+        out = sequence_array.copy()
+        where = np.where(mask == 1)[0]
+        order = np.arange(len(where))
+        np.random.shuffle(order)
+        n2, n3 = int(math.floor(len(where) * p2)), int(math.floor(len(where) * p3))
+        if n2 > 0:
+            out[where[order[:n2]]] = mask_symbol_id
+        if len(where[order[n2:n2 + n3]]) > 0:
+            out[where[order[n2:n2 + n3]]] = random.randint(0, nb_symbol_category - 1)
+        return out
+
+
+class BERT_Text_Dataset(torch.utils.data.Dataset):
+    """(ling_data, masked sy ids, bert_mask) per sentence.  ``metafile``: path(s) of lines ``<id>\\t{sy$tone$flag$ws...} ...``
+    (the ``raw_metafile.txt`` format; only the text is used), ``root_dir``: the director(ies) they belong to.  The mask is
+    drawn anew at every ``__getitem__``; with ``allow_cache`` the encoded sentence is kept (a plain per-process dict)."""
+
+    def __init__(self, config, metafile, root_dir, allow_cache=False, ling_unit=None):
+        from kantts.utils.ling_unit import KanTtsLinguisticUnit
+        from kantts.utils.ling_unit.ling_unit import MASK
+
+        self.config = config
+        metafile = metafile if isinstance(metafile, list) else [metafile]
+        root_dir = root_dir if isinstance(root_dir, list) else [root_dir]
+        self.meta = []
+        for meta_file, data_dir in zip(metafile, root_dir):
+            if not os.path.exists(meta_file):
+                raise ValueError("[BERT_Text_Dataset] meta file: {} not found".format(meta_file))
+            if not os.path.exists(data_dir):
+                raise ValueError("[BERT_Text_Dataset] data dir: {} not found".format(data_dir))
+            self.meta.extend(self.load_meta(meta_file, data_dir))
+        self.allow_cache = allow_cache
+        self.caches = {}
+        self.ling_unit = ling_unit if ling_unit is not None else KanTtsLinguisticUnit(config)
+        self.padder = Padder()
+        self.masking_actor = MaskingActor(config["Model"]["KanTtsTextsyBERT"]["params"]["mask_ratio"])
+        self.mask_id = int(self.ling_unit._streams["sy"].ids[MASK])
+        self.nsym = int(self.ling_unit.get_unit_size()["sy"])
+
+    def __len__(self):
+        return len(self.meta)
+
+    def encoded(self, idx):
+        """The sentence's integer streams (each ends with the id of "~"), without a mask."""
+        if self.allow_cache and idx in self.caches:
+            return self.caches[idx]
+        ling_data = self.ling_unit.encode_symbol_sequence(self.meta[idx])
+        if self.allow_cache:
+            self.caches[idx] = ling_data
+        return ling_data
+
+    def __getitem__(self, idx):
+        ling_data = self.encoded(idx)
+        bert_mask, masked = self.bert_masking(ling_data)
+        return (ling_data, masked, bert_mask)
+
+    def load_meta(self, metafile, data_dir):
+        items = []
+        with open(metafile, "r") as f:
+            for line in f:
+                if line.strip():
+                    _, ling_txt = line.strip().split("\t")
+                    items.append(ling_txt)
+        return items
+
+    @staticmethod
+    def gen_metafile(raw_meta_file, out_dir, split_ratio=0.98):
+        """Shuffle the raw metafile with the fixed dataset seed; ``bert_train.lst`` / ``bert_valid.lst`` in ``out_dir``."""
+        with open(raw_meta_file, "r") as f:
+            lines = f.readlines()
+        random.Random(DATASET_RANDOM_SEED).shuffle(lines)  # == random.seed(1234); random.shuffle(lines)
+        num_train = int(len(lines) * split_ratio) - 1
+        for name, part in (("bert_train.lst", lines[:num_train]), ("bert_valid.lst", lines[num_train:])):
+            with open(os.path.join(out_dir, name), "w") as f:
+                f.writelines(part)
+
+    def bert_masking(self, ling_data):
+        """(mask (L,) of 0. / 1., masked sy ids): every position but the closing "~" is masked with the configured ratio."""
+        mask = self.masking_actor._get_random_mask(len(ling_data[0]), p1=self.masking_actor.mask_ratio)
+        mask[-1] = 0
+        return mask, self.masking_actor._input_bert_masking(ling_data[0], self.nsym, self.mask_id, mask)
+
+    def collate_fn(self, batch):
+        pad_ids = [self.ling_unit._sub_unit_pad[t] for t in self.ling_unit._lfeat_type_list[:4]]
+        return bert_collate(batch, pad_ids, self.padder)
+
+
+class _SyntheticUnit:
+    """What BERT_Text_Dataset and the loaders read of a KanTtsLinguisticUnit, for id streams that never were text: every
+    stream's inventory ends with pad, "~" and [MASK], as ling_unit._Stream lays it out."""
+
+    _lfeat_type_list = ["sy", "tone", "syllable_flag", "word_segment"]
+
+    def __init__(self, sizes):
+        self._sizes = {k: int(sizes[k]) for k in self._lfeat_type_list}
+        self._sub_unit_pad = {k: n - 3 for k, n in self._sizes.items()}
+
+    def get_unit_size(self):
+        return dict(self._sizes)
+
+
+class SyntheticTextDataset(BERT_Text_Dataset):
+    """BERT_Text_Dataset over ``n`` seeded random sentences of ``lo`` .. ``hi`` symbols (the closing "~" included) instead
+    of a metafile: ``train_sybert --synthetic N`` and scripts/sybert_bench.py, which need no language resources.  ``sizes``:
+    the four inventory sizes (default: kantts.utils.synthetic.SAMBERT_VOCAB)."""
+
+    def __init__(self, config, n, seed=DATASET_RANDOM_SEED, lo=20, hi=120, sizes=None):
+        from kantts.utils.synthetic import SAMBERT_VOCAB
+
+        self.config, self.allow_cache, self.caches = config, False, {}
+        self.ling_unit = _SyntheticUnit(sizes or SAMBERT_VOCAB)
+        self.padder = Padder()
+        self.masking_actor = MaskingActor(config["Model"]["KanTtsTextsyBERT"]["params"]["mask_ratio"])
+        size = self.ling_unit.get_unit_size()
+        self.nsym, self.mask_id = size["sy"], size["sy"] - 1
+        rs = np.random.RandomState(seed)
+        self.meta = []
+        for _ in range(int(n)):
+            L = int(rs.randint(lo, hi + 1))
+            self.meta.append([np.append(rs.randint(0, size[k] - 3, size=L - 1), size[k] - 2).astype(np.int32)
+                              for k in self.ling_unit._lfeat_type_list])
+
+    def encoded(self, idx):
+        return self.meta[idx]
+
+
+def bert_collate(batch, pad_ids, padder=None):
+    """Items of BERT_Text_Dataset -> {"input_lings" (B, T, 4) int64: masked sy | tone | syllable_flag | word_segment,
+    "valid_input_lengths" (B) int64: the lengths without the closing "~", "targets" (B, T) int64: the unmasked sy ids,
+    "bert_masks" (B, T)} padded to the longest sentence with the streams' pad ids (the mask with 0)."""
+    padder = padder or Padder()
+    T = max(len(x[0][0]) for x in batch)
+    streams = [[x[1] for x in batch]] + [[x[0][k] for x in batch] for k in (1, 2, 3)]
+    lings = [padder._prepare_scalar_inputs(s, T, pad).long() for s, pad in zip(streams, pad_ids)]
+    return {"input_lings": torch.stack(lings, dim=2),
+            "valid_input_lengths": torch.as_tensor([len(x[0][0]) - 1 for x in batch], dtype=torch.long),
+            "targets": padder._prepare_scalar_inputs([x[0][0] for x in batch], T, pad_ids[0]).long(),
+            "bert_masks": padder._prepare_scalar_inputs([x[2] for x in batch], T, 0.0)}
+
+
+def get_bert_text_datasets(metafile, root_dir, config, allow_cache, split_ratio=0.98):
+    """(train, valid) BERT_Text_Datasets over ``bert_train.lst`` / ``bert_valid.lst`` of every data directory, generated
+    from the raw metafile when missing."""
+    root_dir = root_dir if isinstance(root_dir, list) else [root_dir]
+    metafile = metafile if isinstance(metafile, list) else [metafile]
+    train_lst, valid_lst = [], []
+    for raw_metafile, data_dir in zip(metafile, root_dir):
+        train_meta, valid_meta = os.path.join(data_dir, "bert_train.lst"), os.path.join(data_dir, "bert_valid.lst")
+        if not os.path.exists(train_meta) or not os.path.exists(valid_meta):
+            BERT_Text_Dataset.gen_metafile(raw_metafile, data_dir, split_ratio)
+        train_lst.append(train_meta)
+        valid_lst.append(valid_meta)
+    return (BERT_Text_Dataset(config, train_lst, root_dir, allow_cache),
+            BERT_Text_Dataset(config, valid_lst, root_dir, allow_cache))
+
+
 logging.getLogger(__name__).addHandler(logging.NullHandler())

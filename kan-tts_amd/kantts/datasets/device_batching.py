@@ -220,6 +220,55 @@ class DeviceAMSet:
         return out
 
 
+class DeviceTextSet:
+    """sy-BERT pre-training corpus in HBM: ``items`` = the encoded sentences (``BERT_Text_Dataset.encoded(i)``: integer
+    streams sy | tone | syllable_flag | word_segment [| ...], each ending with the id of "~"), uploaded once as flat
+    (symbols, 4) rows.  ``batch(indices)`` gives the four fields of ``BERT_Text_Dataset.collate_fn`` on the device:
+    ``valid_input_lengths``, ``targets`` and columns 1-3 of ``input_lings`` equal the host collate of the same sentences;
+    column 0 of ``input_lings`` and ``bert_masks`` (fp32) are DRAWN ON THE DEVICE -- what
+    ``bert_masking.draw(seed, counter, targets, lens, mask_ratio, mask_id, nsym)`` gives for the set's ``seed`` and the
+    number ``counter`` of batches drawn before (both live in device memory, ``self.words``).  Two launches (the gather of the
+    rows, then kantts_bert_mask_rows in place, which also leaves the dense targets), two small uploads (offsets and lengths),
+    nothing read back: the width T comes from the host copy of the lengths."""
+
+    KEYS = ("input_lings", "valid_input_lengths", "targets", "bert_masks")
+
+    def __init__(self, items, pad_ids, device, mask_ratio, mask_id, nsym, seed=0):
+        hip.require_sybert()
+        self.device = torch.device(device)
+        self.mask_ratio, self.mask_id, self.nsym, self.seed = float(mask_ratio), int(mask_id), int(nsym), int(seed)
+        if not 0.0 <= self.mask_ratio <= 1.0:
+            raise ValueError("mask_ratio %r is outside [0, 1]" % (mask_ratio,))
+        self.n_sym = np.array([len(it[0]) for it in items], dtype=np.int64)
+        if len(items) and int(self.n_sym.max()) > hip.SYBERT_MAX_T:
+            raise ValueError("a sentence of %d symbols: kantts_bert_mask_rows takes at most %d" % (
+                int(self.n_sym.max()), hip.SYBERT_MAX_T))
+        self.ling, self.sym_off = _flat([np.stack([np.asarray(s) for s in it[:4]], axis=1) for it in items], np.int64,
+                                        self.device)
+        self.pad_ids = torch.as_tensor(list(pad_ids)[:4], dtype=torch.int64).to(self.device)
+        self.words = torch.tensor([self.seed - (1 << 64) if self.seed >= 1 << 63 else self.seed, 0],
+                                  dtype=torch.int64).to(self.device)  # {seed, counter}: kantts_bert_mask_rows advances it
+
+    def __len__(self):
+        return len(self.n_sym)
+
+    def batch(self, indices):
+        from kantts._hip import ops
+
+        idx = np.asarray(indices, dtype=np.int64)
+        B, T = len(idx), int(self.n_sym[idx].max())
+        if B >= hip.SYBERT_MAX_B:
+            raise ValueError("a batch of %d sentences: kantts_bert_mask_rows takes fewer than %d" % (B, hip.SYBERT_MAX_B))
+        up = _dev(np.stack([self.sym_off[idx], self.n_sym[idx] - 1]), torch.int64, self.device)  # offsets | lengths minus "~"
+        n32 = _dev(self.n_sym[idx], torch.int32, self.device)
+        ling = hip.ragged_rows(self.ling, up[0], n32, T, pad=self.pad_ids)
+        masks = torch.empty((B, T), device=self.device, dtype=torch.float32)
+        targets = torch.empty((B, T), device=self.device, dtype=torch.int64)
+        ops.bert_mask_rows(self.words, None, n32, ling, masks, mask_ratio=self.mask_ratio, mask_id=self.mask_id,
+                           nsym=self.nsym, targets_out=targets)
+        return {"input_lings": ling, "valid_input_lengths": up[1], "targets": targets, "bert_masks": masks}
+
+
 class PinnedPrefetcher:
     """Iterate a loader of HOST batches (dicts / tuples / lists of tensors, as the collate functions return) and yield
     DEVICE batches: batch i + 1 is staged in pinned memory and copied on a side stream while the consumer runs step i
@@ -359,13 +408,17 @@ def make_train_loader(kind, dataset, host_loader, device, batch_size, sampler=No
     """``--device_corpus`` of the training entry points.  ``mode``: "hbm" = upload ``dataset`` once and assemble batches on
     the device (DeviceCorpusLoader); "pinned" = keep the host DataLoader and stage / copy its batches one step ahead
     (PinnedPrefetcher); "auto" = "hbm" when the payload takes less than half of the free device memory, else "pinned";
-    "off" = ``host_loader`` as the reference builds it.  ``kind``: "am" (AM_Dataset: duration-supervised, filled-pause,
+    "off" = ``host_loader`` as the reference builds it.  ``kind``: "bert" (BERT_Text_Dataset, the sy-BERT pre-training
+    corpus: DeviceTextSet, whose masks are drawn on the device; its seed is the dataset seed mixed with the rank of a
+    data-parallel run), "am" (AM_Dataset: duration-supervised, filled-pause,
     duration-free (MAS) and speaker-embedding (SE) voices) or "voc" (Voc_Dataset).  A MAS dataset is materialised with
     ``attach_prior`` off (restored afterwards): its prior is evaluated on the device.  With a library built before the MAS /
     SE entry points, "auto" / "hbm" log why and stage host batches ("pinned") for those voices."""
     device = torch.device(device)
     if mode == "off":
         return host_loader
+    if kind == "bert":
+        return _bert_train_loader(dataset, host_loader, device, batch_size, sampler, mode)
     fp = kind == "am" and bool(getattr(dataset, "fp_enable", False))
     if fp and device.type != "cuda":
         raise NotImplementedError("--device_corpus with a filled-pause (FP) model on device '%s': the device-side batch "
@@ -410,3 +463,30 @@ def make_train_loader(kind, dataset, host_loader, device, batch_size, sampler=No
         return DeviceCorpusLoader(dset, batch_size, sampler=sampler, shuffle=sampler is None,
                                   drop_last=bool(getattr(host_loader, "drop_last", False)))
     return PinnedPrefetcher(host_loader, device, r=r)
+
+
+def _bert_train_loader(dataset, host_loader, device, batch_size, sampler, mode):
+    """make_train_loader for ``kind == "bert"``: the encoded sentences are a few bytes per symbol, so "auto" is "hbm" unless
+    the library lacks the sy-BERT entry points (then, and on a host device, the host loader stays)."""
+    if device.type != "cuda":
+        return host_loader
+    if mode == "pinned":
+        return PinnedPrefetcher(host_loader, device)
+    if not hip.has_sybert():
+        logging.warning("--device_corpus %s: this libkantts_hip.so does not export %s, which a device-resident sy-BERT "
+                        "corpus needs; keeping the host loader", mode, ", ".join(hip.SYBERT_SYMBOLS))
+        return host_loader
+    from kantts.datasets import bert_masking
+    from kantts.datasets.dataset import DATASET_RANDOM_SEED
+
+    items = [dataset.encoded(i) for i in range(len(dataset))]
+    if mode == "auto":
+        free, _ = torch.cuda.mem_get_info(device)
+        if corpus_bytes(items) * 2 > free // 2:  # (uploaded as int64 rows)
+            return PinnedPrefetcher(host_loader, device)
+    rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
+    seed = int(bert_masking.mix(DATASET_RANDOM_SEED, rank)) if rank else DATASET_RANDOM_SEED
+    pad_ids = [dataset.ling_unit._sub_unit_pad[t] for t in dataset.ling_unit._lfeat_type_list[:4]]
+    dset = DeviceTextSet(items, pad_ids, device, dataset.masking_actor.mask_ratio, dataset.mask_id, dataset.nsym, seed=seed)
+    return DeviceCorpusLoader(dset, batch_size, sampler=sampler, shuffle=sampler is None,
+                              drop_last=bool(getattr(host_loader, "drop_last", False)))

@@ -112,19 +112,27 @@ def hifigan_model_builder(config, device, rank, distributed, use_arena=None):
     return model, optimizer, scheduler
 
 
-def sybert_model_builder(config, device, rank, distributed):
+def sybert_model_builder(config, device, rank, distributed, use_arena=None):
     model, optimizer, scheduler = {}, {}, {}
     conf = config["Model"]["KanTtsTextsyBERT"]
-    model["KanTtsTextsyBERT"] = KanTtsTextsyBERT(conf["params"]).to(device)
-    optimizer["KanTtsTextsyBERT"] = optimizer_builder(model["KanTtsTextsyBERT"].parameters(),
-                                                      conf["optimizer"].get("type", "Adam"),
-                                                      conf["optimizer"].get("params", {}))
+    net = KanTtsTextsyBERT(conf["params"]).to(device)
+    model["KanTtsTextsyBERT"] = net
+    opt_type = conf["optimizer"].get("type", "Adam")
+    opt_params = conf["optimizer"].get("params", {})
+    if use_arena is None:
+        use_arena = _is_hip(device) and opt_type == "Adam" and not opt_params.get("amsgrad", False)
+    if use_arena:  # as for the acoustic model: one fused Adam launch over the flat parameters, clipping folded in
+        arena = ParamArena(net, bf16_shadow=True)
+        optimizer["KanTtsTextsyBERT"] = ArenaAdam(arena, **opt_params)
+        if distributed:
+            arena.enable_data_parallel()
+    else:
+        optimizer["KanTtsTextsyBERT"] = optimizer_builder(net.parameters(), opt_type, opt_params)
+        if distributed:
+            model["KanTtsTextsyBERT"] = DistributedDataParallel(net, device_ids=[rank], output_device=rank)
     scheduler["KanTtsTextsyBERT"] = scheduler_builder(optimizer["KanTtsTextsyBERT"],
                                                       conf["scheduler"].get("type", "StepLR"),
                                                       conf["scheduler"].get("params", {}))
-    if distributed:
-        model["KanTtsTextsyBERT"] = DistributedDataParallel(model["KanTtsTextsyBERT"], device_ids=[rank],
-                                                            output_device=rank)
     return model, optimizer, scheduler
 
 

@@ -982,17 +982,57 @@ class KanTtsSAMBERT(nn.Module):
         return res
 
 
+# KANTTS_SYBERT_STOCK_HEAD=1 (read once, here): the training form of KanTtsTextsyBERT runs its head as ops.linear +
+# SeqCELoss on stock launches instead of the fused ops.mlm_head_ce -- the yardstick of scripts/sybert_bench.py
+_SYBERT_STOCK_HEAD = os.environ.get("KANTTS_SYBERT_STOCK_HEAD", "0") not in ("", "0")
+
+
+class _GradScale(torch.autograd.Function):
+    """Identity whose gradient is multiplied by a host scalar."""
+
+    @staticmethod
+    def forward(ctx, x, scale):
+        ctx.scale = scale
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.scale, None
+
+
 class KanTtsTextsyBERT(nn.Module):
-    """Masked-LM pre-training wrapper.  Broken at the reference HEAD (SURVEY section 2 row 18:
-    forward unpacks 2 of 3 encoder outputs); kept constructible for state_dict parity only."""
+    """sy-BERT: the text encoder (without its projection) under a Linear(d_model -> |sy|) head, pre-trained as a masked
+    language model (kantts.bin.train_sybert); its checkpoint seeds ``text_encoder.*`` of the acoustic model through
+    ``train_sambert --resume_bert_path``.  Parameters and state_dict keys are the reference class's.
+
+    ``model(inputs_ling, input_lengths)`` returns ``{"logits", "enc_slf_attn_lst"}`` -- what the reference's forward
+    evidently means (it unpacks two of the encoder's three return values and raises: SURVEY section 2 row 18).  The
+    attention maps are materialised only when ``model.return_attns`` is set, as in KanTtsSAMBERT.
+
+    ``model(inputs_ling, input_lengths, targets, bert_masks)`` is the training form: the head and SeqCELoss run fused
+    (ops.mlm_head_ce, csrc/sybert.hip) and the result holds ``"loss"`` -- the value SeqCELoss returns, NOT divided by the
+    vocabulary size -- and ``"err"`` in place of ``"logits"``, which are never materialised.  ``grad_scale`` multiplies the
+    gradient that flows back from ``"loss"`` (the trainer passes its 1 / V here instead of scaling the loss itself)."""
 
     def __init__(self, config):
         super(KanTtsTextsyBERT, self).__init__()
         self.text_encoder = TextFftEncoder(config)
         delattr(self.text_encoder, "ling_proj")
         self.fc = nn.Linear(self.text_encoder.d_model, config["sy"])
+        self.return_attns = False
 
-    def forward(self, inputs_ling, input_lengths):
+    def forward(self, inputs_ling, input_lengths, targets=None, bert_masks=None, grad_scale=1.0):
         info = SeqInfo(input_lengths, inputs_ling.size(1))
-        text_hid, attns, _ = self.text_encoder(inputs_ling, info, return_attns=False)
-        return {"logits": ops.linear(text_hid, self.fc.weight, self.fc.bias), "enc_slf_attn_lst": attns}
+        text_hid, attns, _ = self.text_encoder(inputs_ling, info, return_attns=self.return_attns)
+        if targets is None:
+            return {"logits": ops.linear(text_hid, self.fc.weight, self.fc.bias), "enc_slf_attn_lst": attns}
+        if bert_masks is None:
+            raise ValueError("KanTtsTextsyBERT: targets without bert_masks")
+        if _SYBERT_STOCK_HEAD:
+            from kantts.train.loss import SeqCELoss
+
+            loss, err = SeqCELoss()(ops.linear(text_hid, self.fc.weight, self.fc.bias), targets, bert_masks)
+            loss = loss if grad_scale == 1.0 else _GradScale.apply(loss, grad_scale)
+        else:
+            loss, err = ops.mlm_head_ce(text_hid, self.fc.weight, self.fc.bias, targets, bert_masks, gscale=grad_scale)
+        return {"loss": loss, "err": err, "enc_slf_attn_lst": attns}

@@ -352,7 +352,30 @@ class AttentionCTCLoss(torch.nn.Module):
         return loss.mean()
 
 
+class SeqCELoss(torch.nn.Module):
+    """The sy-BERT criterion (reference :444-460) on a logits tensor: the masked mean of the per-token cross entropy and of
+    [arg-max != target], ``forward(logits, targets, masks) -> (loss, err)``.  This is the PARITY path on stock device
+    operations; training goes through the fused head, which never forms the logits (ops.mlm_head_ce, csrc/sybert.hip, the
+    four-argument form of KanTtsTextsyBERT.forward) and, unlike this class and the reference, lets a non-finite logit on a
+    row with mask 0 leave no trace."""
+
+    def __init__(self, loss_type="ce"):
+        super(SeqCELoss, self).__init__()
+        if loss_type != "ce":
+            raise ValueError("Unknown loss type: {}".format(loss_type))
+        self.loss_type = loss_type
+
+    def forward(self, logits, targets, masks):
+        flat = logits.contiguous().view(-1, logits.size(-1))
+        tg, mk = targets.contiguous().view(-1), masks.contiguous().view(-1)
+        ce = F.cross_entropy(flat, tg, reduction="none")
+        wrong = torch.argmax(flat, dim=-1) != tg
+        total = mk.sum()
+        return (ce * mk).sum() / total, (wrong * mk).sum() / total
+
+
 loss_dict = {
+    "SeqCELoss": SeqCELoss,
     "AttentionBinarizationLoss": AttentionBinarizationLoss,
     "AttentionCTCLoss": AttentionCTCLoss,
     "MelReconLoss": MelReconLoss,

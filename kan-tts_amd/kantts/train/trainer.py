@@ -495,3 +495,124 @@ class GAN_Trainer(Trainer):
                     getattr(self, part)["generator"].load_state_dict(state_dict[part]["generator"])
                     for name, s in state_dict[part]["discriminator"].items():
                         getattr(self, part)["discriminator"][name].load_state_dict(s)
+
+
+class Textsy_BERT_Trainer(Trainer):
+    """sy-BERT pre-training (reference :1045-1219): masked-LM steps of KanTtsTextsyBERT on the batches of
+    BERT_Text_Dataset.collate_fn / DeviceTextSet.batch.  Same constructor arguments, checkpoint layout and logged names
+    (``TotalLoss`` = SeqCELoss / V, ``Error``, ``batch_size``).  Both steps go through the fused head
+    (``model(ling, lengths, targets, bert_masks)``: the logits are never formed); the 1 / V of the reference's
+    ``loss_total / logits.size(-1)`` reaches the backward as the head's gradient scale, the logged loss is divided on the
+    device.  Nothing is read back per step."""
+
+    KEY = "KanTtsTextsyBERT"
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.grad_clip is not None and hasattr(self.optimizer[self.KEY], "set_grad_clip"):
+            self.optimizer[self.KEY].set_grad_clip(self.grad_clip)
+
+    def _to_device(self, batch):
+        to = lambda t, dt: t.to(device=self.device, dtype=dt, non_blocking=True)  # noqa: E731
+        return (to(batch["input_lings"], torch.int64), to(batch["valid_input_lengths"], torch.int64),
+                to(batch["targets"], torch.int64), to(batch["bert_masks"], torch.float32))
+
+    def _vocab(self):
+        net = self.model[self.KEY]
+        return getattr(net, "module", net).fc.out_features
+
+    def train_step(self, batch):
+        ling, lens, targets, masks = self._to_device(batch)
+        net, opt, sch = self.model[self.KEY], self.optimizer[self.KEY], self.scheduler[self.KEY]
+        if ling.is_cuda:
+            from kantts._hip import ops
+
+            ops.advance_rng(self.device)
+        inv_v = 1.0 / self._vocab()
+        res = net(ling, lens, targets, masks, grad_scale=inv_v)
+        total = res["loss"].detach() * inv_v
+        self._accumulate("train", {"TotalLoss": total, "Error": res["err"], "batch_size": float(targets.size(0))})
+        opt.zero_grad()
+        res["loss"].backward()
+        if self.grad_clip is not None and not hasattr(opt, "set_grad_clip"):
+            torch.nn.utils.clip_grad_norm_(net.parameters(), self.grad_clip)
+        opt.step()
+        sch.step()
+        return total
+
+    @torch.no_grad()
+    def eval_step(self, batch):
+        ling, lens, targets, masks = self._to_device(batch)
+        res = self.model[self.KEY](ling, lens, targets, masks)
+        self._accumulate("eval", {"TotalLoss": res["loss"] * (1.0 / self._vocab()), "Error": res["err"],
+                                  "batch_size": float(targets.size(0))})
+
+    @torch.no_grad()
+    def eval_epoch(self):
+        """The base loop, and intermediate results for the first ``num_save_intermediate_results`` validation batches."""
+        keep = int(self.config.get("num_save_intermediate_results", 0))
+        if self.rank == 0 and self.log_dir is not None and keep > 0:
+            self.set_model_state("eval")
+            for n, batch in enumerate(self.valid_loader):
+                if n >= keep:
+                    break
+                self.genearete_and_save_intermediate_result(batch, tag=str(n) if n else "")
+        super().eval_epoch()
+
+    @torch.no_grad()
+    def genearete_and_save_intermediate_result(self, batch, tag=""):
+        """(the reference's spelling)  For the first sentence of ``batch``: ``pred.npy`` (arg-max symbol per position),
+        ``target.npy``, ``bert_mask.npy`` and, when matplotlib is installed, one attention plot per encoder layer and head,
+        under ``<log_dir>/predictions/<steps>steps[<tag>]``."""
+        import numpy as np
+
+        ling, lens, targets, masks = self._to_device(batch)
+        net = self.model[self.KEY]
+        net = getattr(net, "module", net)
+        want, net.return_attns = net.return_attns, True
+        try:
+            res = net(ling[0:1], lens[0:1])
+        finally:
+            net.return_attns = want
+        dirname = os.path.join(self.log_dir, "predictions", "%dsteps%s" % (self.steps, tag))
+        os.makedirs(dirname, exist_ok=True)
+        np.save(os.path.join(dirname, "pred.npy"), torch.argmax(res["logits"], dim=-1).reshape(-1).cpu().numpy())
+        np.save(os.path.join(dirname, "target.npy"), targets[0].cpu().numpy())
+        np.save(os.path.join(dirname, "bert_mask.npy"), masks[0].cpu().numpy())
+        try:
+            import matplotlib
+
+            matplotlib.use("Agg")
+            import matplotlib.pyplot as plt
+        except Exception:  # noqa: BLE001 - the plots are optional
+            return dirname
+        n = int(lens[0])
+        heads = self.config["Model"][self.KEY]["params"]["encoder_num_heads"]
+        for layer, attn in enumerate(res["enc_slf_attn_lst"] or []):
+            if attn is None:
+                continue
+            for head in range(heads):
+                fig, ax = plt.subplots()
+                im = ax.imshow(attn[head, :n, :n].float().cpu().numpy(), aspect="auto", origin="lower", interpolation="none")
+                fig.colorbar(im, ax=ax)
+                ax.set_xlabel("Input timestep\n\nvalid_len_%d" % n)
+                ax.set_ylabel("Output timestep")
+                fig.savefig(os.path.join(dirname, "enc_slf_attn_dev_layer%d_head%d" % (layer, head)))
+                plt.close(fig)
+        return dirname
+
+    def save_checkpoint(self, checkpoint_path):
+        net = self.model[self.KEY]
+        state_dict = {"optimizer": self.optimizer[self.KEY].state_dict(), "scheduler": self.scheduler[self.KEY].state_dict(),
+                      "steps": self.steps, "model": getattr(net, "module", net).state_dict()}
+        os.makedirs(os.path.dirname(checkpoint_path), exist_ok=True)
+        torch.save(state_dict, checkpoint_path)
+
+    def load_checkpoint(self, checkpoint_path, restore_training_state=False, strict=True):
+        state_dict = torch.load(checkpoint_path, map_location="cpu")
+        net = self.model[self.KEY]
+        getattr(net, "module", net).load_state_dict(state_dict["model"], strict=strict)
+        if restore_training_state:
+            self.optimizer[self.KEY].load_state_dict(state_dict["optimizer"])
+            self.scheduler[self.KEY].load_state_dict(state_dict["scheduler"])
+            self.steps = state_dict["steps"]
