@@ -416,8 +416,12 @@ int kantts_fsmn_memory_drop_bwd_pair(const kantts_fsmn_drop_args* a, const kantt
                                      int B, int T, int C, int K, int left_pad, const uint64_t* seed_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Masked L1 ("mae") reduction: loss_accum[0] += sum_{t<lens[b]} |target-pred| / (sum(lens)*C);
- * grad (optional, (B,T,C)) = d loss / d pred.  kantts/train/loss.py:18-37, :51-85. */
+ * Masked L1 ("mae") reduction: loss_accum[0] += sum_{t<rows_b} |target-pred| / (sum_b(rows_b)*C);
+ * grad (optional, (B,T,C)) = d loss / d pred: sign(pred-target) / (sum_b(rows_b)*C) on valid rows, 0 on the others.
+ * Sequence b has rows_b = min(lens[b], T) valid rows, in the mask and in the denominator; lens[b] >= 0 (the kernels do not
+ * agree on a negative length).  B*T*C == 0: KANTTS_OK, nothing is read or written.  A non-empty call whose lengths are all
+ * 0 adds NaN (the reference's 0 / 0) and writes a gradient of zeros.
+ * kantts/train/loss.py:18-37, :51-85. */
 int kantts_masked_l1(const float* pred, const float* target, const int64_t* lens, float* loss_accum, float* grad,
                      int B, int T, int C, void* stream);
 
@@ -497,7 +501,9 @@ int kantts_melspec_bwd(const float* wav, const float* dmel, int B, int T, int n_
  * log-duration / pitch / energy: kantts/train/loss.py:7-85) in ONE launch: term k over pred (B, T, C) against target
  * (float, or -- target_log1p -- int64 values v read as log(v + 1): the duration targets) on rows t < lens[b];
  * losses[k] += mean |target - pred|, losses[KANTTS_LOSS_MAX_TERMS] += the same (the step's total); grad[k] (optional) =
- * d term k / d pred as kantts_masked_l1 writes it.  losses must be zeroed by the caller. */
+ * d term k / d pred as kantts_masked_l1 writes it.  losses must be zeroed by the caller.  Valid rows are
+ * min(lens[b], T), lens[b] >= 0, as for kantts_masked_l1.  Every term must be non-empty (B*T*C > 0: an empty term adds NaN
+ * to losses[k] and to the total).  A term whose lengths are all 0 adds NaN to losses[k] and to the total as well. */
 #define KANTTS_LOSS_MAX_TERMS 5
 typedef struct kantts_loss_term {
   const float* pred;
@@ -531,7 +537,10 @@ int kantts_elem_loss_many(const kantts_eloss_term* terms, int nterms, float* los
 
 /* ------------------------------------------------------------------------------------------
  * weight_norm reparametrisation w = g * v / ||v|| per output row (torch.nn.utils.weight_norm, dim=0):
- * kantts/models/hifigan/layers.py:29,67,105,139, hifigan.py:224,332.  v,w,dw,dv: (rows, cols); g,dg: (rows). */
+ * kantts/models/hifigan/layers.py:29,67,105,139, hifigan.py:224,332.  v,w,dw,dv: (rows, cols); g,dg: (rows).
+ * Backward: dg = sum(dw * v) / ||v||, dv = (g / ||v||) * (dw - v * dg / ||v||).  A row of v that is all zeros has
+ * ||v|| = 0: every output of that row (w and its bf16 images, dg, dv) is NaN, as torch.nn.utils.weight_norm gives, and no
+ * other row is affected.  This holds for all entry points of the family below. */
 int kantts_weight_norm_fwd(const float* v, const float* g, float* w, int rows, int cols, void* stream);
 int kantts_weight_norm_bwd(const float* dw, const float* v, const float* g, float* dv, float* dg, int rows,
                            int cols, void* stream);

@@ -1364,15 +1364,19 @@ class EmulatedLib:
 
     # ------------------------------------------------------------------------------------ loss / optim
     def kantts_masked_l1(self, pred, target, lens, loss, grad, B, T, C, stream):
+        if B * T * C == 0:
+            return 0
         P = _arr(pred, B * T * C).reshape(B, T, C)
         Tg = _arr(target, B * T * C).reshape(B, T, C)
         ln = np.minimum(_arr(lens, B, np.int64), T)
         keep = (np.arange(T)[None, :] < ln[:, None])[:, :, None]
-        inv = np.float32(1.0) / (np.float32(ln.sum()) * np.float32(C))
-        d = P - Tg
-        _arr(loss, 1)[0] += np.float32((np.abs(d) * keep).sum(dtype=np.float64)) * inv
-        if grad:
-            _arr(grad, B * T * C)[:] = (np.sign(d) * keep * inv).astype(np.float32).ravel()
+        with np.errstate(divide="ignore", invalid="ignore"):  # (all lengths 0: the reference's 0 / 0)
+            inv = np.float32(1.0) / (np.float32(ln.sum()) * np.float32(C))
+            d = P - Tg
+            _arr(loss, 1)[0] += np.float32((np.abs(d) * keep).sum(dtype=np.float64)) * inv
+        if grad:  # +-inv on valid rows, +0 on the others and on ties (no -0.0: the single and the _many call give the same bits)
+            gr = np.where(keep & (d > 0), inv, np.where(keep & (d < 0), -inv, np.float32(0)))
+            _arr(grad, B * T * C)[:] = gr.astype(np.float32).ravel()
         return 0
 
     def kantts_elem_loss(self, a, b, target, mode, scale, loss, grad, n, stream):
@@ -1397,6 +1401,8 @@ class EmulatedLib:
         return 0
 
     def kantts_sumsq(self, x, out, n, stream):
+        if n == 0:
+            return 0
         a = _arr(x, n)
         _arr(out, 1)[0] += np.float32((a.astype(np.float64) ** 2).sum())
         return 0
@@ -2002,13 +2008,15 @@ class EmulatedLib:
                 tgt = _arr(q.target, n).reshape(q.B, q.T, q.C)
             lens = np.minimum(_arr(q.lens, q.B, np.int64), q.T)
             valid = (np.arange(q.T)[None, :] < lens[:, None])[:, :, None]
-            inv = np.float32(1.0) / (np.float32(lens.sum()) * np.float32(q.C))
-            d = (pred - tgt) * valid
-            val = np.float32(np.abs(d).sum(dtype=np.float64)) * inv
+            with np.errstate(divide="ignore", invalid="ignore"):  # (all lengths 0: the reference's 0 / 0)
+                inv = np.float32(1.0) / (np.float32(lens.sum()) * np.float32(q.C))
+                d = pred - tgt
+                val = np.float32((np.abs(d) * valid).sum(dtype=np.float64)) * inv
             L[k] += val
             L[5] += val
             if q.grad:
-                _arr(q.grad, n)[:] = (np.sign(d) * inv * valid).astype(np.float32).ravel()
+                gr = np.where(valid & (d > 0), inv, np.where(valid & (d < 0), -inv, np.float32(0)))
+                _arr(q.grad, n)[:] = gr.astype(np.float32).ravel()
         return 0
 
     def kantts_scale_many(self, x, n, count, scale_dev, stream):
