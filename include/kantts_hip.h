@@ -381,6 +381,26 @@ int kantts_fsmn_dwconv_bwd(const float* dy, const float* x, const float* w, cons
                            int left_pad, void* stream);
 /* floats of caller-owned workspace the backward needs (weight-gradient partials; 0 when none) */
 long long kantts_fsmn_dwconv_bwd_ws(int B, int T, int C, int K);
+/* The 41-tap filter gradient of up to KANTTS_FIR_DW_MAX memory blocks in two launches for all of them (the filter gradient
+ * is a leaf of the backward graph: the host records the problems of a step and issues them together).  Per problem:
+ * dw_accum (C, 41) += the filter gradient of kantts_fsmn_dwconv_bwd(dy, x, lens, dx = NULL, ...) with K = 41, the same
+ * workgroups, arithmetic and summation order, hence the same bits; workspace as for that call
+ * (kantts_fsmn_dwconv_bwd_ws(B, T, C, 41) floats; nothing behind ws_floats is written); lens may be NULL.  Problems may
+ * differ in every field; their dw_accum and workspace ranges must not overlap.  A problem with B == 0 or T == 0 is skipped;
+ * nprob == 0 launches nothing.  KANTTS_E_BADARG: nprob outside [0, KANTTS_FIR_DW_MAX], a NULL dy / x / dw_accum, B < 0,
+ * T < 0, C < 1; KANTTS_E_WORKSPACE: a NULL or short workspace; KANTTS_E_UNSUPPORTED: more than 2^31 - 1 workgroups.  On an
+ * error nothing is launched. */
+#define KANTTS_FIR_DW_MAX 16
+typedef struct kantts_fir_dw_problem {
+  const float* dy;
+  const float* x;
+  const int64_t* lens;
+  float* dw_accum;
+  float* workspace;
+  long long ws_floats;
+  int32_t B, T, C, left_pad;
+} kantts_fir_dw_problem;
+int kantts_fsmn_dw41_many(const kantts_fir_dw_problem* probs, int nprob, void* stream);
 /* The memory block of a training step with the two dropouts stacked on it and the residual add, one launch each way
  * (K == 41; c, res, y, dy, dx, dym (B,T,C) fp32 contiguous, w (C,K), lens int64[B] or NULL):
  *   fwd: y = keep2 * (keep1 * m) (+ res),  m = kantts_fsmn_dwconv_fwd(c, w, res = NULL, lens)

@@ -3,6 +3,8 @@
 //   * length regulator as an index gather + segment-sum backward    adaptors.py:15-36
 //   * duration-relative positions                                   positions.py:72-90
 //   * FSMN memory block: depth-wise FIR (k taps) + residual + masks fsmn.py:43-72
+#include <limits.h>
+
 #include "common.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -558,13 +560,14 @@ __global__ __launch_bounds__(256, 2) void fsmn_fir41_kernel(const float* __restr
 // of two windows.)
 #define FS_CH 128
 #define FS_SUB (FS_CH / 4)
-__global__ __launch_bounds__(256) void fsmn_dw41_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                            const int64_t* __restrict__ lens,
-                                                            float* __restrict__ part, int B, int T, int C, int lp) {
-  __shared__ float sm[4][FS_K][65];
-  const int b = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
+// The body of one workgroup (chunk, b, cgroup) of one problem: shared by the single-problem kernel and the many-problem one
+// (kantts_fsmn_dw41_many), so that both give the same bits.
+__device__ __forceinline__ void fsmn_dw41_partial_body(const float* __restrict__ dy, const float* __restrict__ x,
+                                                       const int64_t* __restrict__ lens, float* __restrict__ part, int T,
+                                                       int C, int lp, int chunk, int nchunk, int b, int cgroup,
+                                                       float (*sm)[FS_K][65]) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int c0 = blockIdx.z * 64, c = c0 + lane;
+  const int c0 = cgroup * 64, c = c0 + lane;
   const bool cok = c < C;
   const int cc = cok ? c : 0;
   const int len = lens ? (int)min((long long)lens[b], (long long)T) : T;
@@ -610,14 +613,48 @@ __global__ __launch_bounds__(256) void fsmn_dw41_partial_kernel(const float* __r
   }
 }
 
+__global__ __launch_bounds__(256) void fsmn_dw41_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                            const int64_t* __restrict__ lens,
+                                                            float* __restrict__ part, int B, int T, int C, int lp) {
+  __shared__ float sm[4][FS_K][65];
+  fsmn_dw41_partial_body(dy, x, lens, part, T, C, lp, blockIdx.x, gridDim.x, blockIdx.y, blockIdx.z, sm);
+}
+
+// Up to KANTTS_FIR_DW_MAX filter gradients per launch (kantts_fsmn_dw41_many): the filter gradient of every FSMN layer is a
+// leaf of the backward graph, so the host records them and issues the recorded ones together.  The table travels in the
+// kernel arguments; pend / rend are the running totals of workgroups (partial launch / reduce launch) up to and including
+// each problem.
+struct FirDwManyArgs {
+  const float* dy[KANTTS_FIR_DW_MAX];
+  const float* x[KANTTS_FIR_DW_MAX];
+  const int64_t* lens[KANTTS_FIR_DW_MAX];
+  float* part[KANTTS_FIR_DW_MAX];
+  float* dw[KANTTS_FIR_DW_MAX];
+  int B[KANTTS_FIR_DW_MAX], T[KANTTS_FIR_DW_MAX], C[KANTTS_FIR_DW_MAX], lp[KANTTS_FIR_DW_MAX];
+  int pend[KANTTS_FIR_DW_MAX], rend[KANTTS_FIR_DW_MAX];
+  int nprob;
+};
+
+// A workgroup belongs to the first problem whose running total is above its id (a scan that is the same for every thread);
+// its ids inside the problem run as the single-problem grid does: chunk fastest, then b, then the channel group.
+__global__ __launch_bounds__(256) void fsmn_dw41_partial_many_kernel(const FirDwManyArgs g) {
+  __shared__ float sm[4][FS_K][65];
+  const int id = blockIdx.x;
+  int q = 0;
+  while (q < g.nprob - 1 && id >= g.pend[q]) ++q;
+  const int local = id - (q ? g.pend[q - 1] : 0);
+  const int T = g.T[q], B = g.B[q], nchunk = (T + FS_CH - 1) / FS_CH;
+  const int chunk = local % nchunk, rest = local / nchunk;
+  fsmn_dw41_partial_body(g.dy[q], g.x[q], g.lens[q], g.part[q], T, g.C[q], g.lp[q], chunk, nchunk, rest % B, rest / B, sm);
+}
+
 // dw[i] += sum over the partial rows, in a fixed order: thread = (output i, one of 8 interleaved slices of the rows), the
 // slices meet in LDS.  (One thread per output walking all rows -- 41 workgroups, 128 dependent loads -- took 21.5 us.)
 #define FS_RS 8
-__global__ __launch_bounds__(64 * FS_RS) void fsmn_dw_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw,
-                                                                    int nblk, int n) {
-  __shared__ float sm[FS_RS][64];
+__device__ __forceinline__ void fsmn_dw_reduce_body(const float* __restrict__ part, float* __restrict__ dw, int nblk, int n,
+                                                    int blk, float (*sm)[64]) {
   const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + lane;
+  const int i = blk * 64 + lane;
   const bool ok = i < n;
   const long long ii = ok ? i : 0;
   float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
@@ -636,6 +673,21 @@ __global__ __launch_bounds__(64 * FS_RS) void fsmn_dw_reduce_kernel(const float*
     for (int q = 0; q < FS_RS; ++q) s += sm[q][lane];
     dw[i] += s;
   }
+}
+
+__global__ __launch_bounds__(64 * FS_RS) void fsmn_dw_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw,
+                                                                    int nblk, int n) {
+  __shared__ float sm[FS_RS][64];
+  fsmn_dw_reduce_body(part, dw, nblk, n, blockIdx.x, sm);
+}
+
+__global__ __launch_bounds__(64 * FS_RS) void fsmn_dw_reduce_many_kernel(const FirDwManyArgs g) {
+  __shared__ float sm[FS_RS][64];
+  const int id = blockIdx.x;
+  int q = 0;
+  while (q < g.nprob - 1 && id >= g.rend[q]) ++q;
+  const int nblk = g.B[q] * ((g.T[q] + FS_CH - 1) / FS_CH);
+  fsmn_dw_reduce_body(g.part[q], g.dw[q], nblk, g.C[q] * FS_K, id - (q ? g.rend[q - 1] : 0), sm);
 }
 
 static int fs_xcd_order() {
@@ -732,6 +784,34 @@ extern "C" int kantts_fsmn_dwconv_bwd(const float* dy, const float* x, const flo
       hipLaunchKernelGGL(fsmn_dwconv_bwd_dw_kernel, dim3(kantts_cdiv(T, DW_WT), B), dim3(threads), 0, st, dy, x, lens,
                          dw_accum, B, T, C, K, left_pad);
   }
+  KANTTS_CHECK_LAUNCH();
+}
+
+// The 41-tap filter gradient of nprob memory blocks in TWO launches for all of them (partials, then the fixed-order reduce):
+// per problem the workgroups, their arithmetic and its order are those of kantts_fsmn_dwconv_bwd(dx = NULL), so every
+// dw_accum receives the same bits.  Problems with B == 0 or T == 0 are skipped.
+extern "C" int kantts_fsmn_dw41_many(const kantts_fir_dw_problem* probs, int nprob, void* stream) {
+  if (nprob < 0 || nprob > KANTTS_FIR_DW_MAX || (nprob > 0 && !probs)) return KANTTS_E_BADARG;
+  FirDwManyArgs g = {};
+  long long pend = 0, rend = 0;
+  for (int i = 0; i < nprob; ++i) {
+    const kantts_fir_dw_problem& p = probs[i];
+    if (!p.dy || !p.x || !p.dw_accum || p.B < 0 || p.T < 0 || p.C < 1 || p.C > INT_MAX / FS_K) return KANTTS_E_BADARG;
+    if (p.B == 0 || p.T == 0) continue;
+    const long long nchunk = kantts_cdiv(p.T, FS_CH);
+    if (!p.workspace || p.ws_floats < (long long)p.B * nchunk * p.C * FS_K) return KANTTS_E_WORKSPACE;
+    pend += nchunk * p.B * kantts_cdiv(p.C, 64);
+    rend += kantts_cdiv(p.C * FS_K, 64);
+    if (pend > INT_MAX || (long long)p.B * nchunk > INT_MAX) return KANTTS_E_UNSUPPORTED;
+    const int n = g.nprob++;
+    g.dy[n] = p.dy, g.x[n] = p.x, g.lens[n] = p.lens, g.part[n] = p.workspace, g.dw[n] = p.dw_accum;
+    g.B[n] = p.B, g.T[n] = p.T, g.C[n] = p.C, g.lp[n] = p.left_pad;
+    g.pend[n] = (int)pend, g.rend[n] = (int)rend;
+  }
+  if (g.nprob == 0) return KANTTS_OK;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(fsmn_dw41_partial_many_kernel, dim3((unsigned)pend), dim3(256), 0, st, g);
+  hipLaunchKernelGGL(fsmn_dw_reduce_many_kernel, dim3((unsigned)rend), dim3(64 * FS_RS), 0, st, g);
   KANTTS_CHECK_LAUNCH();
 }
 

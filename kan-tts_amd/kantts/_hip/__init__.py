@@ -418,6 +418,15 @@ class RowSumArgs(Structure):
                 ("src", c_void_p * ROWSUM_MAX), ("dst0", c_void_p * ROWSUM_MAX), ("dst1", c_void_p * ROWSUM_MAX)]
 
 
+FIR_DW_MAX = 16
+
+
+class FirDwProblem(Structure):
+    """kantts_fir_dw_problem (include/kantts_hip.h)."""
+    _fields_ = [("dy", c_void_p), ("x", c_void_p), ("lens", c_void_p), ("dw_accum", c_void_p), ("workspace", c_void_p),
+                ("ws_floats", c_longlong), ("B", c_int32), ("T", c_int32), ("C", c_int32), ("left_pad", c_int32)]
+
+
 class FragMajorDesc(Structure):
     """kantts_fragmajor_desc (include/kantts_hip.h)."""
     _fields_ = [("src_off", c_int64), ("dst_off", c_int64), ("sr", c_int64), ("sk", c_int64), ("R", c_int32),
@@ -476,6 +485,8 @@ def lib():
         if hasattr(L, "kantts_fsmn_memory_drop_fwd") and hasattr(L, "kantts_fsmn_memory_drop_bwd"):  # a library built
             L.kantts_fsmn_memory_drop_fwd.argtypes = [p, p, p, p, p, i, i, i, i, i, f, u64, f, u64, p, p]  # before them
             L.kantts_fsmn_memory_drop_bwd.argtypes = [p, p, p, p, p, i, i, i, i, i, f, u64, f, u64, p, p]  # still loads
+        if hasattr(L, "kantts_fsmn_dw41_many"):  # fir_dw_many_entry_point(): a library built before it still loads
+            L.kantts_fsmn_dw41_many.argtypes = [POINTER(FirDwProblem), i, p]
         L.kantts_masked_l1.argtypes = [p, p, p, p, p, i, i, i, p]
         L.kantts_sumsq.argtypes = [p, p, ll, p]
         L.kantts_elem_loss.argtypes = [p, p, f, i, f, p, p, ll, p]
@@ -652,6 +663,7 @@ EXPORTED_SYMBOLS = [
     *PREDICTOR_PAIR_SYMBOLS,
     *CORPUS_PRIOR_SYMBOLS,
     *SYBERT_SYMBOLS,
+    "kantts_fsmn_dw41_many",
 ]
 
 
@@ -1397,6 +1409,48 @@ def rows_sum_accum(src, dst0, dst1):
     rows_sum_many([(src, dst0, dst1)])
 
 
+def fir_dw_many_entry_point():
+    """True when the loaded library has the many-problem filter gradient (the numpy model of the C ABI does not)."""
+    return hasattr(lib(), "kantts_fsmn_dw41_many")
+
+
+def fir_dw_many(problems):
+    """problems: list of (dy (B,T,C), x (B,T,C), lens int64 (B) | None, dw (C,41), ws, ws_floats, B, T, C, left_pad), all
+    fp32 contiguous: dw += the 41-tap filter gradient of each, up to FIR_DW_MAX problems per pair of launches
+    (kantts_fsmn_dw41_many), the bits of kantts_fsmn_dwconv_bwd(dx = NULL) per problem.  A call must not hold one dw twice
+    (its adds are not ordered inside a launch): a repeated dw starts a new call."""
+    s0 = 0
+    while s0 < len(problems):
+        chunk, seen = [], set()
+        for q in problems[s0:s0 + FIR_DW_MAX]:
+            if ptr(q[3]) in seen:
+                break
+            seen.add(ptr(q[3]))
+            chunk.append(q)
+        s0 += len(chunk)
+        arr = (FirDwProblem * len(chunk))()
+        for g, (dy, x, lens, dw, ws, ws_n, B, T, C, lp) in zip(arr, chunk):
+            g.dy, g.x, g.lens = ptr(dy, torch.float32), ptr(x, torch.float32), ptr(lens, torch.int64)
+            g.dw_accum, g.workspace, g.ws_floats = ptr(dw, torch.float32), ptr(ws, torch.float32), int(ws_n)
+            g.B, g.T, g.C, g.left_pad = int(B), int(T), int(C), int(lp)
+        check(lib().kantts_fsmn_dw41_many(arr, len(chunk), stream()), "fsmn_dw41_many")
+
+
+def fir_dw_accum(dy, x, lens, dw, ws, ws_n, B, T, C, lp):
+    """dw (C, 41) += the filter gradient of a 41-tap memory block, as a RECORDED problem: every one recorded since the last
+    flush of the deferred weight gradients leaves in one pair of launches at the next flush (``fir_dw_many``) instead of a
+    fork of the weight-gradient stream and a pair of launches per layer.  The caller checked ``deferred_tn.enabled`` and
+    ``fir_dw_many_entry_point()``."""
+    ev = sid = None
+    if dy.is_cuda:
+        # the flush may run on another stream than this one (the predictors' side branch records, the main chain flushes):
+        # it waits for THIS point, where the operands have been produced
+        ev, sid = torch.cuda.Event(), torch.cuda.current_stream().cuda_stream
+        ev.record()
+    # dw only through its storage (see rows_sum_accum)
+    deferred_tn.firs.append((dy, x, lens, deferred_tn._desc(dw), ws, ws_n, B, T, C, lp, sid, ev))
+
+
 TN_MAX_GROUP = 16
 
 
@@ -1414,6 +1468,18 @@ class _DeferredTN:
         self.groups = {}
         self.copies = []
         self.rowsums = []  # (partial rows, descriptor of dgamma, descriptor of dbeta): rows_sum_accum
+        self.firs = []  # FSMN filter gradients: fir_dw_accum
+
+    def pending(self):
+        return bool(self.groups or self.copies or self.rowsums or self.firs)
+
+    def discard(self):
+        """Forget everything recorded (a capture that failed)."""
+        self.groups, self.copies, self.rowsums, self.firs = {}, [], [], []
+
+    def fir_keep(self):
+        """The tensors the recorded filter gradients read or use as workspace (``flush_early`` keeps them alive)."""
+        return [t for q in self.firs for t in (q[0], q[1], q[4])]
 
     def add(self, key, g, a, b, c, db, seed, keep):
         self.groups.setdefault(key, []).append((g, a, b, c, db, seed, keep))
@@ -1445,14 +1511,24 @@ class _DeferredTN:
         the tail of the captured step) over four streams was measured: 7.12 ms against 7.14 ms on one stream, same box
         (profiles/r04_runP_direct_grads_and_spread_flush_ab.log) -- the launches are bound by their fp32 atomics, not by
         idle CUs.  Removed."""
-        if not self.groups and not self.copies and not self.rowsums:
+        if not self.pending():
             return
         groups, self.groups = self.groups, {}
         copies, self.copies = self.copies, []
         rowsums, self.rowsums = self.rowsums, []
+        firs, self.firs = self.firs, []
         self._launch([probs[s:s + TN_MAX_GROUP] for probs in groups.values() for s in range(0, len(probs), TN_MAX_GROUP)])
         if rowsums:
             rows_sum_many([(src, self._rebuild(d0), self._rebuild(d1)) for src, d0, d1 in rowsums])
+        if firs:
+            # operands recorded on another stream (the predictors' branch): wait for the last point recorded there
+            here, last = torch.cuda.current_stream() if firs[0][0].is_cuda else None, {}
+            for q in firs:
+                if q[11] is not None and q[10] != here.cuda_stream:
+                    last[q[10]] = q[11]
+            for ev in last.values():
+                here.wait_event(ev)
+            fir_dw_many([q[:3] + (self._rebuild(q[3]),) + q[4:10] for q in firs])
         if copies:
             torch._foreach_copy_([self._rebuild(d) for d, _ in copies], [self._rebuild(s) for _, s in copies])
 

@@ -199,11 +199,12 @@ class _WgradOverlap:
         middle of backward): they then run beside the rest of the backward chain instead of after it."""
         from . import deferred_tn
 
-        if not self.enabled or not (deferred_tn.groups or deferred_tn.copies or deferred_tn.rowsums):
+        if not self.enabled or not deferred_tn.pending():
             return
         # operands were allocated on the main stream; flush() drops its references once the launches are issued
         keep = [k for probs in deferred_tn.groups.values() for q in probs for k in q[6] if k is not None]
         keep += [r[0] for r in deferred_tn.rowsums]
+        keep += deferred_tn.fir_keep()
         with self.side(*keep):
             deferred_tn.flush()
 
@@ -1454,6 +1455,25 @@ def lr_memory(aug, spk, emo, idx, cs, valid_lens, pos_enc, r, frames=None):
 # ================================================================================================
 # FSMN memory block
 # ================================================================================================
+def _fsmn_filter_grad(dy, x, w, lens, dw, B, T, C, K, lp):
+    """dw += the filter gradient of a memory block.  A leaf of the backward graph: when the step defers its weight gradients
+    (``deferred_tn.enabled``) the 41-tap problem is only recorded and leaves with every other recorded one at the next flush
+    (``fir_dw_accum``: two launches for all of them, no fork at the layer); otherwise it runs at once, on the
+    weight-gradient stream when the step overlaps them (partials + reduce are 41 us per layer, ten layers per step).
+    dw itself must NOT be in a keep-alive list: a second reference to the returned gradient makes AccumulateGrad CLONE it on
+    the main stream instead of adopting it -- before the other stream has written it.  The parameter's .grad keeps it alive."""
+    from . import deferred_tn, fir_dw_accum, fir_dw_many_entry_point
+
+    ws_n = int(lib().kantts_fsmn_dwconv_bwd_ws(B, T, C, K))
+    ws = torch.empty(max(ws_n, 1), device=dy.device, dtype=torch.float32)
+    if deferred_tn.enabled and K == 41 and fir_dw_many_entry_point():
+        fir_dw_accum(dy, x, lens, dw, ws, ws_n, B, T, C, lp)
+        return
+    with wgrad_overlap.side(dy, x, ws):
+        check(lib().kantts_fsmn_dwconv_bwd(ptr(dy, torch.float32), ptr(x), ptr(w), ptr(lens), None, ptr(dw), ptr(ws), ws_n,
+                                           B, T, C, K, lp, stream()), "fsmn_dwconv_bwd (dw)")
+
+
 class _FsmnMemory(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, res, lens, lp):
@@ -1475,18 +1495,9 @@ class _FsmnMemory(torch.autograd.Function):
         dy = _c(dy)
         dx = torch.empty_like(x)
         dw = gzeros_like(w)
-        ws_n = int(lib().kantts_fsmn_dwconv_bwd_ws(B, T, C, K))
-        ws = torch.empty(max(ws_n, 1), device=dy.device, dtype=torch.float32)
         check(lib().kantts_fsmn_dwconv_bwd(ptr(dy, torch.float32), ptr(x), ptr(w), ptr(lens), ptr(dx), None, None, 0,
                                            B, T, C, K, lp, stream()), "fsmn_dwconv_bwd (dx)")
-        # the filter gradient is a leaf: on the weight-gradient stream when the step overlaps them (partials + reduce are
-        # 41 us per layer, ten layers per step)
-        # (dw itself must NOT be in the keep-alive list: a second reference to the returned gradient makes AccumulateGrad
-        # CLONE it on the main stream instead of adopting it -- before the side stream has written it.  The parameter's
-        # .grad keeps it alive.)
-        with wgrad_overlap.side(dy, x, ws):
-            check(lib().kantts_fsmn_dwconv_bwd(ptr(dy, torch.float32), ptr(x), ptr(w), ptr(lens), None, ptr(dw), ptr(ws),
-                                               ws_n, B, T, C, K, lp, stream()), "fsmn_dwconv_bwd (dw)")
+        _fsmn_filter_grad(dy, x, w, lens, dw, B, T, C, K, lp)  # a leaf: beside the chain, or recorded for the next flush
         return dx, dw, (dy if has_res else None), None, None
 
 
@@ -1543,14 +1554,9 @@ class _FsmnMemoryDrop(torch.autograd.Function):
             rc = lib().kantts_fsmn_dwconv_bwd(ptr(dym), ptr(c), ptr(w), ptr(lens), ptr(dx), None, None, 0, B, T, C, K, lp,
                                               stream())
         check(rc, "fsmn_memory_drop_bwd")
-        # the filter gradient reads the masked dy the launch wrote beside dx: a leaf, on the weight-gradient stream when the
-        # step overlaps them (dw must NOT be in the keep-alive list: see _FsmnMemory.backward)
+        # the filter gradient reads the masked dy the launch wrote beside dx: a leaf (_fsmn_filter_grad)
         dw = gzeros_like(w)
-        ws_n = int(lib().kantts_fsmn_dwconv_bwd_ws(B, T, C, K))
-        ws = torch.empty(max(ws_n, 1), device=dy.device, dtype=torch.float32)
-        with wgrad_overlap.side(dym, c, ws):
-            check(lib().kantts_fsmn_dwconv_bwd(ptr(dym), ptr(c), ptr(w), ptr(lens), None, ptr(dw), ptr(ws), ws_n, B, T, C,
-                                               K, lp, stream()), "fsmn_dwconv_bwd (dw)")
+        _fsmn_filter_grad(dym, c, w, lens, dw, B, T, C, K, lp)
         # the residual's gradient is the UNMASKED dy
         d_res = dy if has_res and ctx.needs_input_grad[2] else None
         if d_res is not None and ctx.res_grad is not None:
@@ -1591,7 +1597,7 @@ class _FsmnMemoryDrop2(torch.autograd.Function):
     """_FsmnMemoryDrop for TWO memory blocks of one shape over the same lengths (the same layer of the pitch and of the
     energy predictor): kantts_fsmn_memory_drop_fwd_pair / _bwd_pair, one launch each way for both.  Seeds are handed in
     (drawn by the caller in the unpaired order); per problem the bits are those of its own _FsmnMemoryDrop node.  The
-    filter gradients stay one launch per problem on the weight-gradient stream."""
+    filter gradients are one problem each (_fsmn_filter_grad)."""
 
     @staticmethod
     def forward(ctx, lens, lp, cfgs, res_grads, ca, wa, ra, cb, wb, rb):
@@ -1627,12 +1633,8 @@ class _FsmnMemoryDrop2(torch.autograd.Function):
                                                      rng_ptr(dys[0].device), stream()), "fsmn_memory_drop_bwd_pair")
         out = []
         for i, (c, w, dy, dx, dym) in enumerate(zip(cs, ws, dys, dxs, dyms)):
-            dw = gzeros_like(w)  # (must NOT be in the keep-alive list: see _FsmnMemory.backward)
-            ws_n = int(lib().kantts_fsmn_dwconv_bwd_ws(B, T, C, K))
-            wsp = torch.empty(max(ws_n, 1), device=dy.device, dtype=torch.float32)
-            with wgrad_overlap.side(dym, c, wsp):
-                check(lib().kantts_fsmn_dwconv_bwd(ptr(dym), ptr(c), ptr(w), ptr(lens), None, ptr(dw), ptr(wsp), ws_n, B, T, C,
-                                                   K, lp, stream()), "fsmn_dwconv_bwd (dw)")
+            dw = gzeros_like(w)
+            _fsmn_filter_grad(dym, c, w, lens, dw, B, T, C, K, lp)
             d_res = dy if has_res[i] and ctx.needs_input_grad[6 + 3 * i] else None  # the UNMASKED dy
             if d_res is not None and ctx.res_grads[i] is not None:
                 ctx.res_grads[i].dres, d_res = d_res, None
