@@ -327,7 +327,8 @@ int kantts_teacher_plan(const kantts_plan_args* args, void* stream);
  *   uncovered); cs (B,N+1) int32 exclusive prefix sums; lens (B) int64 totals.  Bit-exact.
  * kantts_lr_gather_fwd: out[b,t, off:off+C] = x[b, idx[b,t], :] (0 when idx<0 or t >= valid_lens[b]);
  *   out rows have stride ldo (lets three regulators write one concatenated buffer).
- * kantts_lr_gather_bwd: deterministic segment sum over [cs[n], cs[n+1]). */
+ * kantts_lr_gather_bwd: deterministic segment sum over [cs[n], min(cs[n+1], Tp, valid_lens[b])); accumulate != 0: dx += it.
+ * valid_lens (B) int64, optional, any value >= 0: it is compared in 64 bits (2^31 or 2^32 + 3 mask nothing). */
 int kantts_lr_index(const int64_t* dur_int, const float* dur_float, int32_t* idx, float* pos, int32_t* cs,
                     int64_t* lens, int B, int N, int Tp, void* stream);
 int kantts_lr_gather_fwd(const float* x, const int32_t* idx, const int64_t* valid_lens, float* out, int B, int N,
@@ -379,7 +380,9 @@ int kantts_fsmn_dwconv_fwd_slots(const float* x, const float* w, const float* re
 int kantts_fsmn_dwconv_bwd(const float* dy, const float* x, const float* w, const int64_t* lens, float* dx,
                            float* dw_accum, float* workspace, long long ws_floats, int B, int T, int C, int K,
                            int left_pad, void* stream);
-/* floats of caller-owned workspace the backward needs (weight-gradient partials; 0 when none) */
+/* floats of caller-owned workspace the backward needs: B * ceil(T / 128) * C * 41 weight-gradient partials for K = 41, 0 for
+ * every other K.  A NULL workspace or ws_floats below that, with dw_accum given: KANTTS_E_WORKSPACE, nothing is launched;
+ * nothing behind ws_floats is ever written. */
 long long kantts_fsmn_dwconv_bwd_ws(int B, int T, int C, int K);
 /* The 41-tap filter gradient of up to KANTTS_FIR_DW_MAX memory blocks in two launches for all of them (the filter gradient
  * is a leaf of the backward graph: the host records the problems of a step and issues them together).  Per problem:

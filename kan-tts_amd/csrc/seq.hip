@@ -216,7 +216,7 @@ __global__ void lr_gather_kernel(const float* __restrict__ x, const int32_t* __r
   int t = (int)(bt % Tp), b = (int)(bt / Tp);
   int id = idx[bt];
   float v = 0.f;
-  if (id >= 0 && (!valid || t < (int)valid[b])) v = x[((long long)b * N + id) * C + c];
+  if (id >= 0 && (!valid || t < (int)min((long long)valid[b], (long long)Tp))) v = x[((long long)b * N + id) * C + c];
   out[bt * ldo + ooff + c] = v;
 }
 
@@ -232,7 +232,7 @@ __global__ void lr_gather_bwd_kernel(const float* __restrict__ dout, const int32
   int n = (int)(bn % N), b = (int)(bn / N);
   int s = cs[(long long)b * (N + 1) + n], e = cs[(long long)b * (N + 1) + n + 1];
   if (e > Tp) e = Tp;
-  if (valid && e > (int)valid[b]) e = (int)valid[b];
+  if (valid) e = (int)min((long long)e, (long long)valid[b]);  // 64-bit compare: a length of 2^31 or more masks nothing
   float acc = 0.f;
   for (int t = s; t < e; ++t) acc += dout[((long long)b * Tp + t) * ldo + ooff + c];
   if (accumulate)
@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256) void lr_memory_fwd_kernel(
   const long long bt = g / W4;
   const int t = (int)(bt % Tp), b = (int)(bt / Tp);
   const int id = idx[bt];
-  const bool live = id >= 0 && (!valid || t < (int)valid[b]);
+  const bool live = id >= 0 && (!valid || t < (int)min((long long)valid[b], (long long)Tp));
   const int l = t / r, j = t - l * r;
   float* mrow = mem + (bt / r) * (long long)(r * dt + ds + de);  // (b * L + l): Tp = L * r
   const long long tok = (long long)b * N + (live ? id : 0);
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256) void lr_memory_bwd_kernel(
   const int n = (int)(bn % N), b = (int)(bn / N);
   int s = cs[(long long)b * (N + 1) + n], e = cs[(long long)b * (N + 1) + n + 1];
   if (e > Tp) e = Tp;
-  if (valid && e > (int)valid[b]) e = (int)valid[b];
+  if (valid) e = (int)min((long long)e, (long long)valid[b]);  // 64-bit compare: a length of 2^31 or more masks nothing
   if (s < 0) s = 0;
   const float* base = dmem + (long long)b * (Tp / r) * ldm;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -342,8 +342,9 @@ def test_embedding_and_length_regulator_bit_exact():
     assert_close(go[1], co[1], 1e-5, what="embed scaled")
     for a, c in zip(gg, cg):
         assert_close(a, c, 1e-4, what="embed grad")
-    # bench-sized call (32 x 64 tokens, 512 columns): tiny tables through the LDS images, a 500-row table through the
-    # scatter form, an index tensor with every token on ONE row (maximal collisions)
+    # bench-sized call (32 x 64 tokens, 512 columns): every table goes through the backward kernel's 8-way accumulator cache
+    # (one thread per 32-row chunk, table and column) -- tiny tables stay in it, the 150- and 500-row tables evict on nearly
+    # every row, and an index tensor with every token on ONE row never leaves its first way (maximal collisions)
     ids2 = torch.stack([torch.randint(0, n, (32, 64), generator=g) for n in (150, 7, 500, 5)], -1)
     ids2[:, :, 3] = 2
     tabs2 = [_rand(n, 512, seed=20 + k, grad=True) for k, n in enumerate((150, 7, 500, 5))]
