@@ -766,12 +766,16 @@ int kantts_align_attn_bwd(const float* q, const float* k, const float* prior, co
  *   A_s: (M, klen_s) rows of bf16 (or fp32 when a_f32: rounded to bf16 once per tile), row stride lda.
  *   B_s: b_kn = 0: (N, klen_s) k-contiguous, row stride ldb (forward: the weight);
  *        b_kn = 1: (klen_s, N) n-contiguous, row stride ldb (input gradient through the same weight buffer).
- *   a_shift: conv tap -- row i reads token i + a_shift of its own sequence of T tokens, zero outside [0, T).
+ *   a_shift: conv tap -- row i reads token i + a_shift of its own sequence of T tokens, zero outside [0, T).  M need not be a
+ *            multiple of T, but A then holds every row of the last sequence: rows up to ceil(M / T) * T - 1 may be read.
  *   epilogue: v = (acc + bias[j] + bias2[j]) * alpha; relu; dropout(drop_p; element i*N + j of drop_seed + *seed_dev);
  *             v += res[i][j] (fp32); v = gate[i][j] > 0 ? v : 0 (ReLU backward on a saved activation); rowmask[i] -> 0;
  *             stored as bf16 (c_bf16) or fp32.
  *   a_drop_p > 0 (a_f32 only): A is an incoming gradient through an epilogue dropout of the forward pass; element
- *             (i, k) is multiplied by the keep-scale regenerated from (a_drop_seed + *seed_dev, i * a_drop_ld + k).
+ *             (i, k) is multiplied by the keep-scale regenerated from (a_drop_seed + *seed_dev, i * a_drop_ld + k); under a
+ *             tap shift i is the row that is READ (i + a_shift), the index the forward pass gave that element.
+ *   After the KANTTS_E_BADARG checks (nseg, negative M / N, c NULL) M == 0 or N == 0 returns KANTTS_OK before any other
+ *   check and writes nothing.
  */
 #define KANTTS_BGEMM_MAX_SEG 12
 typedef struct kantts_bgemm_seg {
@@ -849,7 +853,10 @@ int kantts_bgemm_nt_lnbwd(const kantts_bgemm_args* args, const kantts_lnbwd_args
  * Weight / bias gradients: A = gradient of the layer output (M, N), B = layer input (M, K), tokens m are the reduction
  * axis; fp32 atomics into a pre-zeroed gradient that may already be in the parameter's own layout (strides c_*).
  * A / B are bf16 or fp32 (a_f32 / b_f32); a_drop_* as above with the logical index m*N + n.  slices = 0 lets the
- * library choose the token split. */
+ * library choose the token split.  Operands given as fp32 are rounded to bf16 (ties to even) when staged, A after its
+ * keep-scale; db is the sum of that rounded, dropped A, and alpha applies to db as it does to c.  As for kantts_bgemm_nt, B
+ * holds every row of the last sequence when M is no multiple of T.  After the KANTTS_E_BADARG checks (negative M, N < 1,
+ * K < 1, ntaps < 1, nprob) M == 0 returns KANTTS_OK before any other check and writes nothing. */
 typedef struct kantts_bgemm_tn_args {
   const void* a;
   const void* b;
@@ -878,7 +885,8 @@ int kantts_bgemm_tn_grouped(const kantts_bgemm_tn_args* shape, int nprob, const 
 int kantts_cast_f32_bf16(const float* src, void* dst_bf16, long long n, void* stream);
 
 /* Conv1d weights (N, Cin, KT) fp32 at src + src_off -> tap-major (KT, N, Cin) bf16 at dst + dst_off, one table entry
- * per weight (table in device memory), one launch for all of them (kantts/models/sambert/__init__.py:115-127). */
+ * per weight (table in device memory), one launch for all of them (kantts/models/sambert/__init__.py:115-127).
+ * Element-wise accesses: N, Cin, KT and both offsets need no granularity or alignment beyond that of their element type. */
 typedef struct kantts_tapmajor_desc {
   int64_t src_off, dst_off;
   int32_t N, Cin, KT, pad_;

@@ -18,7 +18,8 @@
 // each), reduction tile 64, register-prefetched double-buffered LDS, one barrier per tile.  k-contiguous LDS images are
 // [row][64] bf16 with the 16-byte chunk index XORed by (row >> 1) & 7 (conflict-free 16- and 8-byte fragment reads);
 // n-contiguous images are [k][128 + 16] (8 consecutive k rows start 8 banks apart, as in gemm_fast.hip).
-// TN: 128 x 128 outputs, waves 2x2 with 64x64 each, token tile 32, atomics into the fp32 gradient.
+// TN: BN x BK outputs (64 x 128 by the rule; 128 x 128, 64 x 256 and 128 x 256 through kantts_launch_tuning), waves 2x2
+// with BN/2 x BK/2 each, token tile 64, atomics into the fp32 gradient.
 #include <stdlib.h>
 
 #include "common.h"

@@ -67,8 +67,9 @@ def _bf16_round(x):
     """fp32 array -> fp32 array holding the bf16-rounded values (round to nearest even, like v_cvt_pk_bf16_f32)."""
     u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
     r = ((u >> np.uint32(16)) & np.uint32(1)) + np.uint32(0x7FFF)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)  # a NaN stays a (quiet) NaN: the carry must not reach its exponent or sign
     with np.errstate(over="ignore"):
-        return ((u + r) & np.uint32(0xFFFF0000)).view(np.float32)
+        return np.where(nan, u | np.uint32(0x00400000), u + r).astype(np.uint32).__and__(np.uint32(0xFFFF0000)).view(np.float32)
 
 
 def _rd(ptr, n, bf16):
@@ -1700,6 +1701,8 @@ class EmulatedLib:
     # ------------------------------------------------------------------------------------ bf16 conv contractions
     def kantts_act_cast_bf16(self, src, gate, gate_bf16, dst, act, slope, n, stream):
         n = int(_val(n))
+        if n == 0:
+            return 0
         v = _arr(src, n).copy()
         sl = np.float32(_val(slope))
         if gate:

@@ -419,8 +419,8 @@ def test_layernorm_backward_as_the_epilogue_of_the_input_gradient(M, a_f32, with
 @pytest.mark.parametrize("tile", ["64", "128"])
 def test_weight_gradient_contraction_with_both_output_tiles_gpu(tile, monkeypatch):
     """bgemm_tn_kernel with the 64 x 128 and the 128 x 256 output tile (KANTTS_TN_TILE forces one; on its own the launcher
-    takes the large tile for M >= 4096 problems with enough tiles) against a float64 contraction of the bf16-rounded
-    operands: the decoder feed-forward shape, a ragged one, a 3-tap convolution gradient with a bias gradient."""
+    always takes the 64 x 128 tile, the larger ones are reached only when forced) against a float64 contraction of the
+    bf16-rounded operands: the decoder feed-forward shape, a ragged one, a 3-tap convolution gradient with a bias gradient."""
     import kantts._hip as hip
 
     monkeypatch.setenv("KANTTS_TN_TILE", tile)
