@@ -1098,6 +1098,18 @@ typedef struct kantts_pnca_attn_bwd_args {
   long long ws_floats;
 } kantts_pnca_attn_bwd_args;
 int kantts_pnca_attn_qkv_bwd(const kantts_pnca_attn_bwd_args* args, void* stream);
+/* The seam between two blocks of a stack's backward as one launch (csrc/pnca_block.hip: pnca_bwd_seam_kernel):
+ * kantts_pnca_attn_qkv_bwd(upper) followed by kantts_pnca_block_bwd(lower), where the lower block's dy IS the upper block's
+ * dx.  The row-local half reads of the block above nothing but the 32 dx rows its own workgroup has just produced, so the
+ * two halves run back to back on every tile without a launch boundary; both are the code of the separate launches and every
+ * value those write -- dqkv, dhkv, dx and the upper partial rows; dz, g1, d_ox, d_oh and the lower partial rows -- is written
+ * here bit for bit (dx too: the lower block's weight gradient and the caller read it).  lower->dy is not read.
+ * Requires lower->dy == upper->dx and lower->M == upper->B * upper->L (else KANTTS_E_BADARG) and everything the two entry
+ * points require of their own arguments, checked in that order -- upper first -- with the codes they return (C == 128,
+ * F == 1024, H == 8, band widths <= 16 unless device-resident, row pitches, 16-byte alignment: KANTTS_E_UNSUPPORTED; NULL
+ * operands: KANTTS_E_BADARG; either workspace short of kantts_pnca_block_bwd_ws_floats(M): KANTTS_E_WORKSPACE).  A refused
+ * call launches nothing.  M == 0: KANTTS_OK, nothing is launched. */
+int kantts_pnca_bwd_seam(const kantts_pnca_attn_bwd_args* upper, const kantts_pnca_block_bwd_args* lower, void* stream);
 
 /* For each of n problems: dst0[c] += sum_r src[r*cols + c] for c < split, dst1[c - split] += ... for c >= split (fixed
  * summation order) -- the partial rows of kantts_pnca_block_bwd / kantts_bgemm_nt_lnbwd, many of them in one launch. */

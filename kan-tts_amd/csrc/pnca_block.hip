@@ -48,10 +48,12 @@ static int pb_dbg_mask() {
 #define PB_DBG(bit) ((dbg & (bit)) != 0)
 #define PB_DBG_PARAM , const int dbg
 #define PB_DBG_ARG , pb_dbg_mask()
+#define PB_DBG_PASS , dbg
 #else
 #define PB_DBG(bit) false
 #define PB_DBG_PARAM
 #define PB_DBG_ARG
+#define PB_DBG_PASS
 #endif
 
 #define PB_THREADS 512
@@ -586,29 +588,73 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_block_fwd_kernel(const kantts
 // What crosses rows -- the attention backward, whose key gradients collect queries from neighbouring tiles -- stays a
 // launch of its own (csrc/attn.hip), followed by the QKV input gradient with the first LayerNorm's backward in its
 // epilogue (csrc/gemm_bf16.hip): a block's backward is 3 launches instead of 7.
-__global__ __launch_bounds__(PB_THREADS) void pnca_block_bwd_kernel(const kantts_pnca_block_bwd_args g, const int xcd_band PB_DBG_PARAM) {
-  __shared__ __attribute__((aligned(16))) __bf16 Xs[PB_BM * PB_XP];   // dropout_2(dy) tile, later dropout_fc(g1)
-  __shared__ __attribute__((aligned(16))) __bf16 Ts[PB_BM * PB_TP];   // gate tile -> dz tile
-  __shared__ __attribute__((aligned(16))) float St[512];
+// What the row-local half reads that does not depend on dy: the first four units of the W2^T ring, the gate tile (in flight
+// between pb_gate_load and pb_gate_store) and the LayerNorm operands of the thread's two tokens.  pnca_block_bwd_kernel
+// fetches them at its head; pnca_bwd_seam_kernel fetches them while the cross-row half of the block above still runs.
+struct PbRowPre {
+  u32x4 ring[4][8];
+  u32x4 gq[8];
+  float4 y1r[2];
+  float mu[2], rs[2];
+  bool rz[2];
+  float4 gm;
+};
+__device__ __forceinline__ void pb_ring_load1(const kantts_pnca_block_bwd_args& g, u32x4* w, int s) {
+  // rows s*256 + wave*32 + {0, 16} of W2^T, 4 k-blocks
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const __bf16* p = reinterpret_cast<const __bf16*>(g.wt2) + ((long long)(s * 16 + wave * 2) * 4) * 512 + lane * 8;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) w[j] = *reinterpret_cast<const u32x4*>(p + j * 512);
+}
+__device__ __forceinline__ void pb_gate_load(const kantts_pnca_block_bwd_args& g, int m0, u32x4* gq PB_DBG_PARAM) {
+  const __bf16* gp = reinterpret_cast<const __bf16*>(g.hid);
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    const int id = threadIdx.x + PB_THREADS * it;
+    const long long row = PB_DBG(16) ? 0ll : min((long long)m0 + (id >> 7), (long long)g.M - 1);
+    gq[it] = *reinterpret_cast<const u32x4*>(gp + row * PB_F + (id & 127) * 8);
+  }
+}
+__device__ __forceinline__ void pb_gate_store(__bf16* Ts, const u32x4* gq) {
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    const int id = threadIdx.x + PB_THREADS * it;
+    *reinterpret_cast<u32x4*>(&Ts[(id >> 7) * PB_TP + (id & 127) * 8]) = gq[it];
+  }
+}
+__device__ __forceinline__ void pb_rows_load(const kantts_pnca_block_bwd_args& g, int m0, PbRowPre& pre) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, kg = lane >> 4;
+  const int n0 = (wave & 3) * 32 + (wave >> 2) * 16 + kg * 4;
+  const float* dummy = reinterpret_cast<const float*>(g.wt2);
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    const long long m = min((long long)m0 + b * 16 + li, (long long)g.M - 1);
+    pre.y1r[b] = *reinterpret_cast<const float4*>(g.y1 + m * PB_C + n0);
+    pre.mu[b] = g.mean1[m];
+    pre.rs[b] = g.rstd1[m];
+    const uint8_t q = *(g.rowmask ? g.rowmask + m : reinterpret_cast<const uint8_t*>(dummy));
+    pre.rz[b] = g.rowmask && q != 0;
+  }
+  pre.gm = *reinterpret_cast<const float4*>(g.ln1_gamma + n0);
+}
+
+// The row-local half on tile `tile_id`.  SEAM = false: the stand-alone launch, everything from memory.  SEAM = true
+// (pnca_bwd_seam_kernel): dy is the fp32 tile DXs (32 x PB_QP) the cross-row half of the block above has just left in LDS --
+// the very values it stored as dx -- and `pre` is already loaded, the gate tile already in Ts.
+template <bool SEAM>
+__device__ __forceinline__ void pnca_block_bwd_body(const kantts_pnca_block_bwd_args& g, const int tile_id, __bf16* Xs,
+                                                    __bf16* Ts, float* St, const float* DXs, PbRowPre& pre PB_DBG_PARAM) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, kg = lane >> 4;
   const int M = g.M;
-  const int tile_id = pb_tile(xcd_band);
   const int m0 = tile_id * PB_BM;
   const uint64_t seed_off = g.seed_dev ? *g.seed_dev : 0ull;
-  const __bf16* __restrict__ wt2 = reinterpret_cast<const __bf16*>(g.wt2);  // W2^T (F x 128)
   const __bf16* __restrict__ wt1 = reinterpret_cast<const __bf16*>(g.wt1);  // W1^T (128 x F)
   const __bf16* __restrict__ wxt = reinterpret_cast<const __bf16*>(g.wfcxT);
   const __bf16* __restrict__ wht = reinterpret_cast<const __bf16*>(g.wfchT);
-  const float* dummy = reinterpret_cast<const float*>(g.wt2);
   const int nq = wave & 3, kh = wave >> 2;
   const int n0 = nq * 32 + kh * 16 + kg * 4;
 
-  u32x4 ring[4][8];
-  auto load1 = [&](u32x4* w, int s) {  // rows s*256 + wave*32 + {0, 16} of W2^T, 4 k-blocks
-    const __bf16* p = wt2 + ((long long)(s * 16 + wave * 2) * 4) * 512 + lane * 8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) w[j] = *reinterpret_cast<const u32x4*>(p + j * 512);
-  };
+  u32x4 (&ring)[4][8] = pre.ring;  // W2^T (F x 128) first: pb_ring_load1
   auto load2 = [&](u32x4* w, int u) {  // rows nq*32 + {0, 16} of W1^T, k-blocks kh*16 + u*4 + {0..3}
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
@@ -617,8 +663,10 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_block_bwd_kernel(const kantts
       for (int kk = 0; kk < 4; ++kk) w[a * 4 + kk] = *reinterpret_cast<const u32x4*>(p + kk * 512);
     }
   };
+  if (!SEAM) {
 #pragma unroll
-  for (int j = 0; j < 4; ++j) load1(ring[j], j);
+    for (int j = 0; j < 4; ++j) pb_ring_load1(g, ring[j], j);
+  }
 
   // ---- dy tile -> dropout_2 -> bf16 (masked rows and rows past M are zero)
   {
@@ -626,7 +674,7 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_block_bwd_kernel(const kantts
     const long long src = (long long)m0 + j;
     u32x4 v = {0u, 0u, 0u, 0u};
     if (src < M && !(g.rowmask && g.rowmask[src])) {
-      const float* p = g.dy + src * PB_C + ch * 8;
+      const float* p = SEAM ? DXs + j * PB_QP + ch * 8 : g.dy + src * PB_C + ch * 8;
       float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
       if (g.drop2_p > 0.f) {
         const uint64_t base = (uint64_t)src * (uint64_t)PB_C + (uint64_t)(ch * 8);
@@ -645,37 +693,24 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_block_bwd_kernel(const kantts
     *reinterpret_cast<u32x4*>(&Xs[j * PB_XP + ch * 8]) = v;
   }
   // ---- gate (the saved hidden activation) into the cells the gradient tile will overwrite
-  {
-    const __bf16* gp = reinterpret_cast<const __bf16*>(g.hid);
-    u32x4 gq[8];
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int id = tid + PB_THREADS * it;
-      const long long row = PB_DBG(16) ? 0ll : min((long long)m0 + (id >> 7), (long long)M - 1);
-      gq[it] = *reinterpret_cast<const u32x4*>(gp + row * PB_F + (id & 127) * 8);
-    }
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int id = tid + PB_THREADS * it;
-      *reinterpret_cast<u32x4*>(&Ts[(id >> 7) * PB_TP + (id & 127) * 8]) = gq[it];
-    }
+  if (!SEAM) {
+    pb_gate_load(g, m0, pre.gq PB_DBG_PASS);
+    pb_gate_store(Ts, pre.gq);
   }
   // what the LayerNorm backward needs from memory, requested before the weight stream is consumed
-  float4 y1r[2], dyr[2];
-  float mu[2], rs[2];
-  bool rz[2], live[2];
+  if (!SEAM) pb_rows_load(g, m0, pre);
+  float4 dyr[2];
+  bool live[2];
 #pragma unroll
   for (int b = 0; b < 2; ++b) {
     const long long m = min((long long)m0 + b * 16 + li, (long long)M - 1);
     live[b] = m0 + b * 16 + li < M;
-    y1r[b] = *reinterpret_cast<const float4*>(g.y1 + m * PB_C + n0);
-    dyr[b] = *reinterpret_cast<const float4*>(g.dy + m * PB_C + n0);
-    mu[b] = g.mean1[m];
-    rs[b] = g.rstd1[m];
-    const uint8_t q = *(g.rowmask ? g.rowmask + m : reinterpret_cast<const uint8_t*>(dummy));
-    rz[b] = g.rowmask && q != 0;
+    dyr[b] = *reinterpret_cast<const float4*>(SEAM ? DXs + (b * 16 + li) * PB_QP + n0 : g.dy + m * PB_C + n0);
   }
-  const float4 gm = *reinterpret_cast<const float4*>(g.ln1_gamma + n0);
+  const float4 (&y1r)[2] = pre.y1r;
+  const float (&mu)[2] = pre.mu, (&rs)[2] = pre.rs;
+  const bool (&rz)[2] = pre.rz;
+  const float4 gm = pre.gm;
   __syncthreads();  // dy tile and gate tile complete
 
   // ---- phase 1: dz^T[f][tok] = W2^T[f][:] . dy_d[tok][:], gated by the saved activation
@@ -902,6 +937,14 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_block_bwd_kernel(const kantts
   }
 }
 
+__global__ __launch_bounds__(PB_THREADS) void pnca_block_bwd_kernel(const kantts_pnca_block_bwd_args g, const int xcd_band PB_DBG_PARAM) {
+  __shared__ __attribute__((aligned(16))) __bf16 Xs[PB_BM * PB_XP];   // dropout_2(dy) tile, later dropout_fc(g1)
+  __shared__ __attribute__((aligned(16))) __bf16 Ts[PB_BM * PB_TP];   // gate tile -> dz tile
+  __shared__ __attribute__((aligned(16))) float St[512];
+  PbRowPre pre;
+  pnca_block_bwd_body<false>(g, pb_tile(xcd_band), Xs, Ts, St, nullptr, pre PB_DBG_PASS);
+}
+
 // ================================================================================================================
 // The CROSS-ROW half of the block's backward as one launch: both attention bands' backward, the input gradient of the QKV
 // projection and the backward of the block's first LayerNorm --
@@ -919,14 +962,25 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_block_bwd_kernel(const kantts
 #define PB2_QROWS (PB_BM + PB_HX + PB_HH)   // 64 query rows: 16 in front (memory band), 16 behind (decoder band)
 #define PB2_GP (3 * PB_C + 16)              // bf16 pitch of the [dq | dk | dv] tile: 800 B = 32 mod 64
 
-__global__ __launch_bounds__(PB_THREADS) void pnca_attn_qkv_bwd_kernel(const kantts_pnca_attn_bwd_args g, const int xcd_band PB_DBG_PARAM) {
-  // R: stage 1 = [k|v rows m0-16 .. m0+31 | memory k|v rows m0 .. m0+47]; stage 2 = [q rows m0-16 .. m0+47 | dOx rows m0 ..
-  // m0+47 | dOh rows m0-16 .. m0+31]; then the bf16 gradient tile
-  __shared__ __attribute__((aligned(16))) float R[2 * (PB_BM + PB_HX) * PB_KP];
-  __shared__ __attribute__((aligned(16))) float DQs[PB_BM * PB_QP];
-  __shared__ __attribute__((aligned(16))) float Lx[(PB_BM + PB_HX) * 8], Dx[(PB_BM + PB_HX) * 8];  // rows m0 .. m0+47
-  __shared__ __attribute__((aligned(16))) float Lh[(PB_BM + PB_HX) * 8], Dh[(PB_BM + PB_HX) * 8];  // rows m0-16 .. m0+31
-  __shared__ __attribute__((aligned(16))) float St[512];
+#define PB2_R_FLOATS (2 * (PB_BM + PB_HX) * PB_KP)   // 99 840 B
+#define PB2_LD_FLOATS ((PB_BM + PB_HX) * 8)          // one of Lx / Dx / Lh / Dh
+
+// Hooks of the cross-row body: the stand-alone launch has none.
+struct PbNoSeam {
+  __device__ __forceinline__ void stage2_done() {}
+  __device__ __forceinline__ void tile_consumed() {}
+  __device__ __forceinline__ void dx_rows(int, int, const float*) {}
+};
+
+// R: stage 1 = [k|v rows m0-16 .. m0+31 | memory k|v rows m0 .. m0+47]; stage 2 = [q rows m0-16 .. m0+47 | dOx rows m0 ..
+// m0+47 | dOh rows m0-16 .. m0+31]; then the bf16 gradient tile (the first 32 * PB2_GP * 2 = 25 600 bytes).
+// Lx / Dx: rows m0 .. m0+47; Lh / Dh: rows m0-16 .. m0+31.
+// seam.stage2_done() runs once the last barrier of stage 2 is passed (R behind the gradient tile and DQs are dead from there
+// on), seam.tile_consumed() when the thread has issued its last read of the gradient tile, seam.dx_rows(row, n0, o) with
+// the four dx values the thread stores at (m0 + row, n0 .. n0+3).
+template <class Seam>
+__device__ __forceinline__ void pnca_attn_qkv_bwd_body(const kantts_pnca_attn_bwd_args& g, const int tile_id, float* R, float* DQs,
+                                                       float* Lx, float* Dx, float* Lh, float* Dh, float* St, Seam& seam PB_DBG_PARAM) {
   float* KVs = R;
   float* HKs = R + (PB_BM + PB_HX) * PB_KP;
   float* Qs = R;                                   // (64, PB_QP)
@@ -938,7 +992,6 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_attn_qkv_bwd_kernel(const kan
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, kg = lane >> 4;
   const int L = g.L, H = PB_C / PB_DH;
   const long long M = (long long)g.B * L;
-  const int tile_id = pb_tile(xcd_band);
   const int m0 = tile_id * PB_BM;
   const uint64_t seed_off = g.seed_dev ? *g.seed_dev : 0ull;
   const int bw_x = g.bw_dev ? *g.bw_dev : g.bw_x, bw_h = g.bw_dev ? *g.bw_dev : g.bw_h;
@@ -1152,6 +1205,7 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_attn_qkv_bwd_kernel(const kan
   float dqs[PB_DH];
   pb_lds16(&DQs[row * PB_QP + head * PB_DH], dqs);  // (summed query gradient of (row, head); only the memory-stream threads use it)
   __syncthreads();  // every thread is done with the stage-2 operands: the region becomes the bf16 gradient tile
+  seam.stage2_done();
   {
     // [dq | dk | dv] of the tile: fp32 to memory (the weight gradient of the projection reads it), bf16 to LDS
     auto emit = [&](const float (&v)[PB_DH], int col) {
@@ -1186,6 +1240,7 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_attn_qkv_bwd_kernel(const kan
         acc[b2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16((const bf16x8&)wf[kk2], (const bf16x8&)v, acc[b2], 0, 0, 0);
       }
     }
+    seam.tile_consumed();
 #pragma unroll
     for (int b2 = 0; b2 < 2; ++b2) {  // the chain hands the normalised rows' gradient over in bf16
       const unsigned p01 = pb_pack2(acc[b2][0], acc[b2][1]), p23 = pb_pack2(acc[b2][2], acc[b2][3]);
@@ -1243,6 +1298,7 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_attn_qkv_bwd_kernel(const kan
       }
       const long long mm = (long long)m0 + b2 * 16 + li;
       if (live[b2]) *reinterpret_cast<f32x4*>(g.dx + mm * PB_C + n0) = (f32x4){o[0], o[1], o[2], o[3]};
+      seam.dx_rows(b2 * 16 + li, n0, o);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1258,6 +1314,85 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_attn_qkv_bwd_kernel(const kan
       *reinterpret_cast<f32x4*>(part + PB_C + n0) = (f32x4){pb[0], pb[1], pb[2], pb[3]};
     }
   }
+}
+
+__global__ __launch_bounds__(PB_THREADS) void pnca_attn_qkv_bwd_kernel(const kantts_pnca_attn_bwd_args g, const int xcd_band PB_DBG_PARAM) {
+  __shared__ __attribute__((aligned(16))) float R[PB2_R_FLOATS];
+  __shared__ __attribute__((aligned(16))) float DQs[PB_BM * PB_QP];
+  __shared__ __attribute__((aligned(16))) float Lx[PB2_LD_FLOATS], Dx[PB2_LD_FLOATS];
+  __shared__ __attribute__((aligned(16))) float Lh[PB2_LD_FLOATS], Dh[PB2_LD_FLOATS];
+  __shared__ __attribute__((aligned(16))) float St[512];
+  PbNoSeam seam;
+  pnca_attn_qkv_bwd_body(g, pb_tile(xcd_band), R, DQs, Lx, Dx, Lh, Dh, St, seam PB_DBG_PASS);
+}
+
+// ================================================================================================================
+// The SEAM between two blocks of the decoder's backward as one launch: the cross-row half of block i, then the row-local half
+// of block i-1 on the same 32 rows.  The row-local half reads nothing of block i but its dy = block i's dx, and of that only
+// the tile's own rows, which this workgroup has just produced: no other workgroup is waited for, and the boundary between
+// the two launches (a drained chip, a launch gap, a cold prologue) goes away.  Both halves are the bodies above: every value
+// the two launches write is written here, bit for bit -- dx included (dW2 of block i-1 and autograd read it).
+//
+// LDS (one region, 134 144 bytes, one workgroup per CU as before):
+//   [0, 99 840)          R of the cross-row half; from the end of stage 2 only its first 25 600 bytes are live (the gradient
+//                        tile), and the row-local half's gate / dz tile Ts (66 560 bytes) sits behind them at 25 600
+//   [99 840, 116 736)    DQs; dead from the end of stage 2: the fp32 dx tile DXs (32 x PB_QP), the row-local half's dy
+//   [116 736, 122 880)   Lx, Dx, Lh, Dh
+//   [122 880, 124 928)   St, the row statistics exchange of both LayerNorm backward epilogues (barriers in between)
+//   [124 928, 134 144)   Xs of the row-local half
+// The row-local half's loads that do not wait for dx are issued inside the cross-row half: the gate tile at the end of stage
+// 2 (stored to Ts once the contraction with W_qkv^T has consumed the weight registers), then the first four units of the
+// W2^T ring and the LayerNorm operands, in flight across the cross-row half's LayerNorm epilogue.
+#define PB3_TS_OFF (PB_BM * PB2_GP * 2)
+#define PB3_DQ_OFF (PB2_R_FLOATS * 4)
+#define PB3_LD_OFF (PB3_DQ_OFF + PB_BM * PB_QP * 4)
+#define PB3_ST_OFF (PB3_LD_OFF + 4 * PB2_LD_FLOATS * 4)
+#define PB3_XS_OFF (PB3_ST_OFF + 512 * 4)
+#define PB3_LDS_BYTES (PB3_XS_OFF + PB_BM * PB_XP * 2)
+static_assert(PB3_TS_OFF + PB_BM * PB_TP * 2 <= PB3_DQ_OFF, "the gate tile fits behind the gradient tile");
+static_assert(PB3_TS_OFF % 16 == 0 && PB3_DQ_OFF % 16 == 0 && PB3_LD_OFF % 16 == 0 && PB3_XS_OFF % 16 == 0, "16-byte regions");
+static_assert(PB3_LDS_BYTES <= 160 * 1024, "LDS of one CU");
+
+struct PbSeam {
+  const kantts_pnca_block_bwd_args& lo;
+  const int m0;
+  __bf16* Ts;
+  float* DXs;
+  PbRowPre& pre;
+#ifdef PB_DEBUG
+  const int dbg;
+#endif
+  __device__ __forceinline__ void stage2_done() { pb_gate_load(lo, m0, pre.gq PB_DBG_PASS); }
+  __device__ __forceinline__ void tile_consumed() {
+    pb_gate_store(Ts, pre.gq);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pb_ring_load1(lo, pre.ring[j], j);
+    pb_rows_load(lo, m0, pre);
+  }
+  __device__ __forceinline__ void dx_rows(int row, int n0, const float* o) {
+    *reinterpret_cast<f32x4*>(&DXs[row * PB_QP + n0]) = (f32x4){o[0], o[1], o[2], o[3]};
+  }
+};
+
+__global__ __launch_bounds__(PB_THREADS) void pnca_bwd_seam_kernel(const kantts_pnca_attn_bwd_args up, const kantts_pnca_block_bwd_args lo,
+                                                                   const int xcd_band PB_DBG_PARAM) {
+  __shared__ __attribute__((aligned(16))) unsigned char S[PB3_LDS_BYTES];
+  float* R = reinterpret_cast<float*>(S);
+  float* DQs = reinterpret_cast<float*>(S + PB3_DQ_OFF);
+  float* Ld = reinterpret_cast<float*>(S + PB3_LD_OFF);
+  float* St = reinterpret_cast<float*>(S + PB3_ST_OFF);
+  __bf16* Ts = reinterpret_cast<__bf16*>(S + PB3_TS_OFF);
+  __bf16* Xs = reinterpret_cast<__bf16*>(S + PB3_XS_OFF);
+  const int tile_id = pb_tile(xcd_band);
+  PbRowPre pre;
+#ifdef PB_DEBUG
+  PbSeam seam{lo, tile_id * PB_BM, Ts, DQs, pre, dbg};
+#else
+  PbSeam seam{lo, tile_id * PB_BM, Ts, DQs, pre};
+#endif
+  pnca_attn_qkv_bwd_body(up, tile_id, R, DQs, Ld, Ld + PB2_LD_FLOATS, Ld + 2 * PB2_LD_FLOATS, Ld + 3 * PB2_LD_FLOATS, St, seam PB_DBG_PASS);
+  __syncthreads();  // the dx tile is complete; every wave is done with the gradient tile and the cross-row half's St
+  pnca_block_bwd_body<true>(lo, tile_id, Xs, Ts, St, DQs, pre PB_DBG_PASS);
 }
 
 static bool pb_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -1287,9 +1422,8 @@ extern "C" long long kantts_pnca_block_bwd_ws_floats(int M) {
   return (long long)kantts_cdiv(M > 0 ? M : 1, PB_BM) * (2 * PB_C);
 }
 
-extern "C" int kantts_pnca_block_bwd(const kantts_pnca_block_bwd_args* gp, void* stream) {
-  if (!gp) return KANTTS_E_BADARG;
-  const kantts_pnca_block_bwd_args& g = *gp;
+// What kantts_pnca_block_bwd requires of its arguments (KANTTS_OK or the code it returns); kantts_pnca_bwd_seam asks the same.
+static int pb_check_block_bwd(const kantts_pnca_block_bwd_args& g) {
   if (!g.dy || !g.hid || !g.y1 || !g.mean1 || !g.rstd1 || !g.ln1_gamma || !g.wt2 || !g.wt1 || !g.wfcxT || !g.wfchT || !g.dz ||
       !g.g1 || !g.d_ox || !g.d_oh || g.M < 0)
     return KANTTS_E_BADARG;
@@ -1298,6 +1432,13 @@ extern "C" int kantts_pnca_block_bwd(const kantts_pnca_block_bwd_args* gp, void*
   const void* al[] = {g.dy, g.hid, g.y1, g.ln1_gamma, g.wt2, g.wt1, g.wfcxT, g.wfchT, g.dz, g.g1, g.d_ox, g.d_oh, g.ws};
   for (const void* p : al)
     if (!pb_aligned16(p)) return KANTTS_E_UNSUPPORTED;
+  return KANTTS_OK;
+}
+
+extern "C" int kantts_pnca_block_bwd(const kantts_pnca_block_bwd_args* gp, void* stream) {
+  if (!gp) return KANTTS_E_BADARG;
+  const kantts_pnca_block_bwd_args& g = *gp;
+  if (const int rc = pb_check_block_bwd(g)) return rc;
   if (g.M == 0) return KANTTS_OK;
   hipLaunchKernelGGL(pnca_block_bwd_kernel, dim3(kantts_cdiv(g.M, PB_BM)), dim3(PB_THREADS), 0, (hipStream_t)stream, g, pb_xcd_band() PB_DBG_ARG);
   KANTTS_CHECK_LAUNCH();
@@ -1339,9 +1480,7 @@ extern "C" int kantts_rows_sum_many(const kantts_rowsum_args* gp, void* stream) 
   KANTTS_CHECK_LAUNCH();
 }
 
-extern "C" int kantts_pnca_attn_qkv_bwd(const kantts_pnca_attn_bwd_args* gp, void* stream) {
-  if (!gp) return KANTTS_E_BADARG;
-  const kantts_pnca_attn_bwd_args& g = *gp;
+static int pb_check_attn_bwd(const kantts_pnca_attn_bwd_args& g) {
   if (!g.qkv || !g.hkv || !g.ox || !g.oh || !g.d_ox || !g.d_oh || !g.lse_x || !g.lse_h || !g.wqkvT || !g.x || !g.mean0 ||
       !g.rstd0 || !g.ln0_gamma || !g.dhkv || !g.dx || !g.ws || g.B < 0 || g.L < 0)
     return KANTTS_E_BADARG;
@@ -1353,7 +1492,27 @@ extern "C" int kantts_pnca_attn_qkv_bwd(const kantts_pnca_attn_bwd_args* gp, voi
   const void* al[] = {g.qkv, g.hkv, g.ox, g.oh, g.d_ox, g.d_oh, g.wqkvT, g.x, g.dres, g.ln0_gamma, g.dqkv, g.dhkv, g.dx, g.ws};
   for (const void* p : al)
     if (p && !pb_aligned16(p)) return KANTTS_E_UNSUPPORTED;
+  return KANTTS_OK;
+}
+
+extern "C" int kantts_pnca_attn_qkv_bwd(const kantts_pnca_attn_bwd_args* gp, void* stream) {
+  if (!gp) return KANTTS_E_BADARG;
+  const kantts_pnca_attn_bwd_args& g = *gp;
+  if (const int rc = pb_check_attn_bwd(g)) return rc;
+  const long long M = (long long)g.B * g.L;
   if (M == 0) return KANTTS_OK;
   hipLaunchKernelGGL(pnca_attn_qkv_bwd_kernel, dim3(kantts_cdiv(M, PB_BM)), dim3(PB_THREADS), 0, (hipStream_t)stream, g, pb_xcd_band() PB_DBG_ARG);
+  KANTTS_CHECK_LAUNCH();
+}
+
+extern "C" int kantts_pnca_bwd_seam(const kantts_pnca_attn_bwd_args* up, const kantts_pnca_block_bwd_args* lo, void* stream) {
+  if (!up || !lo) return KANTTS_E_BADARG;
+  if (const int rc = pb_check_attn_bwd(*up)) return rc;
+  if (const int rc = pb_check_block_bwd(*lo)) return rc;
+  const long long M = (long long)up->B * up->L;
+  if (lo->dy != up->dx || (long long)lo->M != M) return KANTTS_E_BADARG;
+  if (M == 0) return KANTTS_OK;
+  hipLaunchKernelGGL(pnca_bwd_seam_kernel, dim3(kantts_cdiv(M, PB_BM)), dim3(PB_THREADS), 0, (hipStream_t)stream, *up, *lo,
+                     pb_xcd_band() PB_DBG_ARG);
   KANTTS_CHECK_LAUNCH();
 }

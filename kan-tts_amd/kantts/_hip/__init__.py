@@ -520,6 +520,8 @@ def lib():
         L.kantts_rows_sum_many.argtypes = [POINTER(RowSumArgs), c_void_p]
         L.kantts_teacher_plan.argtypes = [POINTER(PlanArgs), c_void_p]
         L.kantts_pnca_attn_qkv_bwd.argtypes = [POINTER(PncaAttnBwdArgs), c_void_p]
+        if hasattr(L, "kantts_pnca_bwd_seam"):  # pnca_bwd_seam_entry_point(): a library built before it still loads
+            L.kantts_pnca_bwd_seam.argtypes = [POINTER(PncaAttnBwdArgs), POINTER(PncaBlockBwdArgs), c_void_p]
         L.kantts_copy_roof.argtypes = [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p]
         L.kantts_launch_tuning.argtypes = [c_int, c_int, c_int]
         L.kantts_pnca_decode_run.argtypes = [POINTER(DecodeArgs), c_void_p]
@@ -664,6 +666,7 @@ EXPORTED_SYMBOLS = [
     *CORPUS_PRIOR_SYMBOLS,
     *SYBERT_SYMBOLS,
     "kantts_fsmn_dw41_many",
+    "kantts_pnca_bwd_seam",
 ]
 
 
@@ -1114,6 +1117,25 @@ def pnca_block_bwd(dy, hid, y1, mean1, rstd1, gamma1, rowmask, wt2, wt1, wfcxT, 
     """The row-local half of a PNCA block's backward in one launch (csrc/pnca_block.hip; kantts_pnca_block_bwd in the
     header): feed-forward pair backward, LayerNorm backward + residual, input gradient of the output projection.  Returns the
     (workgroups, 256) partial rows of [dgamma | dbeta] of the LayerNorm: ``rows_sum_accum`` adds them into the gradients."""
+    g, ws = _pnca_block_bwd_args(dy, hid, y1, mean1, rstd1, gamma1, rowmask, wt2, wt1, wfcxT, wfchT, alpha1, drop2_p, drop2_seed,
+                                 fc_p, fc_seed, dz, g1, d_ox, d_oh)
+    if _profile is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    check(lib().kantts_pnca_block_bwd(ctypes.byref(g), stream()), "pnca_block_bwd")
+    if _profile is not None:
+        e1.record()
+        M = int(dy.shape[0])
+        flops = 4.0 * M * 128 * 1024 + 4.0 * M * 128 * 128
+        nbytes = M * (128 * 4 * 2 + 1024 * 2 * 2 + 128 * 4 * 2 + 2 * 128 * 4) + 2 * (2 * 128 * 1024 + 2 * 128 * 128)
+        _profile.append((e0, e1, flops))
+        _profile_families.append(("pnca_block_bwd", e0, e1, flops, float(nbytes)))
+    return ws
+
+
+def _pnca_block_bwd_args(dy, hid, y1, mean1, rstd1, gamma1, rowmask, wt2, wt1, wfcxT, wfchT, alpha1, drop2_p, drop2_seed, fc_p,
+                         fc_seed, dz, g1, d_ox, d_oh):
+    """(kantts_pnca_block_bwd_args, the workspace of partial rows it names) for pnca_block_bwd / pnca_bwd_seam."""
     g = PncaBlockBwdArgs()
     g.dy, g.hid, g.y1 = ptr(dy, torch.float32), ptr(hid, torch.bfloat16), ptr(y1, torch.float32)
     g.mean1, g.rstd1, g.ln1_gamma = ptr(mean1, torch.float32), ptr(rstd1, torch.float32), ptr(gamma1, torch.float32)
@@ -1127,18 +1149,7 @@ def pnca_block_bwd(dy, hid, y1, mean1, rstd1, gamma1, rowmask, wt2, wt1, wfcxT, 
     g.d_ox, g.d_oh = ptr(d_ox, torch.float32), ptr(d_oh, torch.float32)
     ws = torch.empty(((int(dy.shape[0]) + 31) // 32, 256), device=dy.device, dtype=torch.float32)
     g.ws, g.ws_floats = ptr(ws, torch.float32), ws.numel()
-    if _profile is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib().kantts_pnca_block_bwd(ctypes.byref(g), stream()), "pnca_block_bwd")
-    if _profile is not None:
-        e1.record()
-        M = int(dy.shape[0])
-        flops = 4.0 * M * 128 * 1024 + 4.0 * M * 128 * 128
-        nbytes = M * (128 * 4 * 2 + 1024 * 2 * 2 + 128 * 4 * 2 + 2 * 128 * 4) + 2 * (2 * 128 * 1024 + 2 * 128 * 128)
-        _profile.append((e0, e1, flops))
-        _profile_families.append(("pnca_block_bwd", e0, e1, flops, float(nbytes)))
-    return ws
+    return g, ws
 
 
 def teacher_plan(in_lens, out_lens, dur, mel, pos, inv_ts, Tp, max_len, r):
@@ -1350,6 +1361,28 @@ def pnca_attn_qkv_bwd(qkv, hkv, ldh, ox, oh, d_ox, d_oh, lse_x, lse_h, B, L, *, 
     """The cross-row half of a PNCA block's backward in one launch (csrc/pnca_block.hip; kantts_pnca_attn_qkv_bwd in the
     header): both attention bands' backward, the QKV projection's input gradient and the first LayerNorm's backward.
     Returns the partial rows of [dgamma0 | dbeta0] (``rows_sum_accum``), or None when the library declines (band above 16)."""
+    g, ws = _pnca_attn_bwd_args(qkv, hkv, ldh, ox, oh, d_ox, d_oh, lse_x, lse_h, B, L, lens, bw_dev, bw_x, bw_h, att_p, seed_x,
+                                seed_h, wqkvT, x, mean0, rstd0, gamma0, dres, zero_rows, dqkv, dhkv, dx)
+    M = int(B) * int(L)
+    if _profile is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    rc = lib().kantts_pnca_attn_qkv_bwd(ctypes.byref(g), stream())
+    if rc == E_UNSUPPORTED:
+        return None
+    check(rc, "pnca_attn_qkv_bwd")
+    if _profile is not None:
+        e1.record()
+        flops = 2.0 * M * 384 * 128 + 2.0 * 8.0 * B * L * L * 128  # projection input gradient + dense-count attention backward
+        nbytes = M * (384 * 4 * 2 + 256 * 4 * 2 + 4 * 128 * 4 + 128 * 4 * 3) + 2 * 384 * 128
+        _profile.append((e0, e1, flops))
+        _profile_families.append(("pnca_attn_qkv_bwd", e0, e1, flops, float(nbytes)))
+    return ws
+
+
+def _pnca_attn_bwd_args(qkv, hkv, ldh, ox, oh, d_ox, d_oh, lse_x, lse_h, B, L, lens, bw_dev, bw_x, bw_h, att_p, seed_x, seed_h,
+                        wqkvT, x, mean0, rstd0, gamma0, dres, zero_rows, dqkv, dhkv, dx):
+    """(kantts_pnca_attn_bwd_args, the workspace of partial rows it names) for pnca_attn_qkv_bwd / pnca_bwd_seam."""
     g = PncaAttnBwdArgs()
     g.qkv, g.hkv, g.ldh = ptr(qkv, torch.float32), ptr(hkv, torch.float32), int(ldh)
     g.ox, g.oh, g.d_ox, g.d_oh = (ptr(t, torch.float32) for t in (ox, oh, d_ox, d_oh))
@@ -1365,20 +1398,44 @@ def pnca_attn_qkv_bwd(qkv, hkv, ldh, ox, oh, d_ox, d_oh, lse_x, lse_h, B, L, *, 
     M = int(B) * int(L)
     ws = torch.empty(((M + 31) // 32, 256), device=qkv.device, dtype=torch.float32)
     g.ws, g.ws_floats = ptr(ws, torch.float32), ws.numel()
+    return g, ws
+
+
+def pnca_bwd_seam_entry_point():
+    """True when the loaded library has the seam launch (the numpy model of the C ABI and older builds do not)."""
+    return hasattr(lib(), "kantts_pnca_bwd_seam")
+
+
+def pnca_bwd_seam(upper, lower):
+    """The cross-row half of a PNCA block's backward and the row-local half of the block below it in one launch
+    (csrc/pnca_block.hip; kantts_pnca_bwd_seam in the header).  ``upper``: the positional and keyword arguments of
+    pnca_attn_qkv_bwd as (args, kwargs); ``lower``: those of pnca_block_bwd, whose ``dy`` must be the upper ``dx``.  Returns
+    (upper partial rows, lower partial rows), the two tensors the separate calls return, or None when the library declines
+    (band above 16); nothing has been launched then."""
+    ua, uk = upper
+    la, lk = lower
+    gu, ws_u = _pnca_attn_bwd_args(*ua, *(uk[k] for k in ("lens", "bw_dev", "bw_x", "bw_h", "att_p", "seed_x", "seed_h", "wqkvT",
+                                                          "x", "mean0", "rstd0", "gamma0", "dres", "zero_rows", "dqkv", "dhkv",
+                                                          "dx")))
+    gl, ws_l = _pnca_block_bwd_args(*la, *(lk[k] for k in ("alpha1", "drop2_p", "drop2_seed", "fc_p", "fc_seed", "dz", "g1",
+                                                           "d_ox", "d_oh")))
     if _profile is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    rc = lib().kantts_pnca_attn_qkv_bwd(ctypes.byref(g), stream())
+    rc = lib().kantts_pnca_bwd_seam(ctypes.byref(gu), ctypes.byref(gl), stream())
     if rc == E_UNSUPPORTED:
         return None
-    check(rc, "pnca_attn_qkv_bwd")
+    check(rc, "pnca_bwd_seam")
     if _profile is not None:
         e1.record()
-        flops = 2.0 * M * 384 * 128 + 2.0 * 8.0 * B * L * L * 128  # projection input gradient + dense-count attention backward
-        nbytes = M * (384 * 4 * 2 + 256 * 4 * 2 + 4 * 128 * 4 + 128 * 4 * 3) + 2 * 384 * 128
+        B, L = int(ua[9]), int(ua[10])
+        M = B * L
+        flops = 2.0 * M * 384 * 128 + 2.0 * 8.0 * B * L * L * 128 + 4.0 * M * 128 * 1024 + 4.0 * M * 128 * 128
+        nbytes = M * (384 * 4 * 2 + 256 * 4 * 2 + 4 * 128 * 4 + 128 * 4 * 3) + 2 * 384 * 128 + \
+            M * (128 * 4 + 1024 * 2 * 2 + 128 * 4 * 2 + 2 * 128 * 4) + 2 * (2 * 128 * 1024 + 2 * 128 * 128)
         _profile.append((e0, e1, flops))
-        _profile_families.append(("pnca_attn_qkv_bwd", e0, e1, flops, float(nbytes)))
-    return ws
+        _profile_families.append(("pnca_bwd_seam", e0, e1, flops, float(nbytes)))
+    return ws_u, ws_l
 
 
 def rows_sum_many(problems):

@@ -318,7 +318,7 @@ def wgrad_flush_point(x):
             and os.environ.get("KANTTS_NO_EARLY_FLUSH", "") == ""):
         return x
     y = _FlushPoint.apply(x)
-    for attr in ("_kantts_rowmask", "_kantts_prenorm"):  # hand-overs between sub-layers ride through the identity
+    for attr in ("_kantts_rowmask", "_kantts_prenorm", "_kantts_block_bwd"):  # hand-overs between sub-layers ride through the identity
         v = getattr(x, attr, None)
         if v is not None:
             setattr(y, attr, v)
@@ -639,14 +639,15 @@ def fsmn_ffn(x, w1, b1, w2, drop_p=0.0, res_grad=None):
     return linear(h, w2, None)
 
 
-def pnca_block_fused(blk, x, hkv, info, bw_x, bw_h, bw_dev, return_attn, next_ln, training):
+def pnca_block_fused(blk, x, hkv, info, bw_x, bw_h, bw_dev, return_attn, next_ln, training, private_input=False):
     """bf16 mode on a HIP device: ops_bf16.pnca_block_fused (one launch for the block's forward pass); otherwise a no-op
     context (the fp32 parity path keeps its launches)."""
     import contextlib
 
     if get_precision() != "bf16":
         return contextlib.nullcontext()
-    return ops_bf16.pnca_block_fused(blk, x, hkv, info, bw_x, bw_h, bw_dev, return_attn, next_ln, training)
+    return ops_bf16.pnca_block_fused(blk, x, hkv, info, bw_x, bw_h, bw_dev, return_attn, next_ln, training,
+                                     private_input=private_input)
 
 
 def enc_attn_fused(att, x, info, rows, return_attn, next_ln, training):
@@ -942,17 +943,43 @@ class _PncaAttention(torch.autograd.Function):
                 and tok.x.numel() == B * L * D and (bw_dev is not None or (bw_x <= 16 and bw_h <= 16))):
             # fused block: this launch is also the input gradient of the QKV projection and the backward of the LayerNorm in
             # front of it (ops_bf16.LnBwdToken: the projection's backward node only hands the stand-in over)
-            from kantts._hip import pnca_attn_qkv_bwd, rows_sum_accum
+            import kantts._hip as hip
+            from kantts._hip import rows_sum_accum
 
             dx = torch.empty(tok.x.shape, device=q2.device, dtype=torch.float32)
-            part = pnca_attn_qkv_bwd(q2, h2, h2.stride(0), ox, oh, d_ox, d_oh, lsex, lseh, B, L, lens=lens, bw_dev=bw_dev,
-                                     bw_x=bw_x, bw_h=bw_h, att_p=drop_p, seed_x=sx, seed_h=sh, wqkvT=plan.wqkvT, x=tok.x,
-                                     mean0=tok.mean, rstd0=tok.rstd, gamma0=tok.gamma,
-                                     dres=None if tok.dres is None else _c(tok.dres).view(B * L, D),
-                                     zero_rows=tok.zero_rows, dqkv=dqkv, dhkv=dhkv, dx=dx)
+            upper = ((q2, h2, h2.stride(0), ox, oh, d_ox, d_oh, lsex, lseh, B, L),
+                     dict(lens=lens, bw_dev=bw_dev, bw_x=bw_x, bw_h=bw_h, att_p=drop_p, seed_x=sx, seed_h=sh, wqkvT=plan.wqkvT,
+                          x=tok.x, mean0=tok.mean, rstd0=tok.rstd, gamma0=tok.gamma,
+                          dres=None if tok.dres is None else _c(tok.dres).view(B * L, D), zero_rows=tok.zero_rows, dqkv=dqkv,
+                          dhkv=dhkv, dx=dx))
+            part = parts = None
+            low, plan.lower = plan.lower, None
+            if (low is not None and ops_bf16.PNCA_BWD_SEAM["on"] and low.ffn is not None and low.y1 is not None
+                    and not low.done() and hip.pnca_bwd_seam_entry_point()):
+                # the block below hands this block its output privately and its feed-forward node qualifies for the row-local
+                # launch: that launch's work follows this one's on every tile, in ONE launch (kantts_pnca_bwd_seam); the
+                # results wait on the lower plan for that node (ops_bf16._BlockBwd.seam)
+                hid, wt2, wt1, a1, p_out, s2 = low.ffn
+                f32 = dict(device=q2.device, dtype=torch.float32)
+                dep = dict(dz=torch.empty((B * L, 1024), device=q2.device, dtype=torch.bfloat16),
+                           g1=torch.empty((B * L, D), **f32), d_ox=torch.empty((B * L, D), **f32),
+                           d_oh=torch.empty((B * L, D), **f32))
+                parts = hip.pnca_bwd_seam(upper, ((dx.view(B * L, D), hid, low.y1, low.mean1, low.rstd1, low.gamma1.detach(),
+                                                   low.rows, wt2, wt1, low.wfcxT, low.wfchT),
+                                                  dict(alpha1=a1, drop2_p=p_out, drop2_seed=s2, fc_p=low.fc_p,
+                                                       fc_seed=low.fc_seed, **dep)))
+                if parts is not None:
+                    part = parts[0]
+            if part is None:
+                part = hip.pnca_attn_qkv_bwd(*upper[0], **upper[1])
             if part is not None:
                 dg, db = gzeros_like(tok.gamma), gzeros_like(tok.gamma)
                 rows_sum_accum(part, dg, db)
+                if parts is not None:
+                    dep["dg1"], dep["db1"] = gzeros_like(low.gamma1), gzeros_like(low.gamma1)
+                    rows_sum_accum(parts[1], dep["dg1"], dep["db1"])
+                    dep["dx"], dep["version"] = dx, dx._version
+                    low.seam = dep
                 tok.dx, tok.dg, tok.db, tok.by_block = dx, dg, db, True
                 plan.tok0 = plan.wqkvT = None
                 return dqkv.view(B, L, 3 * D), dhkv.view(B, L, 2 * D), None, None, None, None, None, None, None

@@ -372,6 +372,9 @@ def lin_fragT(w):
 PNCA_BLOCK_BWD = {"on": not os.environ.get("KANTTS_NO_PNCA_BLOCK_BWD")}
 # A/B switch: KANTTS_NO_PNCA_ATTN_BWD=1 keeps the two launches of the cross-row half (attention backward, QKV input gradient)
 PNCA_ATTN_BWD = {"on": not os.environ.get("KANTTS_NO_PNCA_ATTN_BWD")}
+# A/B switch: KANTTS_NO_PNCA_BWD_SEAM=1 keeps one launch per half between two blocks of a stack (cross-row half of the upper
+# block, row-local half of the lower one) instead of the seam launch (kantts_pnca_bwd_seam)
+PNCA_BWD_SEAM = {"on": not os.environ.get("KANTTS_NO_PNCA_BWD_SEAM")}
 
 
 class _BlockBwd:
@@ -381,9 +384,16 @@ class _BlockBwd:
     LayerNorm node and the output projection's input-gradient launches would compute, deposits the results here and hands
     autograd stand-ins; the two later nodes check that autograd delivers exactly those stand-ins (anything else means a
     tensor of the chain had another consumer: refused) and return the deposited results.  Weight gradients stay with their
-    nodes (deferred, grouped by shape as everywhere)."""
+    nodes (deferred, grouped by shape as everywhere).
+
+    Seam between two blocks of a stack (kantts_pnca_bwd_seam): ``ffn`` holds what the row-local launch takes from the
+    feed-forward node (set by its forward when that node qualifies for the launch); the plan rides on the block's output
+    (``y._kantts_block_bwd``) and the block that takes that output as its private input keeps it as ``lower``.  The upper
+    block's attention node then runs the lower block's row-local half in its own launch and leaves the results in the lower
+    plan's ``seam``; the lower feed-forward node adopts them if autograd hands it the very dx that launch wrote (same
+    storage, same version, no mask of its own to apply) and launches as ever otherwise."""
     __slots__ = ("y1", "mean1", "rstd1", "gamma1", "rows", "wfcxT", "wfchT", "fc_p", "fc_seed", "placeholder", "d_res", "g1",
-                 "dg1", "db1", "d_ox", "d_oh", "tok0", "wqkvT")
+                 "dg1", "db1", "d_ox", "d_oh", "tok0", "wqkvT", "ffn", "lower", "seam")
 
     def __init__(self):
         for k in self.__slots__:
@@ -393,7 +403,7 @@ class _BlockBwd:
         return self.g1 is not None
 
 
-def pnca_block_fused(blk, x, hkv, info, bw_x, bw_h, bw_dev, return_attn, next_ln, training):
+def pnca_block_fused(blk, x, hkv, info, bw_x, bw_h, bw_dev, return_attn, next_ln, training, private_input=False):
     """Context manager for kantts.models.sambert.PNCABlock.forward: launches the whole block's forward pass
     (csrc/pnca_block.hip) and lets the ops inside the ``with`` adopt its results; a no-op context when the launch does
     not apply (fp32 mode is decided by the caller; other shapes, attention maps requested, band width above 16 or unknown,
@@ -423,6 +433,7 @@ def pnca_block_fused(blk, x, hkv, info, bw_x, bw_h, bw_dev, return_attn, next_ln
         return float(drop.p) if (training and drop.p > 0) else 0.0
 
     att_p, fc_p, p_in, p_out = p_of(at.attention.dropatt), p_of(at.dropout), p_of(ff.dropout_inner), p_of(ff.dropout)
+    lower = getattr(x, "_kantts_block_bwd", None) if private_input else None
     x = _c(x)
     dev = x.device
     ln0 = at.layer_norm
@@ -474,6 +485,8 @@ def pnca_block_fused(blk, x, hkv, info, bw_x, bw_h, bw_dev, return_attn, next_ln
         plan.y1, plan.mean1, plan.rstd1, plan.gamma1, plan.rows = y1, mean1, rstd1, ff.layer_norm.weight, rows
         plan.wfcxT, plan.wfchT, plan.fc_p, plan.fc_seed = lin_fragT(at.fc_x.weight), lin_fragT(at.fc_h.weight), fc_p, sf
         plan.wqkvT = lin_fragT(at.w_x_qkv.weight)  # the cross-row half (ops._PncaAttention.backward: kantts_pnca_attn_qkv_bwd)
+        if PNCA_BWD_SEAM["on"] and lower is not None and lower.ffn is not None and lower.y1.shape[0] == M:
+            plan.lower = lower  # this block's cross-row half and that block's row-local half in one launch
     return _adopting([
         ("linear", dict(y=qkv.view(M, 384), seed=0, ln=None, qkv_of=plan)),
         ("attn", dict(ox=ox, oh=oh, lse_x=lsx, lse_h=lsh, sx=sx, sh=sh, bwd=plan)),
@@ -922,7 +935,11 @@ class _FusedFFNB(torch.autograd.Function):
         if ad is not None:  # computed by the fused block launch (pnca_block_fused)
             hid, out, s1, s2 = ad["hid"], ad["out"], ad["s1"], ad["s2"]
             assert cfg["pair"] and tuple(hid.shape) == (M, F) and tuple(out.shape) == (M, N)
-            cfg["bwd"] = ad.get("bwd")
+            plan = cfg["bwd"] = ad.get("bwd")
+            if (plan is not None and PNCA_BWD_SEAM["on"] and kt == 1 and wt1 is not None and wt2 is not None and h.dtype == BF16
+                    and ctx.needs_input_grad[0] and ctx.needs_input_grad[5]):
+                # what _FusedFFNB.backward hands the row-local launch: the block above may issue it (_BlockBwd.seam)
+                plan.ffn = (hid, wt2, wt1, 1.0 / (1.0 - p_in) if p_in > 0 else 1.0, p_out, s2)
             if pre is not None:
                 pre.xn, pre.mean, pre.rstd = ad["ln"]
             fused = True
@@ -964,7 +981,8 @@ class _FusedFFNB(torch.autograd.Function):
         s1, s2 = ctx.seeds
         dy = _c(dy).view(M, N)
         token = cfg.get("token")
-        if zr is not None and not (token is not None and token.delegated):
+        masked_here = zr is not None and not (token is not None and token.delegated)
+        if masked_here:
             dy = dy.masked_fill(zr.bool().view(M, 1), 0.0)
         d_res = dy.view(*ctx.lead, N)
         dev = dy.device
@@ -975,22 +993,32 @@ class _FusedFFNB(torch.autograd.Function):
         # (k = 3: the three taps are summed in phase 2 from a tile of dz with one halo row either side)
         can_pair = cfg["pair"] and kt in (1, 3) and wt1 is not None and wt2 is not None and (kt == 1 or M % T == 0)
         plan = cfg.get("bwd")
+        seam = None
+        if plan is not None:
+            seam, plan.seam, plan.ffn = plan.seam, None, None
         if (plan is not None and can_pair and kt == 1 and ctx.h_dtype == BF16 and dy.dtype == torch.float32
                 and ctx.needs_input_grad[0] and ctx.needs_input_grad[5]):
             # fused PNCA block: this launch also runs the LayerNorm backward of the sub-layer's input and the input gradient of
             # the attention's output projection (_BlockBwd); the two nodes that follow adopt its results
             from .ops import gzeros_like
 
-            plan.g1 = torch.empty((M, N), device=dev, dtype=torch.float32)
-            plan.d_ox = torch.empty((M, N), device=dev, dtype=torch.float32)
-            plan.d_oh = torch.empty((M, N), device=dev, dtype=torch.float32)
-            plan.dg1, plan.db1 = gzeros_like(plan.gamma1), gzeros_like(plan.gamma1)
-            part = pnca_block_bwd(dy, hid, plan.y1, plan.mean1, plan.rstd1, plan.gamma1.detach(), plan.rows, wt2, wt1,
-                                  plan.wfcxT, plan.wfchT, alpha1=a1, drop2_p=p_out, drop2_seed=s2, fc_p=plan.fc_p,
-                                  fc_seed=plan.fc_seed, dz=dz, g1=plan.g1, d_ox=plan.d_ox, d_oh=plan.d_oh)
-            # the LayerNorm's dgamma / dbeta: per-workgroup partial rows, summed like every other parameter gradient (deferred:
-            # one launch for all recorded sums at the next flush of the weight gradients)
-            rows_sum_accum(part, plan.dg1, plan.db1)
+            if (seam is not None and not masked_here and dy.data_ptr() == seam["dx"].data_ptr()
+                    and dy.numel() == seam["dx"].numel() and dy._version == seam["version"]):
+                # the block above ran this launch's work behind its own cross-row half (kantts_pnca_bwd_seam) on the very
+                # gradient autograd now delivers: nothing else contributed to it, nothing is left to launch
+                dz, plan.g1, plan.d_ox, plan.d_oh = seam["dz"], seam["g1"], seam["d_ox"], seam["d_oh"]
+                plan.dg1, plan.db1 = seam["dg1"], seam["db1"]
+            else:
+                plan.g1 = torch.empty((M, N), device=dev, dtype=torch.float32)
+                plan.d_ox = torch.empty((M, N), device=dev, dtype=torch.float32)
+                plan.d_oh = torch.empty((M, N), device=dev, dtype=torch.float32)
+                plan.dg1, plan.db1 = gzeros_like(plan.gamma1), gzeros_like(plan.gamma1)
+                part = pnca_block_bwd(dy, hid, plan.y1, plan.mean1, plan.rstd1, plan.gamma1.detach(), plan.rows, wt2, wt1,
+                                      plan.wfcxT, plan.wfchT, alpha1=a1, drop2_p=p_out, drop2_seed=s2, fc_p=plan.fc_p,
+                                      fc_seed=plan.fc_seed, dz=dz, g1=plan.g1, d_ox=plan.d_ox, d_oh=plan.d_oh)
+                # the LayerNorm's dgamma / dbeta: per-workgroup partial rows, summed like every other parameter gradient
+                # (deferred: one launch for all recorded sums at the next flush of the weight gradients)
+                rows_sum_accum(part, plan.dg1, plan.db1)
             plan.placeholder, plan.d_res = hb, d_res
             plan.y1 = plan.mean1 = plan.rstd1 = plan.wfcxT = plan.wfchT = None
             dh, fused = hb, True  # stand-in: the LayerNorm node returns plan.g1 and never reads this
@@ -1121,6 +1149,9 @@ def ffn(h, w1, b1, w2, b2, res, *, pad_rows=None, zero_rows=None, p_inner=0.0, p
                                        conv_weight_bf16(w2), wf1, wf2, wt2, wt1, cfg), token)
     if pre is not None and pre.xn is not None:
         y._kantts_prenorm = pre
+    plan = cfg.get("bwd")
+    if plan is not None and plan.ffn is not None:
+        y._kantts_block_bwd = plan  # the block that takes y as its private input may run this block's row-local half
     return y
 
 

@@ -245,7 +245,7 @@ class PNCABlock(nn.Module):
         # bf16 mode: the whole block's forward pass as ONE launch (csrc/pnca_block.hip) whose results the ops below adopt
         # instead of launching; a no-op context whenever that launch does not apply
         with ops.pnca_block_fused(self, input, hkv, info, x_band_width, h_band_width, bw_dev, return_attn, next_ln,
-                                  self.training):
+                                  self.training, private_input=private_input):
             output, ax, ah = self.pnca_attn(input, memory, info, x_band_width, h_band_width, zero_rows=rows,
                                             return_attn=return_attn, bw_dev=bw_dev, hkv=hkv, private_input=private_input,
                                             next_ln=self.pos_ffn.layer_norm)
