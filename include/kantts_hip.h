@@ -1420,6 +1420,11 @@ typedef struct kantts_ctc_args {
 } kantts_ctc_args;
 long long kantts_ctc_attn_workspace(int B, int T1, int T2);
 int kantts_ctc_attn(const kantts_ctc_args* args, void* stream);
+/* kantts_ctc_attn_wide: the same arguments, workspace and arithmetic with eight states per thread instead of four, for the
+ * token counts of byte-input voices; the gradient pass is a second launch on `stream` (a wave per frame, the whole chip)
+ * instead of the tail of the first.  Writes every cell of loss and grad.  Limits: T2 <= 1023 tokens (2 T2 + 1 <= 2048 states, the width of kantts_align_attn_fwd),
+ * T1 <= 24576 frames (KANTTS_E_UNSUPPORTED beyond).  It takes narrow shapes too; kantts_ctc_attn prefetches deeper there. */
+int kantts_ctc_attn_wide(const kantts_ctc_args* args, void* stream);
 
 /* kantts_enc_attn_fwd: the attention sub-layer of an encoder FFT block (MultiHeadSelfAttention.forward,
  * kantts/models/sambert/__init__.py:52-106 inside FFTBlock.forward :152-184) as ONE launch, a workgroup per sequence:

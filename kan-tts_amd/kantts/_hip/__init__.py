@@ -531,6 +531,8 @@ def lib():
         L.kantts_ctc_attn.argtypes = [POINTER(CtcArgs), c_void_p]
         L.kantts_ctc_attn_workspace.argtypes = [c_int, c_int, c_int]
         L.kantts_ctc_attn_workspace.restype = c_longlong
+        if hasattr(L, "kantts_ctc_attn_wide"):  # has_ctc_wide(): a library built before it still loads
+            L.kantts_ctc_attn_wide.argtypes = [POINTER(CtcArgs), c_void_p]
         L.kantts_pnca_decode_blob_sizes.argtypes = [c_int, c_int, c_int, c_int, POINTER(ctypes.c_longlong),
                                                     POINTER(ctypes.c_longlong)]
         L.kantts_pnca_block_bwd_ws_floats.argtypes = [c_int]
@@ -667,6 +669,7 @@ EXPORTED_SYMBOLS = [
     *SYBERT_SYMBOLS,
     "kantts_fsmn_dw41_many",
     "kantts_pnca_bwd_seam",
+    "kantts_ctc_attn_wide",
 ]
 
 
@@ -1338,12 +1341,30 @@ def enc_attn_fwd(x, xn, B, L, *, lens, rowmask, wqkv, bqkv, wfc, bfc, ln1, att_p
     return True
 
 
+CTC_NARROW_T2 = 511  # kantts_ctc_attn: 2 T2 + 1 <= 1024 states
+CTC_WIDE_T2 = 1023   # kantts_ctc_attn_wide: 2 T2 + 1 <= 2048 states (the aligner's own width)
+
+
+def has_ctc_wide():
+    """True when the loaded library exports the wide form of the alignment CTC (csrc/ctc.hip: up to 1023 tokens, what a
+    byte-input voice needs)."""
+    return hasattr(lib(), "kantts_ctc_attn_wide")
+
+
 def ctc_attn(logits, in_lens32, out_lens32, blank, grad_scale):
-    """AttentionCTCLoss and its gradient in one launch (csrc/ctc.hip; kantts_ctc_attn in the header).  logits (B, T1, T2)
-    fp32 contiguous; lengths int32 on the device.  Returns (loss (B,) = nll_b / S_b, grad (B, T1, T2) = grad_scale * d loss_b
-    / d logits)."""
+    """AttentionCTCLoss and its gradient without a host read (csrc/ctc.hip; kantts_ctc_attn / kantts_ctc_attn_wide in the
+    header: one launch for up to 511 tokens, two for up to 1023).  logits (B, T1, T2) fp32 contiguous; lengths int32 on the device.
+    Returns (loss (B,) = nll_b / S_b, grad (B, T1, T2) = grad_scale * d loss_b / d logits)."""
     B, T1, T2 = logits.shape
     assert logits.is_contiguous() and logits.dtype == torch.float32
+    entry = "kantts_ctc_attn"
+    if T2 > CTC_NARROW_T2:
+        entry = "kantts_ctc_attn_wide"
+        if T2 > CTC_WIDE_T2:
+            raise RuntimeError("ctc_attn: %d tokens are more than the %d %s takes" % (T2, CTC_WIDE_T2, entry))
+        if not has_ctc_wide():
+            raise RuntimeError("ctc_attn: %d tokens (more than %d) need the entry point %s, which the loaded library does "
+                               "not export" % (T2, CTC_NARROW_T2, entry))
     n = int(lib().kantts_ctc_attn_workspace(int(B), int(T1), int(T2)))
     ws = torch.empty((max(n, 1),), device=logits.device, dtype=torch.float32)
     loss = torch.empty((B,), device=logits.device, dtype=torch.float32)
@@ -1352,7 +1373,7 @@ def ctc_attn(logits, in_lens32, out_lens32, blank, grad_scale):
     g.logits, g.in_lens, g.out_lens = ptr(logits, torch.float32), ptr(in_lens32, torch.int32), ptr(out_lens32, torch.int32)
     g.ws, g.loss, g.grad = ptr(ws, torch.float32), ptr(loss, torch.float32), ptr(grad, torch.float32)
     g.B, g.T1, g.T2, g.blank, g.grad_scale = int(B), int(T1), int(T2), float(blank), float(grad_scale)
-    check(lib().kantts_ctc_attn(ctypes.byref(g), stream()), "ctc_attn")
+    check(getattr(lib(), entry)(ctypes.byref(g), stream()), entry[len("kantts_"):])
     return loss, grad
 
 

@@ -22,17 +22,17 @@ logging.basicConfig(format="%(asctime)s, %(levelname)-4s [%(filename)s:%(lineno)
 
 def am_inputs(symbol_seq, ling_unit, device, se=None):
     """(inputs_ling, inputs_emotion, inputs_speaker, input_lengths) of one sentence, batch 1."""
-    if ling_unit.using_byte():
-        raise NotImplementedError("byte-index inputs (sambert_16k_MAS_byte.yaml) are outside the hot path")
     feats = ling_unit.encode_symbol_sequence(symbol_seq)
-    sy, tone, syllable, ws, emo, spk = (torch.from_numpy(np.asarray(f)).long().to(device) for f in feats[:6])
+    # byte-input voices carry one symbol stream in front of emotion and speaker, the others four (reference :62-85)
+    n_ling = 1 if ling_unit.using_byte() else 4
+    *ling, emo, spk = (torch.from_numpy(np.asarray(f)).long().to(device) for f in feats[:n_ling + 2])
     # the trailing "~" token is dropped from every stream (reference :117-122)
-    inputs_ling = torch.stack([sy, tone, syllable, ws], dim=-1).unsqueeze(0)[:, :-1, :]
+    inputs_ling = torch.stack(ling, dim=-1).unsqueeze(0)[:, :-1, :]
     inputs_emo = emo.unsqueeze(0)[:, :-1]
     if se is not None:
         # SE models (sambert_se_nsf_global_16k.yaml): the utterance-level speaker embedding of --se_file, (1, dim),
         # repeated over the symbols instead of speaker ids (reference :99-106)
-        inputs_spk = torch.from_numpy(np.asarray(se).repeat(len(feats[5]), axis=0)).float().to(device).unsqueeze(0)[:, :-1, :]
+        inputs_spk = torch.from_numpy(np.asarray(se).repeat(len(feats[n_ling + 1]), axis=0)).float().to(device).unsqueeze(0)[:, :-1, :]
     else:
         inputs_spk = spk.unsqueeze(0)[:, :-1]
     inputs_len = torch.full((1,), inputs_emo.size(1), dtype=torch.long, device=device)

@@ -68,15 +68,20 @@ def _pin(d, pin):
 def am_collate(batch, r, pad_ids, pin=False, se=False, fp=False):
     """batch: list of (ling_data, mel, dur, f0, energy, attn_prior, fp_label, se) as AM_Dataset.__getitem__ returns
     (ling_data = [sy, tone, syllable_flag, word_segment, emotion, speaker] integer arrays including the trailing "~");
-    pad_ids: the six per-stream pad ids (ling_unit._sub_unit_pad in stream order).  ``fp``: filled-pause batches carry
+    pad_ids: the six per-stream pad ids (ling_unit._sub_unit_pad in stream order) -- three, and ling_data = [byte_index,
+    emotion, speaker], for a byte-input voice, whose ``input_lings`` is then (B, T, 1).  ``fp``: filled-pause batches carry
     ``fp_label`` (item slot 6, zero-padded to the input width) and pitch / energy as wide as the DURATIONS, which describe
     the sequence after the insertion (reference dataset.py:773-779, :801-805)."""
     padder = Padder()
     with_duration = not any(item[2] is None for item in batch)
     max_in = max(len(x[0][0]) for x in batch)
     max_dur = max(x[2].shape[0] for x in batch) + 1 if with_duration else None
-    streams = [padder._prepare_scalar_inputs([x[0][k] for x in batch], max_in, pad_ids[k]).long() for k in range(6)]
-    out = {"input_lings": torch.stack(streams[:4], dim=2), "input_emotions": streams[4], "input_speakers": streams[5]}
+    n = len(pad_ids)  # 6 streams, or 3 for a byte-input voice: [byte_index, emotion, speaker] (reference dataset.py:699-707)
+    if n not in (3, 6):
+        raise ValueError("am_collate: %d pad ids; a batch has 6 symbol streams, or 3 for byte-input voices" % n)
+    streams = [padder._prepare_scalar_inputs([x[0][k] for x in batch], max_in, pad_ids[k]).long() for k in range(n)]
+    out = {"input_lings": torch.stack(streams[:n - 2], dim=2), "input_emotions": streams[n - 2],
+           "input_speakers": streams[n - 1]}
     if se:  # speaker-embedding models: one (1, D) vector per utterance, repeated over its symbols (dataset.py:757-762)
         out["input_speakers"] = padder._prepare_targets([x[7].repeat(len(x[0][0]), axis=0) for x in batch], max_in, 0.0)
     if fp:

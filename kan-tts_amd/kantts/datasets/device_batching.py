@@ -15,9 +15,10 @@ corpus (10 h of 22.05 kHz audio and its 80-bin mels is ~4 GB) fits next to the m
 pinned memory and copies it on a side stream while the current step runs (double-buffered; what
 ``GraphedSambertStep.load_batch`` / ``GraphedGanStep.load_batch`` consume).
 
-Every shipped SAM-BERT training configuration except the byte-input one can train from a resident corpus: duration-
-supervised voices, filled-pause voices, duration-free (MAS) voices -- whose alignment prior is evaluated on the device per
-batch instead of per utterance on the host -- and speaker-embedding (SE) voices (csrc/attn_prior.hip).
+Every shipped SAM-BERT training configuration can train from a resident corpus: duration-supervised voices, filled-pause
+voices, duration-free (MAS) voices -- whose alignment prior is evaluated on the device per batch instead of per utterance
+on the host --, speaker-embedding (SE) voices (csrc/attn_prior.hip) and byte-input voices (MAS items whose flat symbol rows
+are three wide -- byte_index | emotion | speaker -- instead of six).
 """
 import logging
 
@@ -81,7 +82,8 @@ class DeviceVocSet:
 
 class DeviceAMSet:
     """Acoustic-model training set in HBM (items of AM_Dataset.__getitem__: (ling_data, mel, dur, f0, energy, attn_prior,
-    fp_label, se) with ling_data = six integer streams incl. the trailing "~").  ``batch(indices)``
+    fp_label, se) with ling_data = six integer streams incl. the trailing "~" -- three for a byte-input voice, whose
+    ``input_lings`` is (B, T, 1)).  ``batch(indices)``
     == ``am_collate([items[i] for i in indices], r, pad_ids, se=se, fp=fp)`` with device tensors.
 
     Duration-supervised items carry the host integer ``band_width`` along.  ``fp``: filled-pause items -- the batch carries
@@ -125,6 +127,10 @@ class DeviceAMSet:
         self.n_f0 = np.array([len(it[3]) for it in items], dtype=np.int64)
         self.n_en = np.array([len(it[4]) for it in items], dtype=np.int64)
         self.pad_ids = torch.as_tensor(list(pad_ids), dtype=torch.int64).to(self.device)
+        self.n_streams = len(pad_ids)
+        if self.n_streams not in (3, 6) or any(len(it[0]) != self.n_streams for it in items):
+            raise ValueError("%d pad ids: items carry 6 symbol streams, or 3 (byte_index, emotion, speaker) for byte-input "
+                             "voices, one pad id each" % self.n_streams)
         if self.se:
             emb = [None if it[7] is None else np.asarray(it[7], dtype=np.float32).reshape(-1) for it in items]
             if any(e is None for e in emb):
@@ -185,8 +191,9 @@ class DeviceAMSet:
         i64 = lambda a: _dev(a, torch.int64, d)  # noqa: E731
         n_sym32 = i32(self.n_sym[idx])
         ling = hip.ragged_rows(self.ling, i64(self.sym_off[idx]), n_sym32, max_in, pad=self.pad_ids)
-        out = {"input_lings": ling[:, :, :4].contiguous(), "input_emotions": ling[:, :, 4].contiguous(),
-               "input_speakers": ling[:, :, 5].contiguous()}
+        n = self.n_streams  # 6, or 3 for a byte-input voice: (B, T, 1) symbols | emotion | speaker
+        out = {"input_lings": ling[:, :, :n - 2].contiguous(), "input_emotions": ling[:, :, n - 2].contiguous(),
+               "input_speakers": ling[:, :, n - 1].contiguous()}
         if self.se:  # the utterance's embedding over its symbols ("~" included), zeros behind them
             out["input_speakers"] = hip.broadcast_rows(self.emb, i64(idx), n_sym32, max_in)
         out["valid_input_lengths"] = i64(self.n_sym[idx] - 1)  # minus "~"

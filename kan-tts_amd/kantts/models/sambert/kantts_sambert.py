@@ -7,8 +7,8 @@ deliberate (documented in DESIGN.md):
     only materialised when ``model.return_attns`` is True; the dict keys are always present;
   * padding is described by lengths, never by materialised (B, L, L) masks;
   * the MAS alignment path (sambert_16k_MAS.yaml), speaker-embedding input (SE: True) and the filled-pause voice
-    (FP: True, sambert_fp_8k.yaml) are implemented; byte-input variants and FP together with SE raise
-    NotImplementedError.
+    (FP: True, sambert_fp_8k.yaml) and byte-index input (using_byte: True, sambert_16k_MAS_byte.yaml) are implemented;
+    FP together with SE, and byte input together with FP or SE, raise NotImplementedError.
 """
 import contextlib
 import types
@@ -188,12 +188,18 @@ class TextFftEncoder(nn.Module):
         d_emb = config["embedding_dim"]
         self.using_byte = False
         self.ling_embedding_grad = False  # set by KanTtsSAMBERT when the MAS attention consumes ling_embedding
-        if config.get("using_byte", False):
-            raise NotImplementedError("byte-index inputs (sambert_16k_MAS_byte.yaml) are outside the hot path")
-        self.sy_emb = nn.Embedding(config["sy"], d_emb)
-        self.tone_emb = nn.Embedding(config["tone"], d_emb)
-        self.syllable_flag_emb = nn.Embedding(config["syllable_flag"], d_emb)
-        self.ws_emb = nn.Embedding(config["word_segment"], d_emb)
+        if config.get("using_byte", False):  # sambert_16k_MAS_byte.yaml: one table of byte symbols (reference :262-265)
+            for other in ("FP", "SE"):
+                if config.get(other, False):
+                    raise NotImplementedError("using_byte together with %s is not a shipped configuration: byte-input voices "
+                                              "take one byte table, category emotions and category speakers" % other)
+            self.using_byte = True
+            self.byte_index_emb = nn.Embedding(config["byte_index"], d_emb)
+        else:
+            self.sy_emb = nn.Embedding(config["sy"], d_emb)
+            self.tone_emb = nn.Embedding(config["tone"], d_emb)
+            self.syllable_flag_emb = nn.Embedding(config["syllable_flag"], d_emb)
+            self.ws_emb = nn.Embedding(config["word_segment"], d_emb)
         max_len = config["max_len"]
         nb_layers = config["encoder_num_layers"]
         nb_heads = config["encoder_num_heads"]
@@ -213,11 +219,15 @@ class TextFftEncoder(nn.Module):
     def forward(self, inputs_ling, masks=None, return_attns=False):
         T = inputs_ling.size(1)
         pos = self.ling_enc.position_enc.table_for(T, inputs_ling.device)
-        # one gather kernel: (sy + tone + syllable_flag + ws) * sqrt(d_model) (+ sinusoid table);
-        # the scaled sum is also what the reference hands back as `ling_embedding` (in-place *=, :62)
+        # one gather kernel: (sy + tone + syllable_flag + ws) * sqrt(d_model) (+ sinusoid table) -- a byte-input voice sums
+        # one table instead of four; the scaled sum is also what the reference hands back as `ling_embedding` (in-place *=, :62)
+        if self.using_byte:
+            streams, tables = inputs_ling[:, :, :1], [self.byte_index_emb.weight]
+        else:
+            streams = inputs_ling[:, :, :4]
+            tables = [self.sy_emb.weight, self.tone_emb.weight, self.syllable_flag_emb.weight, self.ws_emb.weight]
         x, ling_embedding = ops.embed_sum(
-            inputs_ling[:, :, :4],
-            [self.sy_emb.weight, self.tone_emb.weight, self.syllable_flag_emb.weight, self.ws_emb.weight],
+            streams, tables,
             pos=pos, scale=self.d_model ** 0.5, want_scaled="grad" if self.ling_embedding_grad else True)
         enc_output, attns = self.ling_enc(x, masks, return_attns, prescaled=True)
         if hasattr(self, "ling_proj"):

@@ -336,7 +336,8 @@ class AttentionCTCLoss(torch.nn.Module):
     """CTC over the alignment log-probabilities with the phoneme sequence 1..N as target and a constant blank score
     (reference :482-508).  The reference loops over utterances (slice, log_softmax, one torch.nn.CTCLoss call each, whose
     ATen implementation copies the lengths to the host); here the batch is ONE launch of kantts_ctc_attn (csrc/ctc.hip:
-    a workgroup per utterance walks the alpha and beta recurrences and writes the gradient), with the lengths read on the
+    a workgroup per utterance walks the alpha and beta recurrences and writes the gradient; past 511 tokens -- byte-input
+    voices -- kantts_ctc_attn_wide, with the gradient pass as a second launch), with the lengths read on the
     device -- so the MAS training step can be captured in a hipGraph.  Result = mean_b(nll_b / S_b), which is what the
     reference's sum of per-utterance "mean" losses / B computes; zero_infinity semantics."""
 
