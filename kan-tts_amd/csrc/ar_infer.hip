@@ -18,9 +18,6 @@
 // lane are issued before the first is consumed.  Activations live in LDS; HBM sees the K / V cache and the output frames.
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 #define AR_THREADS 512
 #define AR_WAVES 8
 #define AR_D 128        // model width

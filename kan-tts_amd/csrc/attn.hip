@@ -75,28 +75,6 @@ __device__ __forceinline__ void key_range(int mode, int i, int len, int L, int b
   }
 }
 
-__device__ __forceinline__ void load16(const float* p, float* r) {
-  const float4* p4 = reinterpret_cast<const float4*>(p);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float4 t = p4[e];
-    r[4 * e + 0] = t.x;
-    r[4 * e + 1] = t.y;
-    r[4 * e + 2] = t.z;
-    r[4 * e + 3] = t.w;
-  }
-}
-__device__ __forceinline__ void store16(float* p, const float* r) {
-  float4* p4 = reinterpret_cast<float4*>(p);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) p4[e] = make_float4(r[4 * e], r[4 * e + 1], r[4 * e + 2], r[4 * e + 3]);
-}
-__device__ __forceinline__ float dot16(const float* a, const float* b) {
-  float s = 0.f;
-#pragma unroll
-  for (int d = 0; d < DH; ++d) s = fmaf(a[d], b[d], s);
-  return s;
-}
 
 // grid: (ceil(L/128), H, B), block 128: thread <-> query row i
 __global__ __launch_bounds__(128) void attn_fwd_kernel(const AttnArgs a) {
@@ -105,13 +83,13 @@ __global__ __launch_bounds__(128) void attn_fwd_kernel(const AttnArgs a) {
   if (i >= a.L) return;
   const int len = a.lens ? a.lens[b] : a.L;
   const int bw = a.bw_dev ? *a.bw_dev : a.bw;
-  const uint64_t seed = a.seed + (a.seed_dev ? *a.seed_dev : 0ull);
+  const uint64_t seed = a.seed + kantts_seed_offset(a.seed_dev);
   int lo, hi;
   key_range(a.mode, i, len, a.L, bw, lo, hi);
   if (a.mode != 0 && i >= len && !a.probs) hi = lo - 1;  // padded query: skipped (see header)
   const long long row = (long long)b * a.L + i;
   float q[DH], o[DH];
-  load16(a.q + row * a.ldq + h * DH, q);
+  kantts_load16(a.q + row * a.ldq + h * DH, q);
 #pragma unroll
   for (int d = 0; d < DH; ++d) o[d] = 0.f;
   const float* kb = a.k + (long long)b * a.L * a.ldk + h * DH;
@@ -119,8 +97,8 @@ __global__ __launch_bounds__(128) void attn_fwd_kernel(const AttnArgs a) {
   float m = -INFINITY;
   for (int j = lo; j <= hi; ++j) {
     float kk[DH];
-    load16(kb + (long long)j * a.ldk, kk);
-    m = fmaxf(m, dot16(q, kk) * a.scale);
+    kantts_load16(kb + (long long)j * a.ldk, kk);
+    m = fmaxf(m, kantts_dot16(q, kk) * a.scale);
   }
   float l = 0.f;
   float* prow = a.probs ? a.probs + (((long long)h * a.B + b) * a.L + i) * a.L : nullptr;
@@ -128,9 +106,9 @@ __global__ __launch_bounds__(128) void attn_fwd_kernel(const AttnArgs a) {
   KanttsDropSeq drop(a.drop_p, seed);  // consecutive keys share a 64-bit hash four at a time
   for (int j = lo; j <= hi; ++j) {
     float kk[DH], vv[DH];
-    load16(kb + (long long)j * a.ldk, kk);
-    load16(vb + (long long)j * a.ldv, vv);
-    float e = expf(dot16(q, kk) * a.scale - m);
+    kantts_load16(kb + (long long)j * a.ldk, kk);
+    kantts_load16(vb + (long long)j * a.ldv, vv);
+    float e = expf(kantts_dot16(q, kk) * a.scale - m);
     l += e;
     float ed = e * drop.scale(rng_row + j);
 #pragma unroll
@@ -139,15 +117,15 @@ __global__ __launch_bounds__(128) void attn_fwd_kernel(const AttnArgs a) {
   const float inv = (hi >= lo) ? 1.f / l : 0.f;
 #pragma unroll
   for (int d = 0; d < DH; ++d) o[d] *= inv;
-  store16(a.o + row * a.ldo + h * DH, o);
+  kantts_store16(a.o + row * a.ldo + h * DH, o);
   a.lse[((long long)b * a.H + h) * a.L + i] = (hi >= lo) ? (m + logf(l)) : 0.f;
   if (prow) {
     for (int j = 0; j < a.L; ++j) {
       float p = 0.f;
       if (j >= lo && j <= hi) {
         float kk[DH];
-        load16(kb + (long long)j * a.ldk, kk);
-        p = expf(dot16(q, kk) * a.scale - m) * inv * drop.scale(rng_row + j);
+        kantts_load16(kb + (long long)j * a.ldk, kk);
+        p = expf(kantts_dot16(q, kk) * a.scale - m) * inv * drop.scale(rng_row + j);
       }
       prow[j] = p;
     }
@@ -161,16 +139,16 @@ __global__ __launch_bounds__(128) void attn_bwd_dq_kernel(const AttnArgs a) {
   if (i >= a.L) return;
   const int len = a.lens ? a.lens[b] : a.L;
   const int bw = a.bw_dev ? *a.bw_dev : a.bw;
-  const uint64_t seed = a.seed + (a.seed_dev ? *a.seed_dev : 0ull);
+  const uint64_t seed = a.seed + kantts_seed_offset(a.seed_dev);
   int lo, hi;
   key_range(a.mode, i, len, a.L, bw, lo, hi);
   if (a.mode != 0 && i >= len) hi = lo - 1;  // padded query rows carry no gradient
   const long long row = (long long)b * a.L + i;
   float q[DH], go[DH], oo[DH], dq[DH];
-  load16(a.q + row * a.ldq + h * DH, q);
-  load16(a.d_o + row * a.lddo + h * DH, go);
-  load16(a.o + row * a.ldo + h * DH, oo);
-  const float D = dot16(go, oo);
+  kantts_load16(a.q + row * a.ldq + h * DH, q);
+  kantts_load16(a.d_o + row * a.lddo + h * DH, go);
+  kantts_load16(a.o + row * a.ldo + h * DH, oo);
+  const float D = kantts_dot16(go, oo);
   const long long sidx = ((long long)b * a.H + h) * a.L + i;
   const float lse = a.lse[sidx];
   a.dvec[sidx] = D;
@@ -182,10 +160,10 @@ __global__ __launch_bounds__(128) void attn_bwd_dq_kernel(const AttnArgs a) {
   KanttsDropSeq drop(a.drop_p, seed);
   for (int j = lo; j <= hi; ++j) {
     float kk[DH], vv[DH];
-    load16(kb + (long long)j * a.ldk, kk);
-    load16(vb + (long long)j * a.ldv, vv);
-    float p = expf(dot16(q, kk) * a.scale - lse);
-    float dp = dot16(go, vv) * drop.scale(rng_row + j);
+    kantts_load16(kb + (long long)j * a.ldk, kk);
+    kantts_load16(vb + (long long)j * a.ldv, vv);
+    float p = expf(kantts_dot16(q, kk) * a.scale - lse);
+    float dp = kantts_dot16(go, vv) * drop.scale(rng_row + j);
     float ds = p * (dp - D) * a.scale;
 #pragma unroll
     for (int d = 0; d < DH; ++d) dq[d] = fmaf(ds, kk[d], dq[d]);
@@ -193,11 +171,11 @@ __global__ __launch_bounds__(128) void attn_bwd_dq_kernel(const AttnArgs a) {
   float* dst = a.dq + row * a.lddq + h * DH;
   if (a.accumulate_dq) {
     float old[DH];
-    load16(dst, old);
+    kantts_load16(dst, old);
 #pragma unroll
     for (int d = 0; d < DH; ++d) dq[d] += old[d];
   }
-  store16(dst, dq);
+  kantts_store16(dst, dq);
 }
 
 // dK, dV (thread <-> key row j): walks the queries whose interval contains j.
@@ -207,11 +185,11 @@ __global__ __launch_bounds__(128) void attn_bwd_dkv_kernel(const AttnArgs a) {
   if (j >= a.L) return;
   const int len = a.lens ? a.lens[b] : a.L;
   const int bw = a.bw_dev ? *a.bw_dev : a.bw;
-  const uint64_t seed = a.seed + (a.seed_dev ? *a.seed_dev : 0ull);
+  const uint64_t seed = a.seed + kantts_seed_offset(a.seed_dev);
   const long long krow = (long long)b * a.L + j;
   float kk[DH], vv[DH], dk[DH], dv[DH];
-  load16(a.k + krow * a.ldk + h * DH, kk);
-  load16(a.v + krow * a.ldv + h * DH, vv);
+  kantts_load16(a.k + krow * a.ldk + h * DH, kk);
+  kantts_load16(a.v + krow * a.ldv + h * DH, vv);
 #pragma unroll
   for (int d = 0; d < DH; ++d) {
     dk[d] = 0.f;
@@ -238,12 +216,12 @@ __global__ __launch_bounds__(128) void attn_bwd_dkv_kernel(const AttnArgs a) {
       key_range(a.mode, i, len, a.L, bw, lo, hi);
       if (j < lo || j > hi) continue;
       float q[DH], go[DH];
-      load16(qb + (long long)i * a.ldq, q);
-      load16(gb + (long long)i * a.lddo, go);
-      const float p = expf(dot16(q, kk) * a.scale - a.lse[sbase + i]);
+      kantts_load16(qb + (long long)i * a.ldq, q);
+      kantts_load16(gb + (long long)i * a.lddo, go);
+      const float p = expf(kantts_dot16(q, kk) * a.scale - a.lse[sbase + i]);
       const float dsc = kantts_dropout_scale(a.drop_p, seed, ((((uint64_t)h * a.B + b) * a.L + i) * (uint64_t)a.L) + j);
       const float pd = p * dsc;
-      const float dp = dot16(go, vv) * dsc;
+      const float dp = kantts_dot16(go, vv) * dsc;
       const float ds = p * (dp - a.dvec[sbase + i]) * a.scale;
 #pragma unroll
       for (int d = 0; d < DH; ++d) {
@@ -252,8 +230,8 @@ __global__ __launch_bounds__(128) void attn_bwd_dkv_kernel(const AttnArgs a) {
       }
     }
   }
-  store16(a.dk + krow * a.lddk + h * DH, dk);
-  store16(a.dv + krow * a.lddv + h * DH, dv);
+  kantts_store16(a.dk + krow * a.lddk + h * DH, dk);
+  kantts_store16(a.dv + krow * a.lddv + h * DH, dv);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -266,22 +244,6 @@ __global__ __launch_bounds__(128) void attn_bwd_dkv_kernel(const AttnArgs a) {
 #define AT_THREADS 256
 
 // a staged row (16 floats at a 16-byte aligned LDS address) into registers: four ds_read_b128
-__device__ __forceinline__ void lds16(const float* p, float* r) {
-  const float4* p4 = reinterpret_cast<const float4*>(p);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float4 t = p4[e];
-    r[4 * e + 0] = t.x;
-    r[4 * e + 1] = t.y;
-    r[4 * e + 2] = t.z;
-    r[4 * e + 3] = t.w;
-  }
-}
-__device__ __forceinline__ float dot16l(const float* a, const float* lrow) {
-  float b[DH];
-  lds16(lrow, b);
-  return dot16(a, b);
-}
 
 __device__ __forceinline__ void stage_rows(const float* __restrict__ src, int ld, int L, float* __restrict__ dst) {
   for (int idx = threadIdx.x; idx < L * 4; idx += AT_THREADS) {
@@ -299,14 +261,14 @@ __device__ __forceinline__ void attn_fwd_lds_body(const AttnArgs& a, const int h
   float q0[DH];
   {
     const int i0 = min((int)threadIdx.x, a.L - 1);
-    load16(a.q + ((long long)b * a.L + i0) * a.ldq + h * DH, q0);
+    kantts_load16(a.q + ((long long)b * a.L + i0) * a.ldq + h * DH, q0);
   }
   stage_rows(a.k + (long long)b * a.L * a.ldk + h * DH, a.ldk, a.L, Ks);
   stage_rows(a.v + (long long)b * a.L * a.ldv + h * DH, a.ldv, a.L, Vs);
   __syncthreads();
   const int len = a.lens ? a.lens[b] : a.L;
   const int bw = a.bw_dev ? *a.bw_dev : a.bw;
-  const uint64_t seed = a.seed + (a.seed_dev ? *a.seed_dev : 0ull);
+  const uint64_t seed = a.seed + kantts_seed_offset(a.seed_dev);
   for (int i = threadIdx.x; i < a.L; i += AT_THREADS) {
     int lo, hi;
     key_range(a.mode, i, len, a.L, bw, lo, hi);
@@ -317,35 +279,35 @@ __device__ __forceinline__ void attn_fwd_lds_body(const AttnArgs& a, const int h
 #pragma unroll
       for (int d = 0; d < DH; ++d) q[d] = q0[d];
     } else {
-      load16(a.q + row * a.ldq + h * DH, q);
+      kantts_load16(a.q + row * a.ldq + h * DH, q);
     }
 #pragma unroll
     for (int d = 0; d < DH; ++d) o[d] = 0.f;
     float m = -INFINITY;
-    for (int j = lo; j <= hi; ++j) m = fmaxf(m, dot16l(q, Ks + j * AT_LD) * a.scale);
+    for (int j = lo; j <= hi; ++j) m = fmaxf(m, kantts_dot16l(q, Ks + j * AT_LD) * a.scale);
     float l = 0.f;
     const uint64_t rng_row = (((uint64_t)h * a.B + b) * a.L + i) * (uint64_t)a.L;
     KanttsDropSeq drop(a.drop_p, seed);
     for (int j = lo; j <= hi; ++j) {
-      const float e = expf(dot16l(q, Ks + j * AT_LD) * a.scale - m);
+      const float e = expf(kantts_dot16l(q, Ks + j * AT_LD) * a.scale - m);
       l += e;
       const float ed = e * drop.scale(rng_row + j);
       float vv[DH];
-      lds16(Vs + j * AT_LD, vv);
+      kantts_lds16(Vs + j * AT_LD, vv);
 #pragma unroll
       for (int d = 0; d < DH; ++d) o[d] = fmaf(ed, vv[d], o[d]);
     }
     const float inv = (hi >= lo) ? 1.f / l : 0.f;
 #pragma unroll
     for (int d = 0; d < DH; ++d) o[d] *= inv;
-    store16(a.o + row * a.ldo + h * DH, o);
+    kantts_store16(a.o + row * a.ldo + h * DH, o);
     a.lse[((long long)b * a.H + h) * a.L + i] = (hi >= lo) ? (m + logf(l)) : 0.f;
     if (a.probs) {
       float* prow = a.probs + (((long long)h * a.B + b) * a.L + i) * a.L;
       for (int j = 0; j < a.L; ++j) {
         float p = 0.f;
         if (j >= lo && j <= hi)
-          p = expf(dot16l(q, Ks + j * AT_LD) * a.scale - m) * inv * drop.scale(rng_row + j);
+          p = expf(kantts_dot16l(q, Ks + j * AT_LD) * a.scale - m) * inv * drop.scale(rng_row + j);
         prow[j] = p;
       }
     }
@@ -363,16 +325,16 @@ __device__ __forceinline__ void attn_bwd_dq_lds_body(const AttnArgs& a, const in
   float q0[DH], go0[DH], oo0[DH];
   {
     const long long r0 = (long long)b * a.L + min((int)threadIdx.x, a.L - 1);
-    load16(a.q + r0 * a.ldq + h * DH, q0);
-    load16(a.d_o + r0 * a.lddo + h * DH, go0);
-    load16(a.o + r0 * a.ldo + h * DH, oo0);
+    kantts_load16(a.q + r0 * a.ldq + h * DH, q0);
+    kantts_load16(a.d_o + r0 * a.lddo + h * DH, go0);
+    kantts_load16(a.o + r0 * a.ldo + h * DH, oo0);
   }
   stage_rows(a.k + (long long)b * a.L * a.ldk + h * DH, a.ldk, a.L, Ks);
   stage_rows(a.v + (long long)b * a.L * a.ldv + h * DH, a.ldv, a.L, Vs);
   __syncthreads();
   const int len = a.lens ? a.lens[b] : a.L;
   const int bw = a.bw_dev ? *a.bw_dev : a.bw;
-  const uint64_t seed = a.seed + (a.seed_dev ? *a.seed_dev : 0ull);
+  const uint64_t seed = a.seed + kantts_seed_offset(a.seed_dev);
   for (int i = threadIdx.x; i < a.L; i += AT_THREADS) {
     int lo, hi;
     key_range(a.mode, i, len, a.L, bw, lo, hi);
@@ -387,11 +349,11 @@ __device__ __forceinline__ void attn_bwd_dq_lds_body(const AttnArgs& a, const in
         oo[d] = oo0[d];
       }
     } else {
-      load16(a.q + row * a.ldq + h * DH, q);
-      load16(a.d_o + row * a.lddo + h * DH, go);
-      load16(a.o + row * a.ldo + h * DH, oo);
+      kantts_load16(a.q + row * a.ldq + h * DH, q);
+      kantts_load16(a.d_o + row * a.lddo + h * DH, go);
+      kantts_load16(a.o + row * a.ldo + h * DH, oo);
     }
-    const float D = dot16(go, oo);
+    const float D = kantts_dot16(go, oo);
     const long long sidx = ((long long)b * a.H + h) * a.L + i;
     const float lse = a.lse[sidx];
     if (a.dvec) a.dvec[sidx] = D;
@@ -401,9 +363,9 @@ __device__ __forceinline__ void attn_bwd_dq_lds_body(const AttnArgs& a, const in
     KanttsDropSeq drop(a.drop_p, seed);
     for (int j = lo; j <= hi; ++j) {
       float kk[DH];
-      lds16(Ks + j * AT_LD, kk);
-      const float p = expf(dot16(q, kk) * a.scale - lse);
-      const float dp = dot16l(go, Vs + j * AT_LD) * drop.scale(rng_row + j);
+      kantts_lds16(Ks + j * AT_LD, kk);
+      const float p = expf(kantts_dot16(q, kk) * a.scale - lse);
+      const float dp = kantts_dot16l(go, Vs + j * AT_LD) * drop.scale(rng_row + j);
       const float ds = p * (dp - D) * a.scale;
 #pragma unroll
       for (int d = 0; d < DH; ++d) dq[d] = fmaf(ds, kk[d], dq[d]);
@@ -411,11 +373,11 @@ __device__ __forceinline__ void attn_bwd_dq_lds_body(const AttnArgs& a, const in
     float* dst = a.dq + row * a.lddq + h * DH;
     if (a.accumulate_dq) {
       float old[DH];
-      load16(dst, old);
+      kantts_load16(dst, old);
 #pragma unroll
       for (int d = 0; d < DH; ++d) dq[d] += old[d];
     }
-    store16(dst, dq);
+    kantts_store16(dst, dq);
   }
 }
 
@@ -429,8 +391,8 @@ __device__ __forceinline__ void attn_bwd_dkv_lds_body(const AttnArgs& a, const i
   float kk0[DH], vv0[DH];
   {
     const long long r0 = (long long)b * a.L + min((int)threadIdx.x, a.L - 1);
-    load16(a.k + r0 * a.ldk + h * DH, kk0);
-    load16(a.v + r0 * a.ldv + h * DH, vv0);
+    kantts_load16(a.k + r0 * a.ldk + h * DH, kk0);
+    kantts_load16(a.v + r0 * a.ldv + h * DH, vv0);
   }
   stage_rows(a.q + (long long)b * a.L * a.ldq + h * DH, a.ldq, a.L, Qs);
   stage_rows(a.d_o + (long long)b * a.L * a.lddo + h * DH, a.lddo, a.L, Gs);
@@ -439,13 +401,14 @@ __device__ __forceinline__ void attn_bwd_dkv_lds_body(const AttnArgs& a, const i
     Ls[i] = a.lse[sbase + i];
     const long long row = (long long)b * a.L + i;
     float go[DH], oo[DH];
-    load16(a.d_o + row * a.lddo + h * DH, go);
-    load16(a.o + row * a.ldo + h * DH, oo);
-    Ds[i] = dot16(go, oo);
+    kantts_load16(a.d_o + row * a.lddo + h * DH, go);
+    kantts_load16(a.o + row * a.ldo + h * DH, oo);
+    Ds[i] = kantts_dot16(go, oo);
   }
   __syncthreads();
   const int len = a.lens ? a.lens[b] : a.L;
   const int bw = a.bw_dev ? *a.bw_dev : a.bw;
+  // (written out: through kantts_seed_offset the compiler inverts this test in attn_multi_lds_kernel)
   const uint64_t seed = a.seed + (a.seed_dev ? *a.seed_dev : 0ull);
   for (int j = threadIdx.x; j < a.L; j += AT_THREADS) {
     const long long krow = (long long)b * a.L + j;
@@ -457,8 +420,8 @@ __device__ __forceinline__ void attn_bwd_dkv_lds_body(const AttnArgs& a, const i
         vv[d] = vv0[d];
       }
     } else {
-      load16(a.k + krow * a.ldk + h * DH, kk);
-      load16(a.v + krow * a.ldv + h * DH, vv);
+      kantts_load16(a.k + krow * a.ldk + h * DH, kk);
+      kantts_load16(a.v + krow * a.ldv + h * DH, vv);
     }
 #pragma unroll
     for (int d = 0; d < DH; ++d) {
@@ -482,13 +445,13 @@ __device__ __forceinline__ void attn_bwd_dkv_lds_body(const AttnArgs& a, const i
         key_range(a.mode, i, len, a.L, bw, lo, hi);
         if (j < lo || j > hi) continue;
         float q[DH], go[DH];
-        lds16(Qs + i * AT_LD, q);
-        lds16(Gs + i * AT_LD, go);
-        const float p = expf(dot16(q, kk) * a.scale - Ls[i]);
+        kantts_lds16(Qs + i * AT_LD, q);
+        kantts_lds16(Gs + i * AT_LD, go);
+        const float p = expf(kantts_dot16(q, kk) * a.scale - Ls[i]);
         const float dsc =
             kantts_dropout_scale(a.drop_p, seed, ((((uint64_t)h * a.B + b) * a.L + i) * (uint64_t)a.L) + j);
         const float pd = p * dsc;
-        const float dp = dot16(go, vv) * dsc;
+        const float dp = kantts_dot16(go, vv) * dsc;
         const float ds = p * (dp - Ds[i]) * a.scale;
 #pragma unroll
         for (int d = 0; d < DH; ++d) {
@@ -497,8 +460,8 @@ __device__ __forceinline__ void attn_bwd_dkv_lds_body(const AttnArgs& a, const i
         }
       }
     }
-    store16(a.dk + krow * a.lddk + h * DH, dk);
-    store16(a.dv + krow * a.lddv + h * DH, dv);
+    kantts_store16(a.dk + krow * a.lddk + h * DH, dk);
+    kantts_store16(a.dv + krow * a.lddv + h * DH, dv);
   }
 }
 
@@ -532,12 +495,12 @@ __device__ __forceinline__ void attn_fwd_lds_quad_body(const AttnArgs& a, const 
   float* Vs = sm + a.L * AT_LD;
   const int part = threadIdx.x & (AT_P - 1), iq = threadIdx.x >> 2;
   float q0[DH];
-  load16(a.q + ((long long)b * a.L + min(iq, a.L - 1)) * a.ldq + h * DH, q0);
+  kantts_load16(a.q + ((long long)b * a.L + min(iq, a.L - 1)) * a.ldq + h * DH, q0);
   stage_rows(a.k + (long long)b * a.L * a.ldk + h * DH, a.ldk, a.L, Ks);
   stage_rows(a.v + (long long)b * a.L * a.ldv + h * DH, a.ldv, a.L, Vs);
   __syncthreads();
   const int len = a.lens ? a.lens[b] : a.L;
-  const uint64_t seed = a.seed + (a.seed_dev ? *a.seed_dev : 0ull);
+  const uint64_t seed = a.seed + kantts_seed_offset(a.seed_dev);
   const int hi = len - 1;  // mode 0: keys [0, len - 1] for every query
   const int rounds = (a.L + AT_QPR - 1) / AT_QPR;
   for (int r = 0; r < rounds; ++r) {  // all four lanes of a group run every round (DPP needs them), stores are guarded
@@ -549,24 +512,24 @@ __device__ __forceinline__ void attn_fwd_lds_quad_body(const AttnArgs& a, const 
 #pragma unroll
       for (int d = 0; d < DH; ++d) q[d] = q0[d];
     } else {
-      load16(a.q + row * a.ldq + h * DH, q);
+      kantts_load16(a.q + row * a.ldq + h * DH, q);
     }
 #pragma unroll
     for (int d = 0; d < DH; ++d) o[d] = 0.f;
     float m = -INFINITY;
     for (int jb = part; jb * 4 <= hi; jb += AT_P)
-      for (int j = jb * 4; j <= min(hi, jb * 4 + 3); ++j) m = fmaxf(m, dot16l(q, Ks + j * AT_LD) * a.scale);
+      for (int j = jb * 4; j <= min(hi, jb * 4 + 3); ++j) m = fmaxf(m, kantts_dot16l(q, Ks + j * AT_LD) * a.scale);
     m = at_quad_max(m);
     float l = 0.f;
     const uint64_t rng_row = (((uint64_t)h * a.B + b) * a.L + min(i, a.L - 1)) * (uint64_t)a.L;
     KanttsDropSeq drop(a.drop_p, seed);
     for (int jb = part; jb * 4 <= hi; jb += AT_P)
       for (int j = jb * 4; j <= min(hi, jb * 4 + 3); ++j) {
-        const float e = expf(dot16l(q, Ks + j * AT_LD) * a.scale - m);
+        const float e = expf(kantts_dot16l(q, Ks + j * AT_LD) * a.scale - m);
         l += e;
         const float ed = e * drop.scale(rng_row + j);
         float vv[DH];
-      lds16(Vs + j * AT_LD, vv);
+      kantts_lds16(Vs + j * AT_LD, vv);
 #pragma unroll
         for (int d = 0; d < DH; ++d) o[d] = fmaf(ed, vv[d], o[d]);
       }
@@ -587,7 +550,7 @@ __device__ __forceinline__ void attn_fwd_lds_quad_body(const AttnArgs& a, const 
         float* prow = a.probs + (((long long)h * a.B + b) * a.L + i) * a.L;
         for (int j = part; j < a.L; j += AT_P) {
           float p = 0.f;
-          if (j <= hi) p = expf(dot16l(q, Ks + j * AT_LD) * a.scale - m) * inv * kantts_dropout_scale(a.drop_p, seed, rng_row + j);
+          if (j <= hi) p = expf(kantts_dot16l(q, Ks + j * AT_LD) * a.scale - m) * inv * kantts_dropout_scale(a.drop_p, seed, rng_row + j);
           prow[j] = p;
         }
       }
@@ -602,15 +565,15 @@ __device__ __forceinline__ void attn_bwd_dq_lds_quad_body(const AttnArgs& a, con
   float q0[DH], go0[DH], oo0[DH];
   {
     const long long r0 = (long long)b * a.L + min(iq, a.L - 1);
-    load16(a.q + r0 * a.ldq + h * DH, q0);
-    load16(a.d_o + r0 * a.lddo + h * DH, go0);
-    load16(a.o + r0 * a.ldo + h * DH, oo0);
+    kantts_load16(a.q + r0 * a.ldq + h * DH, q0);
+    kantts_load16(a.d_o + r0 * a.lddo + h * DH, go0);
+    kantts_load16(a.o + r0 * a.ldo + h * DH, oo0);
   }
   stage_rows(a.k + (long long)b * a.L * a.ldk + h * DH, a.ldk, a.L, Ks);
   stage_rows(a.v + (long long)b * a.L * a.ldv + h * DH, a.ldv, a.L, Vs);
   __syncthreads();
   const int len = a.lens ? a.lens[b] : a.L;
-  const uint64_t seed = a.seed + (a.seed_dev ? *a.seed_dev : 0ull);
+  const uint64_t seed = a.seed + kantts_seed_offset(a.seed_dev);
   const int hi = len - 1;
   const int rounds = (a.L + AT_QPR - 1) / AT_QPR;
   for (int r = 0; r < rounds; ++r) {
@@ -626,11 +589,11 @@ __device__ __forceinline__ void attn_bwd_dq_lds_quad_body(const AttnArgs& a, con
         oo[d] = oo0[d];
       }
     } else {
-      load16(a.q + row * a.ldq + h * DH, q);
-      load16(a.d_o + row * a.lddo + h * DH, go);
-      load16(a.o + row * a.ldo + h * DH, oo);
+      kantts_load16(a.q + row * a.ldq + h * DH, q);
+      kantts_load16(a.d_o + row * a.lddo + h * DH, go);
+      kantts_load16(a.o + row * a.ldo + h * DH, oo);
     }
-    const float D = dot16(go, oo);
+    const float D = kantts_dot16(go, oo);
     const long long sidx = ((long long)b * a.H + h) * a.L + min(i, a.L - 1);
     const float lse = a.lse[sidx];
     if (a.dvec && live && part == 0) a.dvec[sidx] = D;
@@ -641,9 +604,9 @@ __device__ __forceinline__ void attn_bwd_dq_lds_quad_body(const AttnArgs& a, con
     for (int jb = part; jb * 4 <= hi; jb += AT_P)
       for (int j = jb * 4; j <= min(hi, jb * 4 + 3); ++j) {
         float kk[DH];
-        lds16(Ks + j * AT_LD, kk);
-        const float p = expf(dot16(q, kk) * a.scale - lse);
-        const float dp = dot16l(go, Vs + j * AT_LD) * drop.scale(rng_row + j);
+        kantts_lds16(Ks + j * AT_LD, kk);
+        const float p = expf(kantts_dot16(q, kk) * a.scale - lse);
+        const float dp = kantts_dot16l(go, Vs + j * AT_LD) * drop.scale(rng_row + j);
         const float ds = p * (dp - D) * a.scale;
 #pragma unroll
         for (int d = 0; d < DH; ++d) dq[d] = fmaf(ds, kk[d], dq[d]);
@@ -676,8 +639,8 @@ __device__ __forceinline__ void attn_bwd_dkv_lds_quad_body(const AttnArgs& a, co
   float kk0[DH], vv0[DH];
   {
     const long long r0 = (long long)b * a.L + min(jq, a.L - 1);
-    load16(a.k + r0 * a.ldk + h * DH, kk0);
-    load16(a.v + r0 * a.ldv + h * DH, vv0);
+    kantts_load16(a.k + r0 * a.ldk + h * DH, kk0);
+    kantts_load16(a.v + r0 * a.ldv + h * DH, vv0);
   }
   stage_rows(a.q + (long long)b * a.L * a.ldq + h * DH, a.ldq, a.L, Qs);
   stage_rows(a.d_o + (long long)b * a.L * a.lddo + h * DH, a.lddo, a.L, Gs);
@@ -686,13 +649,13 @@ __device__ __forceinline__ void attn_bwd_dkv_lds_quad_body(const AttnArgs& a, co
     Ls[i] = a.lse[sbase + i];
     const long long row = (long long)b * a.L + i;
     float go[DH], oo[DH];
-    load16(a.d_o + row * a.lddo + h * DH, go);
-    load16(a.o + row * a.ldo + h * DH, oo);
-    Ds[i] = dot16(go, oo);
+    kantts_load16(a.d_o + row * a.lddo + h * DH, go);
+    kantts_load16(a.o + row * a.ldo + h * DH, oo);
+    Ds[i] = kantts_dot16(go, oo);
   }
   __syncthreads();
   const int len = a.lens ? a.lens[b] : a.L;
-  const uint64_t seed = a.seed + (a.seed_dev ? *a.seed_dev : 0ull);
+  const uint64_t seed = a.seed + (a.seed_dev ? *a.seed_dev : 0ull);  // written out, as in attn_bwd_dkv_lds_body
   const int rounds = (a.L + AT_QPR - 1) / AT_QPR;
   for (int r = 0; r < rounds; ++r) {
     const int j = r * AT_QPR + jq;
@@ -706,8 +669,8 @@ __device__ __forceinline__ void attn_bwd_dkv_lds_quad_body(const AttnArgs& a, co
         vv[d] = vv0[d];
       }
     } else {
-      load16(a.k + krow * a.ldk + h * DH, kk);
-      load16(a.v + krow * a.ldv + h * DH, vv);
+      kantts_load16(a.k + krow * a.ldk + h * DH, kk);
+      kantts_load16(a.v + krow * a.ldv + h * DH, vv);
     }
 #pragma unroll
     for (int d = 0; d < DH; ++d) {
@@ -718,13 +681,13 @@ __device__ __forceinline__ void attn_bwd_dkv_lds_quad_body(const AttnArgs& a, co
     if (live && j <= len - 1) {
       for (int i = part; i < a.L; i += AT_P) {
         float q[DH], go[DH];
-        lds16(Qs + i * AT_LD, q);
-        lds16(Gs + i * AT_LD, go);
-        const float p = expf(dot16(q, kk) * a.scale - Ls[i]);
+        kantts_lds16(Qs + i * AT_LD, q);
+        kantts_lds16(Gs + i * AT_LD, go);
+        const float p = expf(kantts_dot16(q, kk) * a.scale - Ls[i]);
         const float dsc =
             kantts_dropout_scale(a.drop_p, seed, ((((uint64_t)h * a.B + b) * a.L + i) * (uint64_t)a.L) + j);
         const float pd = p * dsc;
-        const float dp = dot16(go, vv) * dsc;
+        const float dp = kantts_dot16(go, vv) * dsc;
         const float ds = p * (dp - Ds[i]) * a.scale;
 #pragma unroll
         for (int d = 0; d < DH; ++d) {
@@ -766,12 +729,12 @@ __device__ __forceinline__ void attn_bwd_dq2_lds_body(const AttnArgs& ax, const 
   float* Ks = sm;
   float* Vs = sm + L * AT_LD;
   const int len = ax.lens ? ax.lens[b] : L;
-  const uint64_t seed_off = ax.seed_dev ? *ax.seed_dev : 0ull;
+  const uint64_t seed_off = kantts_seed_offset(ax.seed_dev);
   const int i = threadIdx.x;  // L <= 256 for the role (checked by the launcher): one query per thread, kept across bands
   const bool live = i < L;
   const long long row = (long long)b * L + min(i, L - 1);
   float q[DH], dq[DH];
-  load16(ax.q + row * ax.ldq + h * DH, q);
+  kantts_load16(ax.q + row * ax.ldq + h * DH, q);
 #pragma unroll
   for (int d = 0; d < DH; ++d) dq[d] = 0.f;
   const long long sidx = ((long long)b * ax.H + h) * L + min(i, L - 1);
@@ -780,8 +743,8 @@ __device__ __forceinline__ void attn_bwd_dq2_lds_body(const AttnArgs& ax, const 
   for (int band = 0; band < 2; ++band) {
     const AttnArgs& a = band ? ah : ax;
     float go[DH], oo[DH];
-    load16(a.d_o + row * a.lddo + h * DH, go);
-    load16(a.o + row * a.ldo + h * DH, oo);
+    kantts_load16(a.d_o + row * a.lddo + h * DH, go);
+    kantts_load16(a.o + row * a.ldo + h * DH, oo);
     const float lse = a.lse[sidx];
     if (band) __syncthreads();  // every thread is done with the x band's images
     stage_rows(a.k + (long long)b * L * a.ldk + h * DH, a.ldk, L, Ks);
@@ -791,19 +754,19 @@ __device__ __forceinline__ void attn_bwd_dq2_lds_body(const AttnArgs& ax, const 
     int lo, hi;
     key_range(a.mode, min(i, L - 1), len, L, bw, lo, hi);
     if (!live || i >= len) hi = lo - 1;  // padded query rows carry no gradient
-    const float D = dot16(go, oo);
+    const float D = kantts_dot16(go, oo);
     KanttsDropSeq drop(a.drop_p, a.seed + seed_off);
     for (int j = lo; j <= hi; ++j) {
       float kk[DH];
-      lds16(Ks + j * AT_LD, kk);
-      const float p = expf(dot16(q, kk) * a.scale - lse);
-      const float dp = dot16l(go, Vs + j * AT_LD) * drop.scale(rng_row + j);
+      kantts_lds16(Ks + j * AT_LD, kk);
+      const float p = expf(kantts_dot16(q, kk) * a.scale - lse);
+      const float dp = kantts_dot16l(go, Vs + j * AT_LD) * drop.scale(rng_row + j);
       const float ds = p * (dp - D) * a.scale;
 #pragma unroll
       for (int d = 0; d < DH; ++d) dq[d] = fmaf(ds, kk[d], dq[d]);
     }
   }
-  if (live) store16(ax.dq + row * ax.lddq + h * DH, dq);
+  if (live) kantts_store16(ax.dq + row * ax.lddq + h * DH, dq);
 }
 
 // Up to four attention passes over the same (B, H) grid as ONE launch: blockIdx.z picks the pass.  A PNCA block's
@@ -1075,7 +1038,7 @@ __global__ __launch_bounds__(128) void attn_decode_kernel(const AttnArgs a, int 
   key_range(a.mode, step, len, a.L, bw_seq ? bw_seq[b] : a.bw, lo, hi);
   if (a.mode != 0 && step >= len) hi = lo - 1;  // padded query: context 0 (as in the training kernels)
   float q[DH], o[DH];
-  load16(a.q + (long long)b * a.ldq + h * DH, q);
+  kantts_load16(a.q + (long long)b * a.ldq + h * DH, q);
 #pragma unroll
   for (int d = 0; d < DH; ++d) o[d] = 0.f;
   const float* kb = a.k + (long long)b * a.L * a.ldk + h * DH;
@@ -1083,15 +1046,15 @@ __global__ __launch_bounds__(128) void attn_decode_kernel(const AttnArgs a, int 
   float m = -INFINITY;
   for (int j = lo; j <= hi; ++j) {
     float kk[DH];
-    load16(kb + (long long)j * a.ldk, kk);
-    m = fmaxf(m, dot16(q, kk) * a.scale);
+    kantts_load16(kb + (long long)j * a.ldk, kk);
+    m = fmaxf(m, kantts_dot16(q, kk) * a.scale);
   }
   float l = 0.f;
   for (int j = lo; j <= hi; ++j) {
     float kk[DH], vv[DH];
-    load16(kb + (long long)j * a.ldk, kk);
-    load16(vb + (long long)j * a.ldv, vv);
-    const float e = expf(dot16(q, kk) * a.scale - m);
+    kantts_load16(kb + (long long)j * a.ldk, kk);
+    kantts_load16(vb + (long long)j * a.ldv, vv);
+    const float e = expf(kantts_dot16(q, kk) * a.scale - m);
     l += e;
 #pragma unroll
     for (int d = 0; d < DH; ++d) o[d] = fmaf(e, vv[d], o[d]);
@@ -1099,7 +1062,7 @@ __global__ __launch_bounds__(128) void attn_decode_kernel(const AttnArgs a, int 
   const float inv = (hi >= lo) ? 1.f / l : 0.f;
 #pragma unroll
   for (int d = 0; d < DH; ++d) o[d] *= inv;
-  store16(a.o + (long long)b * a.ldo + h * DH, o);
+  kantts_store16(a.o + (long long)b * a.ldo + h * DH, o);
 }
 
 extern "C" int kantts_attn_decode(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, float* o,

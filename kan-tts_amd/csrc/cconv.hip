@@ -30,15 +30,8 @@
 
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 typedef __attribute__((address_space(3))) void cc_lds_void;
 typedef __attribute__((address_space(1))) const void cc_gl_void;
-typedef __attribute__((address_space(3))) bf16x4 cc_lds_bf16x4;
 
 #define CC_THREADS 256
 #define CC_MAXPH 8
@@ -53,18 +46,13 @@ template <int N>
 __device__ __forceinline__ void cc_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
 }
+// (not kantts_lds_barrier: the LDS wait is already part of cc_wait_vm, so this is the bare s_barrier)
 __device__ __forceinline__ void cc_barrier() {
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 }
-__device__ __forceinline__ unsigned cc_pack2(float a, float b) {
-  bf16x4 t = {(__bf16)a, (__bf16)b, (__bf16)0.f, (__bf16)0.f};
-  return ((u32x2&)t).x;
-}
-__device__ __forceinline__ float cc_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float cc_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 __device__ __forceinline__ bf16x4 cc_tr4(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((cc_lds_bf16x4*)(p));
+  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((kantts_lds_bf16x4*)(p));
 }
 
 struct CcPhase {
@@ -107,9 +95,7 @@ __global__ __launch_bounds__(CC_THREADS) void cconv_kernel(const CcArgs P) {
     // (with a single n tile the band order -- neighbouring row tiles behind one L2 for their shared tap rows -- was measured
     // and is slower: GAN step 27.03 against 26.81 ms, profiles/r06_runGX_cconv_band_single_n_tile_ab.log)
     if (total >= 64 && gx > 1) {
-      const int L = by * gx + bx, k = L & 7, j = L >> 3;
-      const int q = total >> 3, r = total & 7;
-      const int vid = k * q + (k < r ? k : r) + j;
+      const int vid = kantts_xcd_slot(total, by * gx + bx);
       by = vid / gx;
       bx = vid - by * gx;
     }
@@ -307,8 +293,8 @@ __global__ __launch_bounds__(CC_THREADS) void cconv_kernel(const CcArgs P) {
       float gv[8];
       if (g.out_gate_bf16) {
         const u32x4 q = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(g.out_gate) + o);
-        gv[0] = cc_lo(q.x); gv[1] = cc_hi(q.x); gv[2] = cc_lo(q.y); gv[3] = cc_hi(q.y);
-        gv[4] = cc_lo(q.z); gv[5] = cc_hi(q.z); gv[6] = cc_lo(q.w); gv[7] = cc_hi(q.w);
+        gv[0] = kantts_bf16_lo(q.x); gv[1] = kantts_bf16_hi(q.x); gv[2] = kantts_bf16_lo(q.y); gv[3] = kantts_bf16_hi(q.y);
+        gv[4] = kantts_bf16_lo(q.z); gv[5] = kantts_bf16_hi(q.z); gv[6] = kantts_bf16_lo(q.w); gv[7] = kantts_bf16_hi(q.w);
       } else {
         const float* gp = reinterpret_cast<const float*>(g.out_gate) + o;
         const float4 q0 = *reinterpret_cast<const float4*>(gp), q1 = *reinterpret_cast<const float4*>(gp + 4);
@@ -331,7 +317,7 @@ __global__ __launch_bounds__(CC_THREADS) void cconv_kernel(const CcArgs P) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * g.bf_slope;
       }
-      u32x4 w = {cc_pack2(v[0], v[1]), cc_pack2(v[2], v[3]), cc_pack2(v[4], v[5]), cc_pack2(v[6], v[7])};
+      u32x4 w = {kantts_pack2_of4(v[0], v[1]), kantts_pack2_of4(v[2], v[3]), kantts_pack2_of4(v[4], v[5]), kantts_pack2_of4(v[6], v[7])};
       *reinterpret_cast<u32x4*>(reinterpret_cast<__bf16*>(g.out_bf) + o) = w;
     }
   }
@@ -344,13 +330,7 @@ static int cc_launch(const CcArgs& P, hipStream_t st) {
   constexpr int MAIN_BYTES = (NSTAGE * STAGE > EPI_BYTES) ? NSTAGE * STAGE : EPI_BYTES;
   constexpr size_t LDS = MAIN_BYTES + BM * 20;
   static_assert(LDS <= 160 * 1024, "LDS");
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cconv_kernel<BM, BN, WM, WN, NSTAGE>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (int e = kantts_allow_dynamic_lds<&cconv_kernel<BM, BN, WM, WN, NSTAGE>>((int)LDS)) return e;
   const kantts_cconv_args& g = P.a;
   const long long mrows = (long long)((g.Tdst + g.phases - 1) / g.phases) * g.inner;
   const int ntpg = (g.NG + BN - 1) / BN;
@@ -533,8 +513,8 @@ __global__ __launch_bounds__(CC_THREADS) void cconv_narrow_kernel(const CnArgs P
       float gv[8];
       if (g.out_gate_bf16) {
         const u32x4 q = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(g.out_gate) + o);
-        gv[0] = cc_lo(q.x); gv[1] = cc_hi(q.x); gv[2] = cc_lo(q.y); gv[3] = cc_hi(q.y);
-        gv[4] = cc_lo(q.z); gv[5] = cc_hi(q.z); gv[6] = cc_lo(q.w); gv[7] = cc_hi(q.w);
+        gv[0] = kantts_bf16_lo(q.x); gv[1] = kantts_bf16_hi(q.x); gv[2] = kantts_bf16_lo(q.y); gv[3] = kantts_bf16_hi(q.y);
+        gv[4] = kantts_bf16_lo(q.z); gv[5] = kantts_bf16_hi(q.z); gv[6] = kantts_bf16_lo(q.w); gv[7] = kantts_bf16_hi(q.w);
       } else {
         const float* gp = reinterpret_cast<const float*>(g.out_gate) + o;
         const float4 q0 = *reinterpret_cast<const float4*>(gp), q1 = *reinterpret_cast<const float4*>(gp + 4);
@@ -557,7 +537,7 @@ __global__ __launch_bounds__(CC_THREADS) void cconv_narrow_kernel(const CnArgs P
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * g.bf_slope;
       }
-      u32x4 w = {cc_pack2(v[0], v[1]), cc_pack2(v[2], v[3]), cc_pack2(v[4], v[5]), cc_pack2(v[6], v[7])};
+      u32x4 w = {kantts_pack2_of4(v[0], v[1]), kantts_pack2_of4(v[2], v[3]), kantts_pack2_of4(v[4], v[5]), kantts_pack2_of4(v[6], v[7])};
       *reinterpret_cast<u32x4*>(reinterpret_cast<__bf16*>(g.out_bf) + o) = w;
     }
   }
@@ -578,13 +558,7 @@ static int cn_launch(CnArgs& P, int span, hipStream_t st) {
   const size_t epi = (size_t)BM * (BN + 4) * 4;
   if (lds < epi) lds = epi;
   if (lds > 72 * 1024) return KANTTS_E_UNSUPPORTED;  // (two workgroups per CU)
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cconv_narrow_kernel<BM, BN, CP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (int e = kantts_allow_dynamic_lds<&cconv_narrow_kernel<BM, BN, CP>>(72 * 1024)) return e;
   const int mrows = (g.Tdst + g.phases - 1) / g.phases;
   const int ntpg = (g.NG + BN - 1) / BN;
   if ((long long)g.B * g.phases > 65535) return KANTTS_E_UNSUPPORTED;
@@ -593,7 +567,6 @@ static int cn_launch(CnArgs& P, int span, hipStream_t st) {
   KANTTS_CHECK_LAUNCH();
 }
 
-static bool cc_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static int cc_floordiv(int a, int b) {
   int q = a / b;
   if ((a % b != 0) && ((a < 0) != (b < 0))) --q;
@@ -619,8 +592,8 @@ extern "C" int kantts_cconv_launch(const kantts_cconv_args* ap, void* stream) {
   if (g.Ntot != g.groups * g.NG || g.Cin_tot != g.groups * g.CR) return KANTTS_E_BADARG;
   if (g.B == 0 || g.Tdst == 0) return KANTTS_OK;
   if ((g.CR & 7) || (g.NG & 7) || g.K > 64 || g.phases > CC_MAXPH) return KANTTS_E_UNSUPPORTED;
-  if (!cc_aligned16(g.in) || !cc_aligned16(g.w) || (g.bias && !cc_aligned16(g.bias)) || (g.res && !cc_aligned16(g.res)) ||
-      (g.out_gate && !cc_aligned16(g.out_gate)) || (g.out && !cc_aligned16(g.out)) || (g.out_bf && !cc_aligned16(g.out_bf)))
+  if (!kantts_aligned16(g.in) || !kantts_aligned16(g.w) || (g.bias && !kantts_aligned16(g.bias)) || (g.res && !kantts_aligned16(g.res)) ||
+      (g.out_gate && !kantts_aligned16(g.out_gate)) || (g.out && !kantts_aligned16(g.out)) || (g.out_bf && !kantts_aligned16(g.out_bf)))
     return KANTTS_E_UNSUPPORTED;
   const int up = g.up > 1 ? g.up : 1;
   // 32-bit element offsets inside one batch item / one weight image; mulhi division needs tokens < 2^31 / up
@@ -1013,13 +986,7 @@ static int cw_launch2(const CwArgs& P, hipStream_t st) {
   constexpr int STAGE = 2 * 64 * TW * 2;
   constexpr int EPI_BYTES = TW * (TW + 4) * 4;
   constexpr size_t LDS = (NSTAGE * STAGE > EPI_BYTES) ? NSTAGE * STAGE : EPI_BYTES;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cconv_wgrad_kernel<TW, NSTAGE>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (int e = kantts_allow_dynamic_lds<&cconv_wgrad_kernel<TW, NSTAGE>>((int)LDS)) return e;
   const kantts_cconvw_args& g = P.a;
   dim3 grid((g.CR + TW - 1) / TW, g.groups * ((g.NG + TW - 1) / TW), g.K * P.slices);
   if (P.xcd_map) grid = dim3(8u * grid.x * grid.y * (unsigned)g.K * (unsigned)kantts_cdiv(P.slices, 8), 1, 1);
@@ -1215,13 +1182,7 @@ static int ct_launch(const CtArgs& P, hipStream_t st) {
   const kantts_cconvw_args& g = P.a;
   const size_t LDS = 2 * (size_t)(P.rs * 64 * NF * 32 + P.ncp * 4096);
   if (LDS > 150 * 1024) return KANTTS_E_UNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cconv_wgrad_taps_kernel<NF, CF, TPW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (int e = kantts_allow_dynamic_lds<&cconv_wgrad_taps_kernel<NF, CF, TPW>>(150 * 1024)) return e;
   dim3 grid(kantts_cdiv(g.K, 4 * TPW), g.groups, P.slices);
   hipLaunchKernelGGL((cconv_wgrad_taps_kernel<NF, CF, TPW>), grid, dim3(CC_THREADS), LDS, st, P);
   if (P.to_ws) {
@@ -1320,7 +1281,7 @@ extern "C" int kantts_cconv_wgrad_launch(const kantts_cconvw_args* ap, void* str
     return KANTTS_E_BADARG;
   if (g.Ntot != g.groups * g.NG || g.Cin_tot != g.groups * g.CR) return KANTTS_E_BADARG;
   if (g.B == 0 || g.Tdst == 0) return KANTTS_OK;
-  if ((g.CR & 7) || (g.NG & 7) || !cc_aligned16(g.x) || !cc_aligned16(g.dy) || !cc_aligned16(g.dw)) return KANTTS_E_UNSUPPORTED;
+  if ((g.CR & 7) || (g.NG & 7) || !kantts_aligned16(g.x) || !kantts_aligned16(g.dy) || !kantts_aligned16(g.dw)) return KANTTS_E_UNSUPPORTED;
   const int up = g.up > 1 ? g.up : 1;
   if (up > 64 || (long long)g.Tsrc * up * up >= (1ll << 31) || (long long)g.B * g.Tsrc * g.inner >= (1ll << 30) ||
       (long long)g.B * g.Tdst * g.inner >= (1ll << 30) || g.inner > 64)
@@ -1332,7 +1293,7 @@ extern "C" int kantts_cconv_wgrad_launch(const kantts_cconvw_args* ap, void* str
     int slices = ct_slices(g, g.workspace != nullptr);
     bool ws = false;
     if (slices > 1 && g.workspace) {
-      if (g.ws_floats >= (long long)slices * g.K * g.Ntot * g.CR && cc_aligned16(g.workspace))
+      if (g.ws_floats >= (long long)slices * g.K * g.Ntot * g.CR && kantts_aligned16(g.workspace))
         ws = true;
       else
         slices = ct_slices(g, false);
@@ -1374,7 +1335,7 @@ extern "C" int kantts_cconv_wgrad_launch(const kantts_cconvw_args* ap, void* str
   int slices = cw_slices(g, g.workspace != nullptr);
   bool to_ws = false;
   if (slices > 1 && g.workspace) {
-    if (g.ws_floats >= (long long)slices * g.K * g.Ntot * g.CR && cc_aligned16(g.workspace))
+    if (g.ws_floats >= (long long)slices * g.K * g.Ntot * g.CR && kantts_aligned16(g.workspace))
       to_ws = true;
     else
       slices = cw_slices(g, false);
@@ -1407,8 +1368,8 @@ __global__ __launch_bounds__(256) void act_cast_kernel(const float* __restrict__
     float q[8];
     if (GATE_BF16) {
       const u32x4 t = reinterpret_cast<const u32x4*>(gate)[i];
-      q[0] = cc_lo(t.x); q[1] = cc_hi(t.x); q[2] = cc_lo(t.y); q[3] = cc_hi(t.y);
-      q[4] = cc_lo(t.z); q[5] = cc_hi(t.z); q[6] = cc_lo(t.w); q[7] = cc_hi(t.w);
+      q[0] = kantts_bf16_lo(t.x); q[1] = kantts_bf16_hi(t.x); q[2] = kantts_bf16_lo(t.y); q[3] = kantts_bf16_hi(t.y);
+      q[4] = kantts_bf16_lo(t.z); q[5] = kantts_bf16_hi(t.z); q[6] = kantts_bf16_lo(t.w); q[7] = kantts_bf16_hi(t.w);
     } else {
       const float4 t0 = reinterpret_cast<const float4*>(gate)[2 * i], t1 = reinterpret_cast<const float4*>(gate)[2 * i + 1];
       q[0] = t0.x; q[1] = t0.y; q[2] = t0.z; q[3] = t0.w; q[4] = t1.x; q[5] = t1.y; q[6] = t1.z; q[7] = t1.w;
@@ -1419,13 +1380,13 @@ __global__ __launch_bounds__(256) void act_cast_kernel(const float* __restrict__
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * slope;
   }
-  u32x4 w = {cc_pack2(v[0], v[1]), cc_pack2(v[2], v[3]), cc_pack2(v[4], v[5]), cc_pack2(v[6], v[7])};
+  u32x4 w = {kantts_pack2_of4(v[0], v[1]), kantts_pack2_of4(v[2], v[3]), kantts_pack2_of4(v[4], v[5]), kantts_pack2_of4(v[6], v[7])};
   reinterpret_cast<u32x4*>(dst)[i] = w;
 }
 
 extern "C" int kantts_act_cast_bf16(const float* src, const void* gate, int gate_bf16, void* dst, int act, float slope,
                                     long long n, void* stream) {
-  if (!src || !dst || n < 0 || (n & 7) || !cc_aligned16(src) || !cc_aligned16(dst) || (gate && !cc_aligned16(gate)))
+  if (!src || !dst || n < 0 || (n & 7) || !kantts_aligned16(src) || !kantts_aligned16(dst) || (gate && !kantts_aligned16(gate)))
     return KANTTS_E_BADARG;
   if (n == 0) return KANTTS_OK;
   const long long n8 = n / 8;

@@ -30,6 +30,8 @@
 
 static inline int kantts_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+#include "prims.h"
+
 // ---------------------------------------------------------------------------------------------
 // Counter-based RNG for dropout.  The same (seed, element) pair is re-evaluated in backward, so masks are never stored.
 // One 64-bit hash (two rounds of a "splitmix" finaliser) serves FOUR consecutive elements, 16 bits each (round 2: the

@@ -24,7 +24,6 @@ extern std::atomic<int> kantts_tune_c1_wgrad_wgs;  // csrc/gemm_bf16.hip: kantts
 
 __device__ __forceinline__ float c1_gate(float d, float y, float slope) { return d * ((y > 0.f) ? 1.f : slope); }
 
-typedef __bf16 c1_bf16x4 __attribute__((ext_vector_type(4)));
 // ------------------------------------------------------------------------------------------- forward
 __global__ __launch_bounds__(C1_THREADS) void conv_c1_fwd_kernel(const kantts_conv_c1_args g) {
   extern __shared__ __attribute__((aligned(16))) float c1_lds[];
@@ -72,8 +71,8 @@ __global__ __launch_bounds__(C1_THREADS) void conv_c1_fwd_kernel(const kantts_co
     const long long o = (((long long)b * g.Tdst + q0 + ql) * g.inner + p) * g.Cout + n4;
     *reinterpret_cast<float4*>(g.y + o) = acc;
     if (g.y_bf16) {
-      c1_bf16x4 v = {(__bf16)acc.x, (__bf16)acc.y, (__bf16)acc.z, (__bf16)acc.w};
-      *reinterpret_cast<c1_bf16x4*>(reinterpret_cast<__bf16*>(g.y_bf16) + o) = v;
+      bf16x4 v = {(__bf16)acc.x, (__bf16)acc.y, (__bf16)acc.z, (__bf16)acc.w};
+      *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(g.y_bf16) + o) = v;
     }
   }
 }
@@ -191,7 +190,6 @@ __global__ __launch_bounds__(C1_THREADS) void conv_c1_wgrad_kernel(const kantts_
 //           channel permutation; P goes to LDS and every window position GATHERS its <= K terms (no LDS atomics)
 //   wgrad   dw[n][tap]    = sum_q gate(dy[q][n]) * x[q*s + tap*d - pad]   16 channels x 16 taps per accumulator over 4
 //           tokens per MFMA; element m of a lane's float4 is channel 4*li + m of its 64-channel half.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define C1_PLD 17  // pitch of the P tile
 
 template <int G16>  // Cout = 16 * G16

@@ -22,16 +22,11 @@
 
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_t;
-
 #define WG_THREADS 256
 #define WG_BQ 32  // tokens per step = one bf16 MFMA k-step
 
 __device__ __forceinline__ bf16x4 wg_read_tr4(const __bf16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(p));
+  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((kantts_lds_bf16x4*)(p));
 }
 
 template <bool BF16>
@@ -67,6 +62,7 @@ __global__ __launch_bounds__(WG_THREADS, BF16 ? 2 : 1) void conv_wgrad_kernel(co
     const int gx = gridDim.x, gy = gridDim.y;
     const long long total = (long long)gx * gy * gridDim.z;
     if (total >= 64 && total < 0x7fffffffLL && gx * gy > 1) {
+      // kantts_xcd_slot written out: `total` is 64 bits wide here and is shifted before it is narrowed
       const int L = (bz * gy + bytap) * gx + bx, k = L & 7, j = L >> 3;
       const int q = (int)(total >> 3), r = (int)(total & 7);
       const int vid = k * q + (k < r ? k : r) + j;
@@ -381,13 +377,7 @@ static int wg_launch(const kantts_convw_args& g, hipStream_t st) {
   const int Wp = kantts_cdiv(W, dm);
   const size_t lds = (size_t)WG_BQ * 80 * ESZ + (size_t)Wp * dm * PC * ESZ;
   if (lds > 150 * 1024) return KANTTS_E_UNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<BF16, CT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (int e = kantts_allow_dynamic_lds<&conv_wgrad_kernel<BF16, CT>>(150 * 1024)) return e;
   const long long total_steps = (long long)g.B * g.inner * kantts_cdiv(g.Tdst, WG_BQ);
   const long long xy = (long long)g.groups * ntn * ntc * ntg;
   // enough token slabs to fill the chip (~2048 blocks), but at least 4 steps per block to amortise the atomics ...

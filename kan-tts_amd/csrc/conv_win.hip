@@ -24,10 +24,6 @@
 
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 #define CW_THREADS 256
 #define CW_CK 32        // channels per chunk = one bf16 MFMA k-step
 #define CW_MAXTAPS 64
@@ -86,9 +82,7 @@ __global__ __launch_bounds__(CW_THREADS) void conv_win_kernel(kantts_conv_args g
   {
     const int gx = gridDim.x, total = gx * gridDim.y;
     if (total >= 64 && gx > 1) {
-      const int L = by * gx + bx, k = L & 7, j = L >> 3;
-      const int q = total >> 3, r = total & 7;
-      const int vid = k * q + (k < r ? k : r) + j;
+      const int vid = kantts_xcd_slot(total, by * gx + bx);
       by = vid / gx;
       bx = vid - by * gx;
     }
@@ -437,13 +431,7 @@ static int cw_launch(const kantts_conv_args& g, hipStream_t st) {
   if (lds < strip) lds = strip;
   lds += CW_HDR;
   if (lds > 160 * 1024 - 1024) return KANTTS_E_UNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_win_kernel<BF16, WM, MREP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (int e = kantts_allow_dynamic_lds<&conv_win_kernel<BF16, WM, MREP>>(160 * 1024 - 1024)) return e;
   const int mrows = (g.Tdst + g.phases - 1) / g.phases;
   const int ntpg = (g.NG + BN - 1) / BN;
   dim3 grid(g.groups * ntpg, kantts_cdiv((long long)mrows * g.inner, BQ), g.B * g.phases);

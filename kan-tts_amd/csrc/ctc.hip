@@ -38,8 +38,6 @@
 #define CTC_WIDE_D 8     // ... and prefetch depth (MAXS * D ring registers, as above)
 #define CTC_NEG (-1e30f)
 
-__device__ __forceinline__ void ctc_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // log(e^a + e^b + e^c).  The largest term contributes exactly 1: the sum is in [1, 3] and v_exp_f32 / v_log_f32 (1-2 ulp) on
 // arguments of that size cost ~2e-7 absolute per step -- the same size as the rounding of the running sum itself (|alpha| grows
 // to ~2000 at 612 frames: half an ulp is 6e-5).  libm's expf / logf (three + one calls of ~25 instructions on the serial path of
@@ -114,7 +112,7 @@ __device__ __forceinline__ void ctc_walk_both(const float* __restrict__ lg, int 
             if (s < NSt) rows[(long long)t * NSmax + s] = v;
           }
         }
-        ctc_barrier();
+        kantts_lds_barrier();
         float* sw = prev;
         prev = cur;
         cur = sw;
@@ -255,13 +253,8 @@ extern "C" int kantts_ctc_attn(const kantts_ctc_args* a, void* stream) {
   if (2 * a->T2 + 1 > CTC_HALF * CTC_MAXS) return KANTTS_E_UNSUPPORTED;  // more than 511 phonemes
   const size_t lds = (size_t)a->T1 * sizeof(float);
   if (lds > 96 * 1024) return KANTTS_E_UNSUPPORTED;                          // more than 24576 mel frames
-  static bool attr_set = false;
-  if (!attr_set && lds > 32 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ctc_attn_kernel<CTC_MAXS, CTC_D, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (lds > 32 * 1024)
+    if (int e = kantts_allow_dynamic_lds<&ctc_attn_kernel<CTC_MAXS, CTC_D, true>>(96 * 1024)) return e;
   hipLaunchKernelGGL((ctc_attn_kernel<CTC_MAXS, CTC_D, true>), dim3(a->B), dim3(CTC_THREADS), lds, (hipStream_t)stream, *a);
   KANTTS_CHECK_LAUNCH();
 }
@@ -276,11 +269,8 @@ extern "C" int kantts_ctc_attn_wide(const kantts_ctc_args* a, void* stream) {
   if (a->T2 > (CTC_HALF * CTC_WIDE_MAXS - 1) / 2) return KANTTS_E_UNSUPPORTED;  // more than 1023 tokens
   const size_t lds = (size_t)a->T1 * sizeof(float);
   if (lds > 96 * 1024) return KANTTS_E_UNSUPPORTED;                             // more than 24576 mel frames
-  if (lds > 16 * 1024) {  // static + dynamic beyond the 64 KB a kernel gets unasked; per launch: the attribute is per device
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ctc_attn_kernel<CTC_WIDE_MAXS, CTC_WIDE_D, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (lds > 16 * 1024)  // static + dynamic beyond the 64 KB a kernel gets unasked
+    if (int e = kantts_allow_dynamic_lds<&ctc_attn_kernel<CTC_WIDE_MAXS, CTC_WIDE_D, false>>(96 * 1024)) return e;
   hipLaunchKernelGGL((ctc_attn_kernel<CTC_WIDE_MAXS, CTC_WIDE_D, false>), dim3(a->B), dim3(CTC_THREADS), lds, (hipStream_t)stream, *a);
   {
     hipError_t e = hipGetLastError();

@@ -14,26 +14,6 @@
 
 #define DDH 16
 
-__device__ __forceinline__ void d_load16(const float* p, float* r) {
-  const float4* p4 = reinterpret_cast<const float4*>(p);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float4 t = p4[e];
-    r[4 * e + 0] = t.x; r[4 * e + 1] = t.y; r[4 * e + 2] = t.z; r[4 * e + 3] = t.w;
-  }
-}
-__device__ __forceinline__ void d_store16(float* p, const float* r) {
-  float4* p4 = reinterpret_cast<float4*>(p);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) p4[e] = make_float4(r[4 * e], r[4 * e + 1], r[4 * e + 2], r[4 * e + 3]);
-}
-__device__ __forceinline__ float d_dot16(const float* a, const float* b) {
-  float s = 0.f;
-#pragma unroll
-  for (int d = 0; d < DDH; ++d) s = fmaf(a[d], b[d], s);
-  return s;
-}
-
 // softmax(q . K[lo..hi]^T / 4) V[lo..hi] for one head; rows of the (B, L, ld) buffer, head slice at +h*16
 __device__ __forceinline__ void d_attend(const float* q, const float* kb, const float* vb, int ld, int lo, int hi, float* o) {
 #pragma unroll
@@ -41,15 +21,15 @@ __device__ __forceinline__ void d_attend(const float* q, const float* kb, const 
   float m = -INFINITY;
   for (int j = lo; j <= hi; ++j) {
     float kk[DDH];
-    d_load16(kb + (long long)j * ld, kk);
-    m = fmaxf(m, d_dot16(q, kk) * 0.25f);
+    kantts_load16(kb + (long long)j * ld, kk);
+    m = fmaxf(m, kantts_dot16(q, kk) * 0.25f);
   }
   float l = 0.f;
   for (int j = lo; j <= hi; ++j) {
     float kk[DDH], vv[DDH];
-    d_load16(kb + (long long)j * ld, kk);
-    d_load16(vb + (long long)j * ld, vv);
-    const float e = expf(d_dot16(q, kk) * 0.25f - m);
+    kantts_load16(kb + (long long)j * ld, kk);
+    kantts_load16(vb + (long long)j * ld, vv);
+    const float e = expf(kantts_dot16(q, kk) * 0.25f - m);
     l += e;
 #pragma unroll
     for (int d = 0; d < DDH; ++d) o[d] = fmaf(e, vv[d], o[d]);
@@ -74,21 +54,21 @@ __global__ __launch_bounds__(128) void pnca_decode_step_kernel(const float* __re
   const int band = bw_seq ? bw_seq[b] : bw;
   float q[DDH], k[DDH], v[DDH], o[DDH];
   const float* row = qkv + (long long)b * ldq + h * DDH;
-  d_load16(row, q);
-  d_load16(row + D, k);
-  d_load16(row + 2 * D, v);
+  kantts_load16(row, q);
+  kantts_load16(row + D, k);
+  kantts_load16(row + 2 * D, v);
   // this thread owns head h of sequence b: it appends its own slice and later reads only that slice of older rows
   float* xb = xkv + (long long)b * L * 2 * D + h * DDH;
-  d_store16(xb + (long long)step * 2 * D, k);
-  d_store16(xb + (long long)step * 2 * D + D, v);
+  kantts_store16(xb + (long long)step * 2 * D, k);
+  kantts_store16(xb + (long long)step * 2 * D + D, v);
   const bool live = step < len;  // padded query: context 0 (as in the training kernels and kantts_attn_decode)
   // x: causal band [max(0, step - band), step]
   d_attend(q, xb, xb + D, 2 * D, live ? max(0, step - band) : 1, live ? step : 0, o);
-  d_store16(ox + (long long)b * D + h * DDH, o);
+  kantts_store16(ox + (long long)b * D + h * DDH, o);
   // h: look-ahead band [step, min(step + band, L - 1, len - 1)] over the memory K / V
   const float* hb = hkv + (long long)b * L * 2 * D + h * DDH;
   d_attend(q, hb, hb + D, 2 * D, live ? step : 1, live ? min(min(step + band, L - 1), len - 1) : 0, o);
-  d_store16(oh + (long long)b * D + h * DDH, o);
+  kantts_store16(oh + (long long)b * D + h * DDH, o);
 }
 
 extern "C" int kantts_pnca_decode_step(const float* qkv, int ldq, float* xkv_cache, const float* hkv, float* ox, float* oh,

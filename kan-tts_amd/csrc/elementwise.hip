@@ -104,7 +104,6 @@ extern "C" int kantts_weight_norm_tap_images(const float* v, const float* g, flo
 // workgroup put every 2-byte element of it on a cache line of its own (first version: 351 us per launch at 1.4 TB/s of
 // useful traffic, profiles/r04_runC_gan_kernel_stats_top.csv).
 #define WN_R 8
-typedef __bf16 wn_bf16x8 __attribute__((ext_vector_type(8)));
 __global__ __launch_bounds__(256) void weight_norm_table_kernel(const float* __restrict__ flat, float* __restrict__ w,
                                                                __bf16* __restrict__ wf, __bf16* __restrict__ wd,
                                                                const kantts_wn_desc* __restrict__ tab, int ndesc) {
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(256) void weight_norm_table_kernel(const float* __r
   const bool vec = wdo && nr == WN_R && ((rg & 7) == 0);
   for (int j = threadIdx.x; j < cols; j += 256) {  // ci fastest: coalesced on the tap-major side
     const int k = j / cin, ci = j - k * cin;
-    wn_bf16x8 pk;
+    bf16x8 pk;
 #pragma unroll
     for (int i = 0; i < WN_R; ++i) {
       float val = 0.f;
@@ -153,7 +152,7 @@ __global__ __launch_bounds__(256) void weight_norm_table_kernel(const float* __r
       }
       pk[i] = (__bf16)val;
     }
-    if (vec) *reinterpret_cast<wn_bf16x8*>(wdo + (((long long)k * d.groups + grp) * cin + ci) * rg + rl0) = pk;
+    if (vec) *reinterpret_cast<bf16x8*>(wdo + (((long long)k * d.groups + grp) * cin + ci) * rg + rl0) = pk;
   }
 }
 
@@ -303,7 +302,6 @@ struct MeanManyArgs {
   float* o[8];
   int n;
 };
-typedef __bf16 mm_bf16x4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void mean_many_kernel(const MeanManyArgs a, float scale, float* __restrict__ out,
                                                         __bf16* __restrict__ act, float slope, long long n4) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
@@ -315,9 +313,9 @@ __global__ __launch_bounds__(256) void mean_many_kernel(const MeanManyArgs a, fl
     s.x *= scale; s.y *= scale; s.z *= scale; s.w *= scale;
     reinterpret_cast<float4*>(out)[i] = s;
     if (act) {
-      mm_bf16x4 b = {(__bf16)(s.x > 0.f ? s.x : s.x * slope), (__bf16)(s.y > 0.f ? s.y : s.y * slope),
+      bf16x4 b = {(__bf16)(s.x > 0.f ? s.x : s.x * slope), (__bf16)(s.y > 0.f ? s.y : s.y * slope),
                      (__bf16)(s.z > 0.f ? s.z : s.z * slope), (__bf16)(s.w > 0.f ? s.w : s.w * slope)};
-      reinterpret_cast<mm_bf16x4*>(act)[i] = b;
+      reinterpret_cast<bf16x4*>(act)[i] = b;
     }
   }
 }
@@ -412,7 +410,7 @@ extern "C" int kantts_sinadd_bwd(const float* dy, const float* x, float* dx, lon
 __global__ __launch_bounds__(256) void dropout2_add_kernel(const float* __restrict__ x, const float* __restrict__ res,
                                                           float* __restrict__ y, long long n4, float p1, uint64_t seed1,
                                                           float p2, uint64_t seed2, const uint64_t* __restrict__ seed_dev) {
-  const uint64_t off = seed_dev ? *seed_dev : 0ull;
+  const uint64_t off = kantts_seed_offset(seed_dev);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
     const float4 v = reinterpret_cast<const float4*>(x)[i];
     float o[4] = {v.x, v.y, v.z, v.w};

@@ -34,22 +34,11 @@
 
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 #define EA_THREADS 512
 #define EA_TMAX 128          // longest sequence (tokens): 8 token blocks of 16 (the 64-token instantiation holds 4)
 #define EA_C 128
 #define EA_H 8
 #define EA_XP (EA_C + 16)   // bf16 row pitch of the token tiles: 288 B = 32 mod 64
-
-__device__ __forceinline__ unsigned ea_pack2(float a, float b) {
-  typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-  v2 t = {(__bf16)a, (__bf16)b};
-  return (unsigned&)t;
-}
 
 __device__ __forceinline__ float ea_col_max(float v) {  // over the 4 lane groups kg that share a column li
   v = fmaxf(v, __shfl_xor(v, 16, 64));
@@ -69,7 +58,7 @@ __global__ __launch_bounds__(EA_THREADS) void enc_attn_fwd_kernel(const kantts_e
   const int b = blockIdx.x, qb = blockIdx.y, T = g.L;         // this workgroup: queries qb * 16 .. + 15 of sequence b
   const long long m0 = (long long)b * T;
   const int len = g.lens ? min(max(g.lens[b], 0), T) : T;
-  const uint64_t seed_off = g.seed_dev ? *g.seed_dev : 0ull;
+  const uint64_t seed_off = kantts_seed_offset(g.seed_dev);
   const __bf16* __restrict__ wq = reinterpret_cast<const __bf16*>(g.wqkv);
   const __bf16* __restrict__ wf = reinterpret_cast<const __bf16*>(g.wfc);
   const float* dummy = reinterpret_cast<const float*>(g.wqkv);  // any mapped, 16-byte aligned address
@@ -225,7 +214,7 @@ __global__ __launch_bounds__(EA_THREADS) void enc_attn_fwd_kernel(const kantts_e
   }
   __syncthreads();  // every wave has read the normalised rows: rows 0..15 of the tile become the context tile
   {
-    const u32x2 pk = {ea_pack2(ao[0], ao[1]), ea_pack2(ao[2], ao[3])};
+    const u32x2 pk = {kantts_pack2(ao[0], ao[1]), kantts_pack2(ao[2], ao[3])};
     *reinterpret_cast<u32x2*>(&Xs[li * EA_XP + wave * 16 + kg * 4]) = pk;
   }
   __syncthreads();
@@ -278,7 +267,7 @@ __global__ __launch_bounds__(EA_THREADS) void enc_attn_fwd_kernel(const kantts_e
     const float z0 = (y1v[0] - mu) * rs * l1g.x + l1b.x, z1 = (y1v[1] - mu) * rs * l1g.y + l1b.y;
     const float z2 = (y1v[2] - mu) * rs * l1g.z + l1b.z, z3 = (y1v[3] - mu) * rs * l1g.w + l1b.w;
     if (g.xn1_bf16) {
-      const u32x2 pk = {ea_pack2(z0, z1), ea_pack2(z2, z3)};
+      const u32x2 pk = {kantts_pack2(z0, z1), kantts_pack2(z2, z3)};
       *reinterpret_cast<u32x2*>(reinterpret_cast<__bf16*>(g.xn1) + m * EA_C + n0) = pk;
     } else {
       *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(g.xn1) + m * EA_C + n0) = (f32x4){z0, z1, z2, z3};
@@ -290,8 +279,6 @@ __global__ __launch_bounds__(EA_THREADS) void enc_attn_fwd_kernel(const kantts_e
   }
 }
 
-static bool ea_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 extern "C" int kantts_enc_attn_fwd(const kantts_enc_attn_args* gp, void* stream) {
   if (!gp) return KANTTS_E_BADARG;
   const kantts_enc_attn_args& g = *gp;
@@ -302,7 +289,7 @@ extern "C" int kantts_enc_attn_fwd(const kantts_enc_attn_args* gp, void* stream)
   if (g.xn1 && (!g.mean1 || !g.rstd1)) return KANTTS_E_BADARG;
   const void* ps[] = {g.x, g.xn, g.wqkv, g.wfc, g.bqkv, g.bfc, g.ln1_gamma, g.ln1_beta, g.qkv, g.o, g.y1, g.xn1};
   for (const void* p : ps)
-    if (!ea_aligned16(p)) return KANTTS_E_UNSUPPORTED;
+    if (!kantts_aligned16(p)) return KANTTS_E_UNSUPPORTED;
   if (g.L <= 64)
     hipLaunchKernelGGL(enc_attn_fwd_kernel<4>, dim3(g.B, (g.L + 15) / 16), dim3(EA_THREADS), 0, (hipStream_t)stream, g);
   else

@@ -30,12 +30,6 @@
 // = 22.3 MB against 35.6 MB for the two-launch form.
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 #define FP_THREADS 512
 // Geometry is a template parameter of the kernel (ffn_pair_body.inc): input width K1, output width N, hidden width F, token
 // tile height BM, most taps of phase 1 MAXKT.  What is instantiated is what the model runs:
@@ -59,13 +53,6 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 #define FP_DEPTH_TALL 2
 #endif
 
-__device__ __forceinline__ unsigned fp_pack2(float a, float b) {
-  bf16x4 t = {(__bf16)a, (__bf16)b, (__bf16)0.f, (__bf16)0.f};
-  return ((u32x2&)t).x;
-}
-__device__ __forceinline__ float fp_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float fp_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-
 // KT2 = taps of PHASE 2 (the backward pass of a k = 3 first convolution: dh[m] = sum_tap dz[m + pad - tap] . W1[tap]):
 // the tile then covers 32 rows of the intermediate of which the inner 32 - (KT2 - 1) are output rows -- the halo rows are
 // recomputed by the neighbouring workgroup (6 % more phase-1 work instead of a second launch that re-reads dz).
@@ -73,7 +60,6 @@ template <bool BWD, int KT2, int K1, int N, int F, int BM, int MAXKT>
 __global__ __launch_bounds__(FP_THREADS) void ffn_pair_kernel(const kantts_ffn_args g) {
 #include "ffn_pair_body.inc"
 }
-static bool fp_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // the k = 1 geometries (FSMN feed-forward nets): forward form or backward form, nothing else
 template <int K1, int N, int F, int BM>
@@ -96,9 +82,9 @@ static int fp_check(const kantts_ffn_args* gp, bool* launch) {
   if (!blk && !wide && !slim) return KANTTS_E_UNSUPPORTED;
   if (g.KT > 9 || g.pad < 0 || g.pad >= g.KT || (g.KT > 1 && g.T <= 0)) return KANTTS_E_UNSUPPORTED;
   if ((g.ldx & 7) || (g.ldy & 3) || (g.res && (g.ldr & 3))) return KANTTS_E_UNSUPPORTED;
-  if (!fp_aligned16(g.x) || !fp_aligned16(g.w1) || !fp_aligned16(g.w2) || !fp_aligned16(g.y) ||
-      (g.t_out && !fp_aligned16(g.t_out)) || (g.gate && !fp_aligned16(g.gate)) || (g.res && !fp_aligned16(g.res)) ||
-      (g.bias1 && !fp_aligned16(g.bias1)) || (g.bias2 && !fp_aligned16(g.bias2)))
+  if (!kantts_aligned16(g.x) || !kantts_aligned16(g.w1) || !kantts_aligned16(g.w2) || !kantts_aligned16(g.y) ||
+      (g.t_out && !kantts_aligned16(g.t_out)) || (g.gate && !kantts_aligned16(g.gate)) || (g.res && !kantts_aligned16(g.res)) ||
+      (g.bias1 && !kantts_aligned16(g.bias1)) || (g.bias2 && !kantts_aligned16(g.bias2)))
     return KANTTS_E_UNSUPPORTED;
   if (g.xdrop_p > 0.f && !g.x_f32) return KANTTS_E_UNSUPPORTED;
   if (g.gate && g.KT != 1) return KANTTS_E_UNSUPPORTED;
@@ -107,7 +93,7 @@ static int fp_check(const kantts_ffn_args* gp, bool* launch) {
   if (kt2 == 3 && (!g.gate || g.T <= 0 || (g.s2_step != 1 && g.s2_step != -1) || g.M % g.T)) return KANTTS_E_UNSUPPORTED;
   if (g.ln_out) {
     if (!g.ln_gamma || !g.ln_beta || !g.ln_mean || !g.ln_rstd) return KANTTS_E_BADARG;
-    if (g.gate || kt2 != 1 || !fp_aligned16(g.ln_out) || !fp_aligned16(g.ln_gamma) || !fp_aligned16(g.ln_beta))
+    if (g.gate || kt2 != 1 || !kantts_aligned16(g.ln_out) || !kantts_aligned16(g.ln_gamma) || !kantts_aligned16(g.ln_beta))
       return KANTTS_E_UNSUPPORTED;
   }
   // the FSMN shapes carry only the ports an FSMN feed-forward net uses: k = 1 either way, no LayerNorm epilogue, no

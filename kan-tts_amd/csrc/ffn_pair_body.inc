@@ -33,7 +33,7 @@
   const int mo0 = blockIdx.x * OUT;                     // first output row of this workgroup
   const int m0 = mo0 - HL;                              // global row of tile row 0 (may be negative)
   const int M = g.M, KT = MAXKT == 1 ? 1 : g.KT, pad = MAXKT == 1 ? 0 : g.pad, T = g.T;
-  const uint64_t seed_off = g.seed_dev ? *g.seed_dev : 0ull;
+  const uint64_t seed_off = kantts_seed_offset(g.seed_dev);
   const __bf16* __restrict__ w1 = reinterpret_cast<const __bf16*>(g.w1);
   const __bf16* __restrict__ w2 = reinterpret_cast<const __bf16*>(g.w2);
 
@@ -109,8 +109,8 @@
 #pragma unroll
       for (int it = 0; it < XIT; ++it) {
         const int id = tid + FP_THREADS * it, j = id / XV;
-        u32x4 v = {fp_pack2(xa[it].x, xa[it].y), fp_pack2(xa[it].z, xa[it].w), fp_pack2(xb[it].x, xb[it].y),
-                   fp_pack2(xb[it].z, xb[it].w)};
+        u32x4 v = {kantts_pack2_of4(xa[it].x, xa[it].y), kantts_pack2_of4(xa[it].z, xa[it].w), kantts_pack2_of4(xb[it].x, xb[it].y),
+                   kantts_pack2_of4(xb[it].z, xb[it].w)};
         if (m0 + j >= M) v = (u32x4){0u, 0u, 0u, 0u};
         *reinterpret_cast<u32x4*>(&Xs[j * XP + (id % XV) * 8]) = v;
       }
@@ -149,10 +149,10 @@
             a = make_float4(lo4[0], lo4[1], lo4[2], lo4[3]);
             b = make_float4(hi4[0], hi4[1], hi4[2], hi4[3]);
           }
-          v.x = fp_pack2(a.x, a.y);
-          v.y = fp_pack2(a.z, a.w);
-          v.z = fp_pack2(b.x, b.y);
-          v.w = fp_pack2(b.z, b.w);
+          v.x = kantts_pack2_of4(a.x, a.y);
+          v.y = kantts_pack2_of4(a.z, a.w);
+          v.z = kantts_pack2_of4(b.x, b.y);
+          v.w = kantts_pack2_of4(b.z, b.w);
         } else {
           v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(g.x) + src * g.ldx + ch * 8);
         }
@@ -248,7 +248,7 @@
         float o[4] = {acc[a][b][0], acc[a][b][1], acc[a][b][2], acc[a][b][3]};
         if (BWD) {
           const u32x2 q = *reinterpret_cast<const u32x2*>(&Ts[tok * TP + f0]);
-          const float gv[4] = {fp_lo(q.x), fp_hi(q.x), fp_lo(q.y), fp_hi(q.y)};
+          const float gv[4] = {kantts_bf16_lo(q.x), kantts_bf16_hi(q.x), kantts_bf16_lo(q.y), kantts_bf16_hi(q.y)};
 #pragma unroll
           for (int r4 = 0; r4 < 4; ++r4) o[r4] = (gv[r4] > 0.f) ? o[r4] * g.alpha1 : 0.f;
         } else {
@@ -266,7 +266,7 @@
             for (int r4 = 0; r4 < 4; ++r4) o[r4] = 0.f;
           }
         }
-        const u32x2 pk = {fp_pack2(o[0], o[1]), fp_pack2(o[2], o[3])};
+        const u32x2 pk = {kantts_pack2_of4(o[0], o[1]), kantts_pack2_of4(o[2], o[3])};
         *reinterpret_cast<u32x2*>(&Ts[tok * TP + f0]) = pk;
       }
     }
@@ -425,7 +425,7 @@
       }
       if (!live[b]) continue;
       if (g.y_bf16) {
-        const u32x2 pk = {fp_pack2(o[0], o[1]), fp_pack2(o[2], o[3])};
+        const u32x2 pk = {kantts_pack2_of4(o[0], o[1]), kantts_pack2_of4(o[2], o[3])};
         *reinterpret_cast<u32x2*>(reinterpret_cast<__bf16*>(g.y) + m * g.ldy + n0[a]) = pk;
       } else {
         const f32x4 v = {o[0], o[1], o[2], o[3]};
@@ -479,7 +479,7 @@
       const float y0 = (o[0] - mu[b]) * rs[b] * lg4.x + lb4.x, y1 = (o[1] - mu[b]) * rs[b] * lg4.y + lb4.y;
       const float y2 = (o[2] - mu[b]) * rs[b] * lg4.z + lb4.z, y3 = (o[3] - mu[b]) * rs[b] * lg4.w + lb4.w;
       if (g.ln_out_bf16) {
-        const u32x2 pk = {fp_pack2(y0, y1), fp_pack2(y2, y3)};
+        const u32x2 pk = {kantts_pack2_of4(y0, y1), kantts_pack2_of4(y2, y3)};
         *reinterpret_cast<u32x2*>(reinterpret_cast<__bf16*>(g.ln_out) + m * N + n0[0]) = pk;
       } else {
         const f32x4 v = {y0, y1, y2, y3};

@@ -64,17 +64,14 @@ __device__ __forceinline__ void fsmn_drop41_body(const float* __restrict__ x, co
   int vid = blockIdx.x;
   {
     const int total = gridDim.x;
-    if (total >= 64) {
-      const int k = vid & 7, j = vid >> 3, q = total >> 3, r = total & 7;
-      vid = k * q + (k < r ? k : r) + j;
-    }
+    if (total >= 64) vid = kantts_xcd_slot(total, vid);
   }
   const int cb = vid % ncb, bt = vid / ncb;
   const int b = bt / nt, t0 = (bt - b * nt) * FD_TT, c0 = cb * FD_CB;
   const int tid = threadIdx.x;
   const int len = lens ? (int)min((long long)lens[b], (long long)T) : T;
   const long long row0 = (long long)b * T;
-  const uint64_t off = seed_dev ? *seed_dev : 0ull;
+  const uint64_t off = kantts_seed_offset(seed_dev);
   const uint64_t s1 = seed1 + off, s2 = seed2 + off;
 
   if (t0 >= len) {  // a tile of padding: the masked FIR is zero, so y = 0 * keep1 * keep2 + res; dx = dym = 0
@@ -232,8 +229,6 @@ __global__ __launch_bounds__(FD_THREADS) void fsmn_drop41_pair_kernel(const FdPa
   fsmn_drop41_body<BWD>(a.x, a.w, a.res, lens, a.y, a.dym, B, T, C, lp, a.p1, a.seed1, a.p2, a.seed2, seed_dev);
 }
 
-static bool fd_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 static int fd_check(const void* a, const void* w, const void* o, int B, int T, int C, int K, int left_pad, float p1, float p2,
                     long long* blocks) {
   if (!a || !w || !o || B < 0 || T < 0 || C < 1 || K < 1 || left_pad < 0 || left_pad >= K || p1 < 0.f || p1 >= 1.f ||
@@ -250,7 +245,7 @@ static int fd_check_fwd(const float* c, const float* w, const float* res, float*
                         float p1, float p2, long long* blocks) {
   const int rc = fd_check(c, w, y, B, T, C, K, left_pad, p1, p2, blocks);
   if (rc != KANTTS_OK) return rc;
-  if (!fd_aligned16(c) || !fd_aligned16(res) || !fd_aligned16(y)) return KANTTS_E_UNSUPPORTED;
+  if (!kantts_aligned16(c) || !kantts_aligned16(res) || !kantts_aligned16(y)) return KANTTS_E_UNSUPPORTED;
   return KANTTS_OK;
 }
 static int fd_check_bwd(const float* dy, const float* w, float* dx, float* dym, int B, int T, int C, int K, int left_pad,
@@ -258,7 +253,7 @@ static int fd_check_bwd(const float* dy, const float* w, float* dx, float* dym, 
   const int rc = fd_check(dy, w, dx, B, T, C, K, left_pad, p1, p2, blocks);
   if (rc != KANTTS_OK) return rc;
   if (!dym) return KANTTS_E_BADARG;
-  if (!fd_aligned16(dy) || !fd_aligned16(dx) || !fd_aligned16(dym)) return KANTTS_E_UNSUPPORTED;
+  if (!kantts_aligned16(dy) || !kantts_aligned16(dx) || !kantts_aligned16(dym)) return KANTTS_E_UNSUPPORTED;
   return KANTTS_OK;
 }
 

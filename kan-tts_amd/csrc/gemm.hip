@@ -16,9 +16,6 @@
 
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 #define G_BN 64
 #define G_BK 32
 #define G_THREADS 256
@@ -73,7 +70,7 @@ __device__ __forceinline__ float g_load_a(const kantts_gemm_seg& s, const kantts
   if (s.a_act) v = v > 0.f ? v : v * s.a_slope;
   if (s.a_gate && !(s.a_gate[off] > 0.f)) v *= s.a_gate_slope;
   if (s.a_drop_p > 0.f)
-    v *= kantts_dropout_scale(s.a_drop_p, s.a_drop_seed + (g.seed_dev ? *g.seed_dev : 0ull), (uint64_t)off);
+    v *= kantts_dropout_scale(s.a_drop_p, s.a_drop_seed + kantts_seed_offset(g.seed_dev), (uint64_t)off);
   return v;
 }
 
@@ -98,7 +95,7 @@ __device__ __forceinline__ float g_epilogue(const kantts_gemm_args& g, float acc
   if (g.relu) v = fmaxf(v, 0.f);
   if (g.out_act) v = v > 0.f ? v : v * g.out_slope;
   if (g.drop_p > 0.f)
-    v *= kantts_dropout_scale(g.drop_p, g.drop_seed + (g.seed_dev ? *g.seed_dev : 0ull),
+    v *= kantts_dropout_scale(g.drop_p, g.drop_seed + kantts_seed_offset(g.seed_dev),
                               (uint64_t)i * (uint64_t)g.N + (uint64_t)j);
   if (first_slice && g.res) v += g.res[(long long)i * g.r_is + (long long)j * g.r_js + grp * g.r_gs];
   if (g.gate) {
@@ -203,7 +200,7 @@ __global__ __launch_bounds__(G_THREADS) void gemm_seg_mfma_kernel(const kantts_g
   const int zrem = blockIdx.z % zper;
   const int grp = zrem / g.splitk;
   const int zslice = zrem % g.splitk;
-  const uint64_t seed_off = g.seed_dev ? *g.seed_dev : 0ull;
+  const uint64_t seed_off = kantts_seed_offset(g.seed_dev);
 
   f32x4 acc[MREP][2];
 #pragma unroll

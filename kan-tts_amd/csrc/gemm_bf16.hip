@@ -24,28 +24,14 @@
 
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 #define BG_THREADS 256
 #define BG_BN 128
 #define BG_BK 64
 #define BG_LDKN (BG_BN + 16)  // pitch (elements) of an n-contiguous image
 
-typedef __attribute__((address_space(3))) bf16x4 bg_lds_bf16x4;
 __device__ __forceinline__ bf16x4 bg_tr4(const __bf16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bg_lds_bf16x4*)(p));
+  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((kantts_lds_bf16x4*)(p));
 }
-
-__device__ __forceinline__ unsigned bg_pack2(float a, float b) {
-  bf16x4 t = {(__bf16)a, (__bf16)b, (__bf16)0.f, (__bf16)0.f};
-  return ((u32x2&)t).x;
-}
-__device__ __forceinline__ float bg_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bg_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 
 // 8 consecutive elements of a row as bf16: either a 16-byte copy or two float4 loads rounded once.  `drop` regenerates
 // an epilogue dropout of the forward pass on the incoming gradient (element index = logical offset in the tensor).
@@ -69,10 +55,10 @@ __device__ __forceinline__ u32x4 bg_load8(const void* base, long long elem, bool
       a = make_float4(lo4[0], lo4[1], lo4[2], lo4[3]);
       b = make_float4(hi4[0], hi4[1], hi4[2], hi4[3]);
     }
-    r.x = bg_pack2(a.x, a.y);
-    r.y = bg_pack2(a.z, a.w);
-    r.z = bg_pack2(b.x, b.y);
-    r.w = bg_pack2(b.z, b.w);
+    r.x = kantts_pack2_of4(a.x, a.y);
+    r.y = kantts_pack2_of4(a.z, a.w);
+    r.z = kantts_pack2_of4(b.x, b.y);
+    r.w = kantts_pack2_of4(b.z, b.w);
   } else {
     r = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(base) + e_);
     if (!ok) r = (u32x4){0u, 0u, 0u, 0u};
@@ -114,10 +100,10 @@ __device__ __forceinline__ u32x4 bg_finish8(const BgRaw<F32>& raw, bool ok, floa
       kantts_dropout_scale4(drop_p, seed, logical, lo4);
       kantts_dropout_scale4(drop_p, seed, logical + 4, hi4);
     }
-    r.x = bg_pack2(lo4[0], lo4[1]);
-    r.y = bg_pack2(lo4[2], lo4[3]);
-    r.z = bg_pack2(hi4[0], hi4[1]);
-    r.w = bg_pack2(hi4[2], hi4[3]);
+    r.x = kantts_pack2_of4(lo4[0], lo4[1]);
+    r.y = kantts_pack2_of4(lo4[2], lo4[3]);
+    r.z = kantts_pack2_of4(hi4[0], hi4[1]);
+    r.w = kantts_pack2_of4(hi4[2], hi4[3]);
   } else {
     r = raw.v[0];
   }
@@ -137,9 +123,7 @@ __device__ __forceinline__ void bg_xcd_remap(int& bx, int& by) {
   // that share an A row tile stay behind one L2
   const int gx = gridDim.x, total = gx * gridDim.y;
   if (total >= 64) {
-    const int L = by * gx + bx, k = L & 7, j = L >> 3;
-    const int q = total >> 3, r = total & 7;
-    const int vid = k * q + (k < r ? k : r) + j;
+    const int vid = kantts_xcd_slot(total, by * gx + bx);
     by = vid / gx;
     bx = vid - by * gx;
   }
@@ -177,8 +161,6 @@ static void bg_launch_nt(const kantts_bgemm_args& g, dim3 grid, hipStream_t st) 
   }
 }
 
-static bool bg_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // The argument checks and the tile choice of kantts_bgemm_nt, shared with the pair form.  *bm = 0: nothing to launch.
 static int bg_nt_check(const kantts_bgemm_args* gp, int* bm_out) {
   *bm_out = 0;
@@ -187,19 +169,19 @@ static int bg_nt_check(const kantts_bgemm_args* gp, int* bm_out) {
   if (g.nseg < 1 || g.nseg > KANTTS_BGEMM_MAX_SEG || g.M < 0 || g.N < 0 || !g.c) return KANTTS_E_BADARG;
   if (g.M == 0 || g.N == 0) return KANTTS_OK;
   // 16-byte vector access everywhere: 8-element granularity of every extent / leading dimension
-  if ((g.N & 7) || (g.ldc & 7) || !bg_aligned16(g.c)) return KANTTS_E_UNSUPPORTED;
-  if (g.res && ((g.ldr & 3) || !bg_aligned16(g.res))) return KANTTS_E_UNSUPPORTED;
-  if (g.gate && ((g.ldg & 7) || !bg_aligned16(g.gate))) return KANTTS_E_UNSUPPORTED;
-  if ((g.bias && !bg_aligned16(g.bias)) || (g.bias2 && !bg_aligned16(g.bias2))) return KANTTS_E_UNSUPPORTED;
+  if ((g.N & 7) || (g.ldc & 7) || !kantts_aligned16(g.c)) return KANTTS_E_UNSUPPORTED;
+  if (g.res && ((g.ldr & 3) || !kantts_aligned16(g.res))) return KANTTS_E_UNSUPPORTED;
+  if (g.gate && ((g.ldg & 7) || !kantts_aligned16(g.gate))) return KANTTS_E_UNSUPPORTED;
+  if ((g.bias && !kantts_aligned16(g.bias)) || (g.bias2 && !kantts_aligned16(g.bias2))) return KANTTS_E_UNSUPPORTED;
   if (g.ln_out) {
     if (!g.ln_gamma || !g.ln_beta || !g.ln_mean || !g.ln_rstd) return KANTTS_E_BADARG;
-    if (g.N != 128 || g.c_bf16 || !bg_aligned16(g.ln_out) || !bg_aligned16(g.ln_gamma) || !bg_aligned16(g.ln_beta))
+    if (g.N != 128 || g.c_bf16 || !kantts_aligned16(g.ln_out) || !kantts_aligned16(g.ln_gamma) || !kantts_aligned16(g.ln_beta))
       return KANTTS_E_UNSUPPORTED;
   }
   for (int s = 0; s < g.nseg; ++s) {
     const kantts_bgemm_seg& sg = g.seg[s];
     if (!sg.a || !sg.b || sg.klen < 8 || (sg.klen & 7) || (sg.lda & 7) || (sg.ldb & 7)) return KANTTS_E_UNSUPPORTED;
-    if (!bg_aligned16(sg.a) || !bg_aligned16(sg.b)) return KANTTS_E_UNSUPPORTED;
+    if (!kantts_aligned16(sg.a) || !kantts_aligned16(sg.b)) return KANTTS_E_UNSUPPORTED;
     if (sg.a_shift != 0 && g.T <= 0) return KANTTS_E_BADARG;
   }
   // 64-row tiles once they give every CU a workgroup, else 32-row tiles.  128-row tiles (one round of 408 workgroups
@@ -296,15 +278,15 @@ extern "C" int kantts_bgemm_nt_lnbwd(const kantts_bgemm_args* gp, const kantts_l
   // what the model has: the input gradient of a projection (weights stored (out, in) = [k][n]: b_kn) of LayerNorm-ed rows
   if (g.N != 128 || !g.b_kn || g.ln_out || g.gate || g.relu || g.drop_p > 0.f) return KANTTS_E_UNSUPPORTED;
   if (g.M == 0) return KANTTS_OK;
-  if (g.c && ((g.ldc & 7) || !bg_aligned16(g.c))) return KANTTS_E_UNSUPPORTED;
-  if (g.res && ((g.ldr & 3) || !bg_aligned16(g.res))) return KANTTS_E_UNSUPPORTED;
-  if ((g.bias && !bg_aligned16(g.bias)) || (g.bias2 && !bg_aligned16(g.bias2))) return KANTTS_E_UNSUPPORTED;
-  if (!bg_aligned16(l.x) || !bg_aligned16(l.gamma) || !bg_aligned16(l.dx) || (l.dres && !bg_aligned16(l.dres)))
+  if (g.c && ((g.ldc & 7) || !kantts_aligned16(g.c))) return KANTTS_E_UNSUPPORTED;
+  if (g.res && ((g.ldr & 3) || !kantts_aligned16(g.res))) return KANTTS_E_UNSUPPORTED;
+  if ((g.bias && !kantts_aligned16(g.bias)) || (g.bias2 && !kantts_aligned16(g.bias2))) return KANTTS_E_UNSUPPORTED;
+  if (!kantts_aligned16(l.x) || !kantts_aligned16(l.gamma) || !kantts_aligned16(l.dx) || (l.dres && !kantts_aligned16(l.dres)))
     return KANTTS_E_UNSUPPORTED;
   for (int s = 0; s < g.nseg; ++s) {
     const kantts_bgemm_seg& sg = g.seg[s];
     if (!sg.a || !sg.b || sg.klen < 8 || (sg.klen & 7) || (sg.lda & 7) || (sg.ldb & 7)) return KANTTS_E_UNSUPPORTED;
-    if (!bg_aligned16(sg.a) || !bg_aligned16(sg.b)) return KANTTS_E_UNSUPPORTED;
+    if (!kantts_aligned16(sg.a) || !kantts_aligned16(sg.b)) return KANTTS_E_UNSUPPORTED;
     if (sg.a_shift != 0 && g.T <= 0) return KANTTS_E_BADARG;
   }
   // 32-row tiles: 2 x 256 same-address atomics per workgroup, and one round of workgroups at the decoder's 6528 rows
@@ -395,7 +377,7 @@ __global__ __launch_bounds__(BG_THREADS) void bgemm_tn_kernel(const TnGroupArgs 
   g.db = ga.db[prob];
   g.a_drop_seed = ga.a_drop_seed[prob];
   const int shift = g.shift0 + tap * g.shift_step;
-  const uint64_t seed_off = g.seed_dev ? *g.seed_dev : 0ull;
+  const uint64_t seed_off = kantts_seed_offset(g.seed_dev);
 
   f32x4 acc[MR][NR];
 #pragma unroll
@@ -534,13 +516,8 @@ __global__ __launch_bounds__(BG_THREADS) void bgemm_tn_kernel(const TnGroupArgs 
 template <bool A_F32, bool B_F32, int BN, int BK>
 static int bg_tn_go(TnGroupArgs& ga, dim3 grid, hipStream_t st) {
   constexpr size_t LDS = 2 * (size_t)TN_BT * ((BN + 16) + (BK + 16)) * 2;
-  static bool attr_set = false;
-  if (!attr_set && LDS > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bgemm_tn_kernel<A_F32, B_F32, BN, BK>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (LDS > 64 * 1024)
+    if (int e = kantts_allow_dynamic_lds<&bgemm_tn_kernel<A_F32, B_F32, BN, BK>>((int)LDS)) return e;
   hipLaunchKernelGGL((bgemm_tn_kernel<A_F32, B_F32, BN, BK>), grid, dim3(BG_THREADS), LDS, st, ga);
   KANTTS_CHECK_LAUNCH();
 }
@@ -572,7 +549,7 @@ static int bg_tn_launch(TnGroupArgs& ga, hipStream_t st) {
   if ((g.N & 7) || (g.K & 7) || (g.lda & 7) || (g.ldb & 7)) return KANTTS_E_UNSUPPORTED;
   for (int p = 0; p < ga.nprob; ++p) {
     if (!ga.a[p] || !ga.b[p] || !ga.c[p]) return KANTTS_E_BADARG;
-    if (!bg_aligned16(ga.a[p]) || !bg_aligned16(ga.b[p])) return KANTTS_E_UNSUPPORTED;
+    if (!kantts_aligned16(ga.a[p]) || !kantts_aligned16(ga.b[p])) return KANTTS_E_UNSUPPORTED;
   }
   if ((g.shift0 != 0 || g.shift_step != 0) && g.T <= 0) return KANTTS_E_BADARG;
   // tile (BN x BK) and token slices.  kantts_launch_tuning(tn_tile = BN * 1000 + BK (64128 / 128128 / 64256 / 128256),
@@ -659,12 +636,12 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n8) return;
   const float4 a = reinterpret_cast<const float4*>(src)[2 * i], b = reinterpret_cast<const float4*>(src)[2 * i + 1];
-  u32x4 w = {bg_pack2(a.x, a.y), bg_pack2(a.z, a.w), bg_pack2(b.x, b.y), bg_pack2(b.z, b.w)};
+  u32x4 w = {kantts_pack2_of4(a.x, a.y), kantts_pack2_of4(a.z, a.w), kantts_pack2_of4(b.x, b.y), kantts_pack2_of4(b.z, b.w)};
   reinterpret_cast<u32x4*>(dst)[i] = w;
 }
 
 extern "C" int kantts_cast_f32_bf16(const float* src, void* dst, long long n, void* stream) {
-  if (!src || !dst || n < 0 || (n & 7) || !bg_aligned16(src) || !bg_aligned16(dst)) return KANTTS_E_BADARG;
+  if (!src || !dst || n < 0 || (n & 7) || !kantts_aligned16(src) || !kantts_aligned16(dst)) return KANTTS_E_BADARG;
   if (n == 0) return KANTTS_OK;
   const long long n8 = n / 8;
   hipLaunchKernelGGL(cast_bf16_kernel, dim3(kantts_cdiv(n8, 256)), dim3(256), 0, (hipStream_t)stream, src,
@@ -704,16 +681,16 @@ __global__ __launch_bounds__(256) void relu_gate_kernel(const void* __restrict__
   float d[8], a[8];
   if (DY_BF16) {
     const u32x4 q = reinterpret_cast<const u32x4*>(dy)[i];
-    d[0] = bg_lo(q.x); d[1] = bg_hi(q.x); d[2] = bg_lo(q.y); d[3] = bg_hi(q.y);
-    d[4] = bg_lo(q.z); d[5] = bg_hi(q.z); d[6] = bg_lo(q.w); d[7] = bg_hi(q.w);
+    d[0] = kantts_bf16_lo(q.x); d[1] = kantts_bf16_hi(q.x); d[2] = kantts_bf16_lo(q.y); d[3] = kantts_bf16_hi(q.y);
+    d[4] = kantts_bf16_lo(q.z); d[5] = kantts_bf16_hi(q.z); d[6] = kantts_bf16_lo(q.w); d[7] = kantts_bf16_hi(q.w);
   } else {
     const float4 p = reinterpret_cast<const float4*>(dy)[2 * i], q = reinterpret_cast<const float4*>(dy)[2 * i + 1];
     d[0] = p.x; d[1] = p.y; d[2] = p.z; d[3] = p.w; d[4] = q.x; d[5] = q.y; d[6] = q.z; d[7] = q.w;
   }
   if (Y_BF16) {
     const u32x4 q = reinterpret_cast<const u32x4*>(y)[i];
-    a[0] = bg_lo(q.x); a[1] = bg_hi(q.x); a[2] = bg_lo(q.y); a[3] = bg_hi(q.y);
-    a[4] = bg_lo(q.z); a[5] = bg_hi(q.z); a[6] = bg_lo(q.w); a[7] = bg_hi(q.w);
+    a[0] = kantts_bf16_lo(q.x); a[1] = kantts_bf16_hi(q.x); a[2] = kantts_bf16_lo(q.y); a[3] = kantts_bf16_hi(q.y);
+    a[4] = kantts_bf16_lo(q.z); a[5] = kantts_bf16_hi(q.z); a[6] = kantts_bf16_lo(q.w); a[7] = kantts_bf16_hi(q.w);
   } else {
     const float4 p = reinterpret_cast<const float4*>(y)[2 * i], q = reinterpret_cast<const float4*>(y)[2 * i + 1];
     a[0] = p.x; a[1] = p.y; a[2] = p.z; a[3] = p.w; a[4] = q.x; a[5] = q.y; a[6] = q.z; a[7] = q.w;
@@ -721,13 +698,13 @@ __global__ __launch_bounds__(256) void relu_gate_kernel(const void* __restrict__
   float o[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] = a[e] > 0.f ? d[e] * scale : 0.f;
-  u32x4 w = {bg_pack2(o[0], o[1]), bg_pack2(o[2], o[3]), bg_pack2(o[4], o[5]), bg_pack2(o[6], o[7])};
+  u32x4 w = {kantts_pack2_of4(o[0], o[1]), kantts_pack2_of4(o[2], o[3]), kantts_pack2_of4(o[4], o[5]), kantts_pack2_of4(o[6], o[7])};
   reinterpret_cast<u32x4*>(dz)[i] = w;
 }
 
 extern "C" int kantts_relu_gate_bf16(const void* dy, int dy_bf16, const void* y, int y_bf16, void* dz_bf16, float scale,
                                      long long n, void* stream) {
-  if (!dy || !y || !dz_bf16 || n < 0 || (n & 7) || !bg_aligned16(dy) || !bg_aligned16(y) || !bg_aligned16(dz_bf16))
+  if (!dy || !y || !dz_bf16 || n < 0 || (n & 7) || !kantts_aligned16(dy) || !kantts_aligned16(y) || !kantts_aligned16(dz_bf16))
     return KANTTS_E_BADARG;
   if (n == 0) return KANTTS_OK;
   const long long n8 = n / 8;

@@ -22,7 +22,7 @@
   int bx = blockIdx.x, by = blockIdx.y;
   bg_xcd_remap(bx, by);
   const int i0 = by * BM, j0 = bx * BG_BN;
-  const uint64_t seed_off = g.seed_dev ? *g.seed_dev : 0ull;
+  const uint64_t seed_off = kantts_seed_offset(g.seed_dev);
 
   f32x4 acc[MREP][NREP];
 #pragma unroll
@@ -268,8 +268,8 @@
       float gv[8];
       if (g.gate_bf16) {
         const u32x4 q = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(g.gate) + (long long)i * g.ldg + j);
-        gv[0] = bg_lo(q.x); gv[1] = bg_hi(q.x); gv[2] = bg_lo(q.y); gv[3] = bg_hi(q.y);
-        gv[4] = bg_lo(q.z); gv[5] = bg_hi(q.z); gv[6] = bg_lo(q.w); gv[7] = bg_hi(q.w);
+        gv[0] = kantts_bf16_lo(q.x); gv[1] = kantts_bf16_hi(q.x); gv[2] = kantts_bf16_lo(q.y); gv[3] = kantts_bf16_hi(q.y);
+        gv[4] = kantts_bf16_lo(q.z); gv[5] = kantts_bf16_hi(q.z); gv[6] = kantts_bf16_lo(q.w); gv[7] = kantts_bf16_hi(q.w);
       } else {
         const float* gp = reinterpret_cast<const float*>(g.gate) + (long long)i * g.ldg + j;
         const float4 q0 = *reinterpret_cast<const float4*>(gp), q1 = *reinterpret_cast<const float4*>(gp + 4);
@@ -284,7 +284,7 @@
     }
     if (!LNB || (g.c && live)) {
       if (g.c_bf16) {
-        u32x4 w = {bg_pack2(o[0], o[1]), bg_pack2(o[2], o[3]), bg_pack2(o[4], o[5]), bg_pack2(o[6], o[7])};
+        u32x4 w = {kantts_pack2_of4(o[0], o[1]), kantts_pack2_of4(o[2], o[3]), kantts_pack2_of4(o[4], o[5]), kantts_pack2_of4(o[6], o[7])};
         *reinterpret_cast<u32x4*>(reinterpret_cast<__bf16*>(g.c) + (long long)i * g.ldc + j) = w;
       } else {
         float* cp = reinterpret_cast<float*>(g.c) + (long long)i * g.ldc + j;
@@ -295,9 +295,9 @@
     }
     if constexpr (LNB) {  // same arithmetic, in the same order, as ln128_bwd_kernel (csrc/norm.hip) on dy = o
       if (g.c_bf16) {     // ... as the two-launch form hands it over: rounded to bf16
-        const u32x4 w = {bg_pack2(o[0], o[1]), bg_pack2(o[2], o[3]), bg_pack2(o[4], o[5]), bg_pack2(o[6], o[7])};
-        o[0] = bg_lo(w.x); o[1] = bg_hi(w.x); o[2] = bg_lo(w.y); o[3] = bg_hi(w.y);
-        o[4] = bg_lo(w.z); o[5] = bg_hi(w.z); o[6] = bg_lo(w.w); o[7] = bg_hi(w.w);
+        const u32x4 w = {kantts_pack2_of4(o[0], o[1]), kantts_pack2_of4(o[2], o[3]), kantts_pack2_of4(o[4], o[5]), kantts_pack2_of4(o[6], o[7])};
+        o[0] = kantts_bf16_lo(w.x); o[1] = kantts_bf16_hi(w.x); o[2] = kantts_bf16_lo(w.y); o[3] = kantts_bf16_hi(w.y);
+        o[4] = kantts_bf16_lo(w.z); o[5] = kantts_bf16_hi(w.z); o[6] = kantts_bf16_lo(w.w); o[7] = kantts_bf16_hi(w.w);
       }
       const long long off = (long long)i * 128 + j;
       const float4 xa = *reinterpret_cast<const float4*>(lnb->x + off), xb = *reinterpret_cast<const float4*>(lnb->x + off + 4);
@@ -350,7 +350,7 @@
 #pragma unroll
       for (int e = 0; e < 8; ++e) y[e] = (o[e] - mu) * rs * lg[e] + lb[e];
       if (g.ln_out_bf16) {
-        u32x4 w = {bg_pack2(y[0], y[1]), bg_pack2(y[2], y[3]), bg_pack2(y[4], y[5]), bg_pack2(y[6], y[7])};
+        u32x4 w = {kantts_pack2_of4(y[0], y[1]), kantts_pack2_of4(y[2], y[3]), kantts_pack2_of4(y[4], y[5]), kantts_pack2_of4(y[6], y[7])};
         *reinterpret_cast<u32x4*>(reinterpret_cast<__bf16*>(g.ln_out) + (long long)i * 128 + j) = w;
       } else {
         float* yp = reinterpret_cast<float*>(g.ln_out) + (long long)i * 128 + j;

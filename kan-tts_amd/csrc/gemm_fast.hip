@@ -18,10 +18,6 @@
 
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 #define F_BN 64
 #define F_THREADS 256
 
@@ -67,9 +63,8 @@ __device__ __forceinline__ void lds_store4(void* base, int idx, float v0, float 
 
 // gfx950 LDS transpose read: the 16 lanes of a group each point at 4 contiguous bf16 of a [4 k][16 rows] block
 // (lane i: k-row i>>2, rows 4*(i&3)..+3, any row pitch) and receive column i: the 4 k values of row i.
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 __device__ __forceinline__ bf16x4 lds_read_tr4(const __bf16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p));
+  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((kantts_lds_bf16x4*)(p));
 }
 
 // One operand (A when IS_A, else B) of a tile: fetch() issues the global loads, commit() writes LDS.
@@ -269,9 +264,7 @@ __global__ __launch_bounds__(F_THREADS) void gemm_fast_kernel(const kantts_gemm_
   {
     const int gx = gridDim.x, total = gx * gridDim.y;
     if (total >= 64) {
-      const int L = by * gx + bx, k = L & 7, j = L >> 3;
-      const int q = total >> 3, r = total & 7;
-      const int vid = k * q + (k < r ? k : r) + j;
+      const int vid = kantts_xcd_slot(total, by * gx + bx);
       by = vid / gx;
       bx = vid - by * gx;
     }
@@ -288,7 +281,7 @@ __global__ __launch_bounds__(F_THREADS) void gemm_fast_kernel(const kantts_gemm_
   } else if (g.z_taps > 0) {
     ztap = 0;
   }
-  const uint64_t seed_off = g.seed_dev ? *g.seed_dev : 0ull;
+  const uint64_t seed_off = kantts_seed_offset(g.seed_dev);
 
   f32x4 acc[MREP][2];
 #pragma unroll

@@ -34,11 +34,6 @@ __device__ __forceinline__ float lstm_tanh(float x) {
   return fmaf(2.f, lstm_sigmoid<FAST>(2.f * x), -1.f);
 }
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory counter, i.e. it waits
-// until the step's global STORES (saved gates / cell state / outputs: pure outputs, never re-read by this kernel) have
-// been acknowledged by L2 -- two or three such round trips on the critical path of every time step.
-__device__ __forceinline__ void lstm_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // gx: (B,T,ndir*4H) [direction d at column offset d*4H]; out: (B,T,ndir*H)
 // whh: (ndir, 4H, H), bhh: (ndir, 4H); c_out: (ndir,B,T,H);
 // gates_out: (ndir,B,T,H,4) -- the saved activations i, f, g, o of a cell side by side.  The tensor is private to the fwd / bwd
@@ -221,7 +216,7 @@ __global__ __launch_bounds__(LG) void lstm_fwd_kernel(const float* __restrict__ 
         cob[t * LH + j] = c;
       }
       cur ^= 1;
-      lstm_barrier();
+      kantts_lds_barrier();
     }
 #pragma unroll
     for (int u = 0; u < PF; ++u) gq[u] = gn[u];
@@ -362,7 +357,7 @@ __device__ __forceinline__ void lstm_fwd_pair_body(const float* __restrict__ gx,
         }
         if (LSTM_ABL & 1) p_sink += hn;
         cur ^= 1;
-        if (!(LSTM_ABL & 4)) lstm_barrier();
+        if (!(LSTM_ABL & 4)) kantts_lds_barrier();
       }
     }
   }
@@ -509,7 +504,7 @@ __global__ __launch_bounds__(LG) void lstm_bwd_kernel(const float* __restrict__ 
           dg_s[cur][kq * LH + k] = mine;
         dgb[t * LG + kq * LH + k] = mine;
       }
-      lstm_barrier();
+      kantts_lds_barrier();
       {
         float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;  // partial dh of the row's four cells over 32 gradient rows
         if (BF16) {
@@ -661,7 +656,7 @@ __device__ __forceinline__ void lstm_bwd_pair_body(const float* __restrict__ dou
           d0[0] = m0;
           d0[LH] = m1;
         }
-        lstm_barrier();
+        kantts_lds_barrier();
         {
           float a[8];
 #pragma unroll

@@ -161,12 +161,6 @@ extern "C" int kantts_layernorm_bwd(const float* dy, const float* x, const float
 // reduces over 16 lanes with 4 xor-shuffles; the generic kernel above spends a whole wave (and 6-step reductions) on a
 // 512-byte row.  The output / incoming gradient may be bf16: LayerNorm outputs only feed contractions
 // (csrc/gemm_bf16.hip), so the normalised activations never exist in fp32 in HBM.
-typedef unsigned int ln_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ unsigned ln_pack2(float a, float b) {
-  typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-  v2 t = {(__bf16)a, (__bf16)b};
-  return (unsigned&)t;
-}
 __device__ __forceinline__ float ln_sum16(float v) {
   v += __shfl_xor(v, 1, 64);
   v += __shfl_xor(v, 2, 64);
@@ -209,8 +203,8 @@ __global__ __launch_bounds__(256) void ln128_fwd_kernel(const float* __restrict_
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] = (v[e] - mu) * rs * gm[e] + bt[e];
   if (OUT_BF16) {
-    ln_u32x4 w = {ln_pack2(o[0], o[1]), ln_pack2(o[2], o[3]), ln_pack2(o[4], o[5]), ln_pack2(o[6], o[7])};
-    *reinterpret_cast<ln_u32x4*>(reinterpret_cast<__bf16*>(y) + (long long)row * 128 + c0) = w;
+    u32x4 w = {kantts_pack2(o[0], o[1]), kantts_pack2(o[2], o[3]), kantts_pack2(o[4], o[5]), kantts_pack2(o[6], o[7])};
+    *reinterpret_cast<u32x4*>(reinterpret_cast<__bf16*>(y) + (long long)row * 128 + c0) = w;
   } else {
     float4* yp = reinterpret_cast<float4*>(reinterpret_cast<float*>(y) + (long long)row * 128 + c0);
     yp[0] = make_float4(o[0], o[1], o[2], o[3]);
@@ -245,7 +239,7 @@ __global__ __launch_bounds__(256) void ln128_bwd_kernel(const void* __restrict__
     const long long off = (long long)(live ? row : 0) * 128 + c0;
     float d[8], xv[8];
     if (DY_BF16) {
-      const ln_u32x4 q = *reinterpret_cast<const ln_u32x4*>(reinterpret_cast<const __bf16*>(dy) + off);
+      const u32x4 q = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(dy) + off);
       d[0] = __uint_as_float(q.x << 16); d[1] = __uint_as_float(q.x & 0xffff0000u);
       d[2] = __uint_as_float(q.y << 16); d[3] = __uint_as_float(q.y & 0xffff0000u);
       d[4] = __uint_as_float(q.z << 16); d[5] = __uint_as_float(q.z & 0xffff0000u);

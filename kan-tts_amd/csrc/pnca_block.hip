@@ -29,12 +29,6 @@
 // order, the same counter-based dropout indices), so the fused launch and the chain agree to fp32 summation order.
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 // Ablation build only (scripts/build_pbdbg.sh, -DPB_DEBUG; never the product library): KANTTS_PB_DBG is a mask of phases to
 // skip -- forward: 1 attention loops, 2 stores of what backward saves (qkv / contexts / y1 / xn1 / hid), 4 feed-forward
 // phases; backward: 1 dgamma / dbeta atomics, 2 output-projection input gradient, 4 LayerNorm backward arithmetic, 8 dz store,
@@ -76,34 +70,6 @@ static int pb_dbg_mask() {
 static_assert((PB_BM + PB_HX) * PB_XP * 2 <= PB_A_BYTES, "Xq tile");
 static_assert(PB_BM * PB_TP * 2 <= PB_T_BYTES, "hidden tile");
 
-__device__ __forceinline__ unsigned pb_pack2(float a, float b) {
-  bf16x4 t = {(__bf16)a, (__bf16)b, (__bf16)0.f, (__bf16)0.f};
-  return ((u32x2&)t).x;
-}
-
-__device__ __forceinline__ void pb_lds16(const float* p, float* r) {
-  const float4* p4 = reinterpret_cast<const float4*>(p);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float4 t = p4[e];
-    r[4 * e + 0] = t.x;
-    r[4 * e + 1] = t.y;
-    r[4 * e + 2] = t.z;
-    r[4 * e + 3] = t.w;
-  }
-}
-__device__ __forceinline__ float pb_dot16(const float* a, const float* b) {
-  float s = 0.f;
-#pragma unroll
-  for (int d = 0; d < PB_DH; ++d) s = fmaf(a[d], b[d], s);
-  return s;
-}
-__device__ __forceinline__ float pb_dot16l(const float* a, const float* lrow) {
-  float b[PB_DH];
-  pb_lds16(lrow, b);
-  return pb_dot16(a, b);
-}
-
 // [round 6] Row tile of this workgroup.  Neighbouring 32-row tiles share their halo rows (the band of both attentions, the
 // taps' rows), and consecutive workgroup ids are dealt to the 8 XCDs in turn, each with its own L2: in id order every halo row
 // was fetched from HBM / the memory-side cache by two XCDs.  XCD k (= id % 8) owns a contiguous band of tiles instead
@@ -112,8 +78,7 @@ __device__ __forceinline__ float pb_dot16l(const float* a, const float* lrow) {
 __device__ __forceinline__ int pb_tile(int xcd_band) {
   const int L = blockIdx.x, total = gridDim.x;
   if (!xcd_band || total < 64) return L;
-  const int k = L & 7, j = L >> 3, q = total >> 3, r = total & 7;
-  return k * q + (k < r ? k : r) + j;
+  return kantts_xcd_slot(total, L);
 }
 static int pb_xcd_band() {
   static const bool off = getenv("KANTTS_PNCA_NO_XCD_BAND") != nullptr;
@@ -137,7 +102,7 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_block_fwd_kernel(const kantts
   const int M = g.B * g.L, L = g.L;
   const int tile_id = pb_tile(xcd_band);
   const int m0 = tile_id * PB_BM;
-  const uint64_t seed_off = g.seed_dev ? *g.seed_dev : 0ull;
+  const uint64_t seed_off = kantts_seed_offset(g.seed_dev);
   const __bf16* __restrict__ wq = reinterpret_cast<const __bf16*>(g.wqkv);
   const __bf16* __restrict__ wfx = reinterpret_cast<const __bf16*>(g.wfcx);
   const __bf16* __restrict__ wfh = reinterpret_cast<const __bf16*>(g.wfch);
@@ -307,20 +272,20 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_block_fwd_kernel(const kantts
     const float* ktile = (band ? Hs : KVs) + head * PB_DH;
     const int r0 = band ? row - i : row + PB_HX - i;  // tile row of key j is r0 + j
     float q[PB_DH], o[PB_DH];
-    pb_lds16(&Qs[row * PB_QP + head * PB_DH], q);
+    kantts_lds16(&Qs[row * PB_QP + head * PB_DH], q);
 #pragma unroll
     for (int d = 0; d < PB_DH; ++d) o[d] = 0.f;
     float mx = -INFINITY;
-    for (int j = lo; j <= hi; ++j) mx = fmaxf(mx, pb_dot16l(q, ktile + (r0 + j) * PB_KP) * 0.25f);
+    for (int j = lo; j <= hi; ++j) mx = fmaxf(mx, kantts_dot16l(q, ktile + (r0 + j) * PB_KP) * 0.25f);
     float l = 0.f;
     const uint64_t rng_row = (((uint64_t)head * g.B + b) * L + i) * (uint64_t)L;
     KanttsDropSeq drop(g.att_p, (band ? g.seed_h : g.seed_x) + seed_off);
     for (int j = lo; j <= hi; ++j) {
-      const float e = expf(pb_dot16l(q, ktile + (r0 + j) * PB_KP) * 0.25f - mx);
+      const float e = expf(kantts_dot16l(q, ktile + (r0 + j) * PB_KP) * 0.25f - mx);
       l += e;
       const float ed = e * drop.scale(rng_row + j);
       float vv[PB_DH];
-      pb_lds16(ktile + (r0 + j) * PB_KP + PB_C, vv);
+      kantts_lds16(ktile + (r0 + j) * PB_KP + PB_C, vv);
 #pragma unroll
       for (int d = 0; d < PB_DH; ++d) o[d] = fmaf(ed, vv[d], o[d]);
     }
@@ -338,8 +303,8 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_block_fwd_kernel(const kantts
         *reinterpret_cast<float4*>(od + 4 * e) = make_float4(o[4 * e], o[4 * e + 1], o[4 * e + 2], o[4 * e + 3]);
       (band ? g.lse_h : g.lse_x)[((long long)b * (PB_C / PB_DH) + head) * L + i] = (hi >= lo) ? (mx + logf(l)) : 0.f;
     }
-    u32x4 p0 = {pb_pack2(o[0], o[1]), pb_pack2(o[2], o[3]), pb_pack2(o[4], o[5]), pb_pack2(o[6], o[7])};
-    u32x4 p1 = {pb_pack2(o[8], o[9]), pb_pack2(o[10], o[11]), pb_pack2(o[12], o[13]), pb_pack2(o[14], o[15])};
+    u32x4 p0 = {kantts_pack2_of4(o[0], o[1]), kantts_pack2_of4(o[2], o[3]), kantts_pack2_of4(o[4], o[5]), kantts_pack2_of4(o[6], o[7])};
+    u32x4 p1 = {kantts_pack2_of4(o[8], o[9]), kantts_pack2_of4(o[10], o[11]), kantts_pack2_of4(o[12], o[13]), kantts_pack2_of4(o[14], o[15])};
     *reinterpret_cast<u32x4*>(&Cs[row * PB_CP + band * PB_C + head * PB_DH]) = p0;
     *reinterpret_cast<u32x4*>(&Cs[row * PB_CP + band * PB_C + head * PB_DH + 8]) = p1;
   }
@@ -422,7 +387,7 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_block_fwd_kernel(const kantts
       const float* o = y1v[b];
       const float z0 = (o[0] - mu[b]) * rs[b] * l1g.x + l1b.x, z1 = (o[1] - mu[b]) * rs[b] * l1g.y + l1b.y;
       const float z2 = (o[2] - mu[b]) * rs[b] * l1g.z + l1b.z, z3 = (o[3] - mu[b]) * rs[b] * l1g.w + l1b.w;
-      const u32x2 pk = {pb_pack2(z0, z1), pb_pack2(z2, z3)};
+      const u32x2 pk = {kantts_pack2_of4(z0, z1), kantts_pack2_of4(z2, z3)};
       *reinterpret_cast<u32x2*>(&Xs[(b * 16 + li) * PB_XP + n0]) = pk;
       if (!live[b]) continue;
       if (g.xn1 && !PB_DBG(2)) *reinterpret_cast<u32x2*>(reinterpret_cast<__bf16*>(g.xn1) + m * PB_C + n0) = pk;
@@ -475,7 +440,7 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_block_fwd_kernel(const kantts
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[r] = 0.f;
           }
-          const u32x2 pk = {pb_pack2(o[0], o[1]), pb_pack2(o[2], o[3])};
+          const u32x2 pk = {kantts_pack2_of4(o[0], o[1]), kantts_pack2_of4(o[2], o[3])};
           *reinterpret_cast<u32x2*>(&Ts[tok * PB_TP + f0]) = pk;
         }
       }
@@ -562,7 +527,7 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_block_fwd_kernel(const kantts
       const float z0 = (o[0] - mu[b]) * rs[b] * l2g.x + l2b.x, z1 = (o[1] - mu[b]) * rs[b] * l2g.y + l2b.y;
       const float z2 = (o[2] - mu[b]) * rs[b] * l2g.z + l2b.z, z3 = (o[3] - mu[b]) * rs[b] * l2g.w + l2b.w;
       if (g.ln2_out_bf16) {
-        const u32x2 pk = {pb_pack2(z0, z1), pb_pack2(z2, z3)};
+        const u32x2 pk = {kantts_pack2_of4(z0, z1), kantts_pack2_of4(z2, z3)};
         *reinterpret_cast<u32x2*>(reinterpret_cast<__bf16*>(g.ln2_out) + m * PB_C + n0) = pk;
       } else {
         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(g.ln2_out) + m * PB_C + n0) = (f32x4){z0, z1, z2, z3};
@@ -647,7 +612,7 @@ __device__ __forceinline__ void pnca_block_bwd_body(const kantts_pnca_block_bwd_
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, kg = lane >> 4;
   const int M = g.M;
   const int m0 = tile_id * PB_BM;
-  const uint64_t seed_off = g.seed_dev ? *g.seed_dev : 0ull;
+  const uint64_t seed_off = kantts_seed_offset(g.seed_dev);
   const __bf16* __restrict__ wt1 = reinterpret_cast<const __bf16*>(g.wt1);  // W1^T (128 x F)
   const __bf16* __restrict__ wxt = reinterpret_cast<const __bf16*>(g.wfcxT);
   const __bf16* __restrict__ wht = reinterpret_cast<const __bf16*>(g.wfchT);
@@ -685,10 +650,10 @@ __device__ __forceinline__ void pnca_block_bwd_body(const kantts_pnca_block_bwd_
         a = make_float4(lo4[0], lo4[1], lo4[2], lo4[3]);
         b = make_float4(hi4[0], hi4[1], hi4[2], hi4[3]);
       }
-      v.x = pb_pack2(a.x, a.y);
-      v.y = pb_pack2(a.z, a.w);
-      v.z = pb_pack2(b.x, b.y);
-      v.w = pb_pack2(b.z, b.w);
+      v.x = kantts_pack2_of4(a.x, a.y);
+      v.y = kantts_pack2_of4(a.z, a.w);
+      v.z = kantts_pack2_of4(b.x, b.y);
+      v.w = kantts_pack2_of4(b.z, b.w);
     }
     *reinterpret_cast<u32x4*>(&Xs[j * PB_XP + ch * 8]) = v;
   }
@@ -748,7 +713,7 @@ __device__ __forceinline__ void pnca_block_bwd_body(const kantts_pnca_block_bwd_
           float o[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) o[r] = (gv[r] > 0.f) ? acc[a][b][r] * g.alpha1 : 0.f;
-          const u32x2 pk = {pb_pack2(o[0], o[1]), pb_pack2(o[2], o[3])};
+          const u32x2 pk = {kantts_pack2_of4(o[0], o[1]), kantts_pack2_of4(o[2], o[3])};
           *reinterpret_cast<u32x2*>(&Ts[tok * PB_TP + f0]) = pk;
         }
       }
@@ -807,7 +772,7 @@ __device__ __forceinline__ void pnca_block_bwd_body(const kantts_pnca_block_bwd_
       const f32x4 v = *reinterpret_cast<const f32x4*>(&Ex[(((nq * 2 + kh) * 2 + b) * 64 + lane) * 4]);
       const f32x4 s = (kh ? acc2[1][b] : acc2[0][b]) + v;
       // the chain stores dh in the dtype of the normalised rows (bf16) and the LayerNorm backward reads that
-      const unsigned p01 = pb_pack2(s[0], s[1]), p23 = pb_pack2(s[2], s[3]);
+      const unsigned p01 = kantts_pack2_of4(s[0], s[1]), p23 = kantts_pack2_of4(s[2], s[3]);
       dh[b][0] = __uint_as_float(p01 << 16); dh[b][1] = __uint_as_float(p01 & 0xffff0000u);
       dh[b][2] = __uint_as_float(p23 << 16); dh[b][3] = __uint_as_float(p23 & 0xffff0000u);
       if (!live[b]) dh[b][0] = dh[b][1] = dh[b][2] = dh[b][3] = 0.f;
@@ -878,7 +843,7 @@ __device__ __forceinline__ void pnca_block_bwd_body(const kantts_pnca_block_bwd_
       float o[4] = {g1v[b][0], g1v[b][1], g1v[b][2], g1v[b][3]};
       if (g.fc_p > 0.f) kantts_dropout_scale4(g.fc_p, g.fc_seed + seed_off, (uint64_t)m * (uint64_t)PB_C + (uint64_t)n0, o);
       if (!live[b]) o[0] = o[1] = o[2] = o[3] = 0.f;
-      const u32x2 pk = {pb_pack2(o[0], o[1]), pb_pack2(o[2], o[3])};
+      const u32x2 pk = {kantts_pack2_of4(o[0], o[1]), kantts_pack2_of4(o[2], o[3])};
       *reinterpret_cast<u32x2*>(&Xs[(b * 16 + li) * PB_XP + n0]) = pk;
     }
     // dgamma / dbeta of LN1: sum over the tile's 32 tokens (16 lanes x 2) -> this workgroup's row of the workspace; the
@@ -993,7 +958,7 @@ __device__ __forceinline__ void pnca_attn_qkv_bwd_body(const kantts_pnca_attn_bw
   const int L = g.L, H = PB_C / PB_DH;
   const long long M = (long long)g.B * L;
   const int m0 = tile_id * PB_BM;
-  const uint64_t seed_off = g.seed_dev ? *g.seed_dev : 0ull;
+  const uint64_t seed_off = kantts_seed_offset(g.seed_dev);
   const int bw_x = g.bw_dev ? *g.bw_dev : g.bw_x, bw_h = g.bw_dev ? *g.bw_dev : g.bw_h;
   const __bf16* __restrict__ wt = reinterpret_cast<const __bf16*>(g.wqkvT);  // W_qkv^T (128 x 384)
   const float* dummy = reinterpret_cast<const float*>(g.wqkvT);
@@ -1095,9 +1060,9 @@ __device__ __forceinline__ void pnca_attn_qkv_bwd_body(const kantts_pnca_attn_bw
     KanttsDropSeq drop(g.att_p, (band ? g.seed_h : g.seed_x) + seed_off);
     for (int j = lo; j <= hi; ++j) {
       float kj[PB_DH];
-      pb_lds16(ktile + (r0 + j) * PB_KP, kj);
-      const float p = expf(pb_dot16(q, kj) * 0.25f - lse);
-      const float dp = pb_dot16l(go, ktile + (r0 + j) * PB_KP + PB_C) * drop.scale(rng_row + j);
+      kantts_lds16(ktile + (r0 + j) * PB_KP, kj);
+      const float p = expf(kantts_dot16(q, kj) * 0.25f - lse);
+      const float dp = kantts_dot16l(go, ktile + (r0 + j) * PB_KP + PB_C) * drop.scale(rng_row + j);
       const float ds = p * (dp - D) * 0.25f;
 #pragma unroll
       for (int d = 0; d < PB_DH; ++d) dq[d] = fmaf(ds, kj[d], dq[d]);
@@ -1174,14 +1139,14 @@ __device__ __forceinline__ void pnca_attn_qkv_bwd_body(const kantts_pnca_attn_bw
       const int qrow = row + PB_HX + (ip - i);                 // Qs row of query ip
       const int grow = band ? row + PB_HX + (ip - i) : row + (ip - i);
       float qi[PB_DH], gi[PB_DH];
-      pb_lds16(&Qs[qrow * PB_QP + head * PB_DH], qi);
-      pb_lds16(&Gt[grow * PB_QP + head * PB_DH], gi);
+      kantts_lds16(&Qs[qrow * PB_QP + head * PB_DH], qi);
+      kantts_lds16(&Gt[grow * PB_QP + head * PB_DH], gi);
       const float lse = band ? Lh[grow * 8 + head] : Lx[grow * 8 + head];
       const float D = band ? Dh[grow * 8 + head] : Dx[grow * 8 + head];
-      const float p = expf(pb_dot16(qi, kk) * 0.25f - lse);
+      const float p = expf(kantts_dot16(qi, kk) * 0.25f - lse);
       const float dsc = kantts_dropout_scale(g.att_p, seed, ((((uint64_t)head * g.B + b) * L + ip) * (uint64_t)L) + i);
       const float pd = p * dsc;
-      const float dp = pb_dot16(gi, vv) * dsc;
+      const float dp = kantts_dot16(gi, vv) * dsc;
       const float ds = p * (dp - D) * 0.25f;
 #pragma unroll
       for (int d = 0; d < PB_DH; ++d) {
@@ -1203,7 +1168,7 @@ __device__ __forceinline__ void pnca_attn_qkv_bwd_body(const kantts_pnca_attn_bw
     }
   }
   float dqs[PB_DH];
-  pb_lds16(&DQs[row * PB_QP + head * PB_DH], dqs);  // (summed query gradient of (row, head); only the memory-stream threads use it)
+  kantts_lds16(&DQs[row * PB_QP + head * PB_DH], dqs);  // (summed query gradient of (row, head); only the memory-stream threads use it)
   __syncthreads();  // every thread is done with the stage-2 operands: the region becomes the bf16 gradient tile
   seam.stage2_done();
   {
@@ -1214,8 +1179,8 @@ __device__ __forceinline__ void pnca_attn_qkv_bwd_body(const kantts_pnca_attn_bw
         for (int e = 0; e < 4; ++e)
           *reinterpret_cast<float4*>(g.dqkv + m * (3 * PB_C) + col + 4 * e) = make_float4(v[4 * e], v[4 * e + 1], v[4 * e + 2], v[4 * e + 3]);
       }
-      const u32x4 p0 = {pb_pack2(v[0], v[1]), pb_pack2(v[2], v[3]), pb_pack2(v[4], v[5]), pb_pack2(v[6], v[7])};
-      const u32x4 p1 = {pb_pack2(v[8], v[9]), pb_pack2(v[10], v[11]), pb_pack2(v[12], v[13]), pb_pack2(v[14], v[15])};
+      const u32x4 p0 = {kantts_pack2_of4(v[0], v[1]), kantts_pack2_of4(v[2], v[3]), kantts_pack2_of4(v[4], v[5]), kantts_pack2_of4(v[6], v[7])};
+      const u32x4 p1 = {kantts_pack2_of4(v[8], v[9]), kantts_pack2_of4(v[10], v[11]), kantts_pack2_of4(v[12], v[13]), kantts_pack2_of4(v[14], v[15])};
       *reinterpret_cast<u32x4*>(&Tg[row * PB2_GP + col]) = valid ? p0 : (u32x4){0u, 0u, 0u, 0u};
       *reinterpret_cast<u32x4*>(&Tg[row * PB2_GP + col + 8]) = valid ? p1 : (u32x4){0u, 0u, 0u, 0u};
     };
@@ -1243,7 +1208,7 @@ __device__ __forceinline__ void pnca_attn_qkv_bwd_body(const kantts_pnca_attn_bw
     seam.tile_consumed();
 #pragma unroll
     for (int b2 = 0; b2 < 2; ++b2) {  // the chain hands the normalised rows' gradient over in bf16
-      const unsigned p01 = pb_pack2(acc[b2][0], acc[b2][1]), p23 = pb_pack2(acc[b2][2], acc[b2][3]);
+      const unsigned p01 = kantts_pack2_of4(acc[b2][0], acc[b2][1]), p23 = kantts_pack2_of4(acc[b2][2], acc[b2][3]);
       dh[b2][0] = __uint_as_float(p01 << 16); dh[b2][1] = __uint_as_float(p01 & 0xffff0000u);
       dh[b2][2] = __uint_as_float(p23 << 16); dh[b2][3] = __uint_as_float(p23 & 0xffff0000u);
       if (!live[b2]) dh[b2][0] = dh[b2][1] = dh[b2][2] = dh[b2][3] = 0.f;
@@ -1395,8 +1360,6 @@ __global__ __launch_bounds__(PB_THREADS) void pnca_bwd_seam_kernel(const kantts_
   pnca_block_bwd_body<true>(lo, tile_id, Xs, Ts, St, DQs, pre PB_DBG_PASS);
 }
 
-static bool pb_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 extern "C" int kantts_pnca_block_fwd(const kantts_pnca_block_args* gp, void* stream) {
   if (!gp) return KANTTS_E_BADARG;
   const kantts_pnca_block_args& g = *gp;
@@ -1411,7 +1374,7 @@ extern "C" int kantts_pnca_block_fwd(const kantts_pnca_block_args* gp, void* str
   const void* al[] = {g.x, g.xn, g.hkv, g.wqkv, g.bqkv, g.wfcx, g.wfch, g.bfcx, g.bfch, g.ln1_gamma, g.ln1_beta, g.w1, g.w2,
                       g.bias1, g.bias2, g.ln2_gamma, g.ln2_beta, g.qkv, g.ox, g.oh, g.y1, g.xn1, g.hid, g.out, g.ln2_out};
   for (const void* p : al)
-    if (p && !pb_aligned16(p)) return KANTTS_E_UNSUPPORTED;
+    if (p && !kantts_aligned16(p)) return KANTTS_E_UNSUPPORTED;
   const long long M = (long long)g.B * g.L;
   if (M == 0) return KANTTS_OK;
   hipLaunchKernelGGL(pnca_block_fwd_kernel, dim3(kantts_cdiv(M, PB_BM)), dim3(PB_THREADS), 0, (hipStream_t)stream, g, pb_xcd_band() PB_DBG_ARG);
@@ -1431,7 +1394,7 @@ static int pb_check_block_bwd(const kantts_pnca_block_bwd_args& g) {
   if (!g.ws || g.ws_floats < kantts_pnca_block_bwd_ws_floats(g.M)) return KANTTS_E_WORKSPACE;
   const void* al[] = {g.dy, g.hid, g.y1, g.ln1_gamma, g.wt2, g.wt1, g.wfcxT, g.wfchT, g.dz, g.g1, g.d_ox, g.d_oh, g.ws};
   for (const void* p : al)
-    if (!pb_aligned16(p)) return KANTTS_E_UNSUPPORTED;
+    if (!kantts_aligned16(p)) return KANTTS_E_UNSUPPORTED;
   return KANTTS_OK;
 }
 
@@ -1491,7 +1454,7 @@ static int pb_check_attn_bwd(const kantts_pnca_attn_bwd_args& g) {
   if (g.ws_floats < kantts_pnca_block_bwd_ws_floats((int)M)) return KANTTS_E_WORKSPACE;
   const void* al[] = {g.qkv, g.hkv, g.ox, g.oh, g.d_ox, g.d_oh, g.wqkvT, g.x, g.dres, g.ln0_gamma, g.dqkv, g.dhkv, g.dx, g.ws};
   for (const void* p : al)
-    if (p && !pb_aligned16(p)) return KANTTS_E_UNSUPPORTED;
+    if (p && !kantts_aligned16(p)) return KANTTS_E_UNSUPPORTED;
   return KANTTS_OK;
 }
 

@@ -4,10 +4,6 @@
 #pragma once
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 #define SCONV_THREADS 256
 #define SCONV_MAXK 11
 #define SCONV_MAXSTEP 7

@@ -347,8 +347,6 @@ __global__ __launch_bounds__(256) void lr_memory_bwd_kernel(
   *reinterpret_cast<float4*>(out) = acc;
 }
 
-static inline bool lrm_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 extern "C" int kantts_lr_memory_fwd(const float* aug, const float* spk, const float* emo, const int32_t* idx,
                                     const int64_t* valid_lens, const float* pos_enc, float* memory, float* lr_text,
                                     float* lr_spk, float* lr_emo, int B, int N, int Tp, int r, int d_t, int d_s, int d_e,
@@ -359,7 +357,7 @@ extern "C" int kantts_lr_memory_fwd(const float* aug, const float* spk, const fl
   if ((d_t | d_s | d_e) & 3) return KANTTS_E_UNSUPPORTED;  // 16-byte accesses
   for (const void* p : {(const void*)aug, (const void*)spk, (const void*)emo, (const void*)pos_enc, (const void*)memory,
                         (const void*)lr_text, (const void*)lr_spk, (const void*)lr_emo})
-    if (!lrm_aligned16(p)) return KANTTS_E_UNSUPPORTED;
+    if (!kantts_aligned16(p)) return KANTTS_E_UNSUPPORTED;
   const long long total = (long long)B * Tp * ((d_t + d_s + d_e) >> 2);
   if ((total + 255) / 256 > 0x7fffffffLL) return KANTTS_E_UNSUPPORTED;
   if (total == 0) return KANTTS_OK;
@@ -376,7 +374,7 @@ extern "C" int kantts_lr_memory_bwd(const float* d_memory, long long ldm, const 
     return KANTTS_E_BADARG;
   if (((d_t | d_s | d_e) & 3) || (ldm & 3)) return KANTTS_E_UNSUPPORTED;
   for (const void* p : {(const void*)d_memory, (const void*)d_aug, (const void*)d_spk, (const void*)d_emo})
-    if (!lrm_aligned16(p)) return KANTTS_E_UNSUPPORTED;
+    if (!kantts_aligned16(p)) return KANTTS_E_UNSUPPORTED;
   const long long total = (long long)B * N * ((d_t + d_s + d_e) >> 2);
   if ((total + 255) / 256 > 0x7fffffffLL) return KANTTS_E_UNSUPPORTED;
   if (total == 0) return KANTTS_OK;
@@ -499,9 +497,7 @@ __global__ __launch_bounds__(256, 2) void fsmn_fir41_kernel(const float* __restr
   if (xcd_order) {
     const int gx = gridDim.x, total = gx * gridDim.y;
     if (total >= 64) {
-      const int L = by * gx + bx, k = L & 7, j = L >> 3;
-      const int q = total >> 3, r = total & 7;
-      const int vid = k * q + (k < r ? k : r) + j;
+      const int vid = kantts_xcd_slot(total, by * gx + bx);
       by = vid / gx;
       bx = vid - by * gx;
     }

@@ -21,8 +21,6 @@
 //                 the first channel tile) and d_hid row blocks (contraction over symbols), one launch, the role by blockIdx.
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 #define SYB_TAG 0x53594245ull
 #define SYB_MASK_THREADS 1024
 #define SYB_MASK_WAVES (SYB_MASK_THREADS / 64)

@@ -21,24 +21,14 @@
 
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 #define UP_THREADS 512
 
-__device__ __forceinline__ unsigned up_pack2(float a, float b) {
-  typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-  v2 t = {(__bf16)a, (__bf16)b};
-  return (unsigned&)t;
-}
-__device__ __forceinline__ float up_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float up_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 __device__ __forceinline__ unsigned up_lrelu2(unsigned u, float slope) {
-  float a = up_lo(u), b = up_hi(u);
+  float a = kantts_bf16_lo(u), b = kantts_bf16_hi(u);
   a = a > 0.f ? a : a * slope;
   b = b > 0.f ? b : b * slope;
-  return up_pack2(a, b);
+  return kantts_pack2(a, b);
 }
 
 struct UpArgs {
@@ -133,10 +123,10 @@ __global__ __launch_bounds__(UP_THREADS) void upsample_stream_kernel(const UpArg
         if (a.out_bf16) {
           if (a.res) {
             const u32x4 q = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(a.res) + off);
-            o[0] += up_lo(q.x); o[1] += up_hi(q.x); o[2] += up_lo(q.y); o[3] += up_hi(q.y);
-            o[4] += up_lo(q.z); o[5] += up_hi(q.z); o[6] += up_lo(q.w); o[7] += up_hi(q.w);
+            o[0] += kantts_bf16_lo(q.x); o[1] += kantts_bf16_hi(q.x); o[2] += kantts_bf16_lo(q.y); o[3] += kantts_bf16_hi(q.y);
+            o[4] += kantts_bf16_lo(q.z); o[5] += kantts_bf16_hi(q.z); o[6] += kantts_bf16_lo(q.w); o[7] += kantts_bf16_hi(q.w);
           }
-          u32x4 w = {up_pack2(o[0], o[1]), up_pack2(o[2], o[3]), up_pack2(o[4], o[5]), up_pack2(o[6], o[7])};
+          u32x4 w = {kantts_pack2(o[0], o[1]), kantts_pack2(o[2], o[3]), kantts_pack2(o[4], o[5]), kantts_pack2(o[6], o[7])};
           *reinterpret_cast<u32x4*>(reinterpret_cast<__bf16*>(a.out) + off) = w;
         } else {
           if (a.res) {
@@ -159,13 +149,7 @@ __global__ __launch_bounds__(UP_THREADS) void upsample_stream_kernel(const UpArg
 template <int CIN, int COUT, int S>
 static int up_launch(const UpArgs& a, hipStream_t st) {
   constexpr size_t lds = (size_t)S * COUT * 2 * CIN * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&upsample_stream_kernel<CIN, COUT, S>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (int e = kantts_allow_dynamic_lds<&upsample_stream_kernel<CIN, COUT, S>>((int)lds)) return e;
   const int ntile = (a.ntok + 15) / 16;
   int blocks = kantts_cdiv(ntile, UP_THREADS / 64);
   int per_cu = lds > 40 * 1024 ? 2 : 4;  // workgroups a CU can hold (LDS bound)
@@ -175,7 +159,6 @@ static int up_launch(const UpArgs& a, hipStream_t st) {
   hipLaunchKernelGGL((upsample_stream_kernel<CIN, COUT, S>), dim3(blocks), dim3(UP_THREADS), lds, st, a);
   KANTTS_CHECK_LAUNCH();
 }
-
 
 // [round 4] A variant with the weights in REGISTERS (a wave owning one pair of 16-row weight tiles for the whole launch,
 // fragments loaded straight from L2, no LDS, no barrier) was written and measured: 25.8 / 14.4 us per stage against
@@ -209,11 +192,10 @@ extern "C" int kantts_upsample_stream(const void* x_bf16, const void* wp_bf16, c
 // is loaded, every 16-byte chunk of the destination stored (the value stored is the chunk loaded at the same index, folded
 // with a running XOR so that no load is dead code).  bench.py runs it with the upsampling stages' algorithmic bytes inside
 // the same 4-launch graph as the real kernels: what a 10-34 MB problem can reach on this chip including its launch ramp.
-typedef unsigned int cr_u32x4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void copy_roof_kernel(const cr_u32x4* __restrict__ src, long long nread,
-                                                       cr_u32x4* __restrict__ dst, long long nwrite) {
+__global__ __launch_bounds__(256) void copy_roof_kernel(const u32x4* __restrict__ src, long long nread,
+                                                       u32x4* __restrict__ dst, long long nwrite) {
   const long long n = nread > nwrite ? nread : nwrite;
-  cr_u32x4 acc = {0u, 0u, 0u, 0u};
+  u32x4 acc = {0u, 0u, 0u, 0u};
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     if (i < nread) acc ^= src[i];
     if (i < nwrite) dst[i] = acc;
@@ -227,6 +209,6 @@ extern "C" int kantts_copy_roof(const void* src, long long read_bytes, void* dst
   long long blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(copy_roof_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     reinterpret_cast<const cr_u32x4*>(src), nr, reinterpret_cast<cr_u32x4*>(dst), nw);
+                     reinterpret_cast<const u32x4*>(src), nr, reinterpret_cast<u32x4*>(dst), nw);
   KANTTS_CHECK_LAUNCH();
 }

@@ -35,7 +35,7 @@ def gcov_all(out):
                 fn = None
         for g in glob.glob(os.path.join(ROOT, "*.gcov")):
             base = os.path.basename(g)
-            if base.endswith((".hip.gcov", ".inc.gcov")) or base == "common.h.gcov":
+            if base.endswith((".hip.gcov", ".inc.gcov")) or base in ("common.h.gcov", "prims.h.gcov"):
                 os.replace(g, os.path.join(out, base))
             else:
                 os.remove(g)

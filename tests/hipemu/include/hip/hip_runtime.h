@@ -40,7 +40,12 @@ enum { hipSuccess = 0 };
 enum { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
 static inline hipError_t hipGetLastError() { return hipSuccess; }
 static inline const char* hipGetErrorString(hipError_t) { return "hipemu"; }
-static inline hipError_t hipFuncSetAttribute(const void*, int, int) { return hipSuccess; }
+// The current device is an ordinal a test can set (hipemu_set_device); attribute calls succeed and are counted per
+// (function, device) for hipemu_attr_calls -- both in runtime.cpp.
+#define HIPEMU_HAS_DEVICES 1  // csrc/prims.h supplies a one-device hipGetDevice of its own without it
+hipError_t hipGetDevice(int* ordinal);
+hipError_t hipSetDevice(int ordinal);
+hipError_t hipFuncSetAttribute(const void* fn, int attr, int value);
 
 // ---- vector types
 #define HIPEMU_VEC(T, N2, N3, N4)                                                           \

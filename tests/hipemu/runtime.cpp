@@ -347,3 +347,28 @@ void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& fn
   body = nullptr;
 }
 }  // namespace hipemu
+
+// ---- devices: a current ordinal, and how often a function attribute was set per (function, device)
+namespace {
+struct AttrCall { const void* fn; int device, count; };
+int cur_device = 0;
+std::vector<AttrCall> attr_calls;
+}  // namespace
+hipError_t hipGetDevice(int* ordinal) { *ordinal = cur_device; return hipSuccess; }
+hipError_t hipSetDevice(int ordinal) { cur_device = ordinal; return hipSuccess; }
+hipError_t hipFuncSetAttribute(const void* fn, int, int) {
+  for (AttrCall& c : attr_calls)
+    if (c.fn == fn && c.device == cur_device) { ++c.count; return hipSuccess; }
+  attr_calls.push_back({fn, cur_device, 1});
+  return hipSuccess;
+}
+extern "C" void hipemu_set_device(int ordinal) { cur_device = ordinal; }
+// the table so far, oldest entry first: fills up to `cap` rows of (function, device, count), returns the number of rows
+extern "C" int hipemu_attr_calls(const void** fns, int* devices, int* counts, int cap) {
+  for (int i = 0; i < (int)attr_calls.size() && i < cap; ++i) {
+    fns[i] = attr_calls[i].fn;
+    devices[i] = attr_calls[i].device;
+    counts[i] = attr_calls[i].count;
+  }
+  return (int)attr_calls.size();
+}
